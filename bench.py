@@ -4,8 +4,13 @@
 One "step" = one pass of the whole hot path over a batch of synthetic traces already
 resident in HBM.  Prints ONE JSON line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3stream|4shard]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3stream|4shard] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run builds the workload, warms up, times the K steps and prints the headline line.  --full adds everything
+else: per-kernel times and roofline, the passes each waited for, the device's state, the workload's result check, the
+streaming leg, the short configs[2] / configs[3] measurements and the CPU baseline.  --dump-outputs DIR writes what the
+last timed step computed (window table, decoded results, per-trace statistics) as DIR/<name>.npy.
 
 Workloads (BASELINE.json `configs`; the default -- the driver's line -- is configs[1]):
   --config 1        configs[1]: 1024 noise replicas per GPU of the 71-round file_source_test stand-in
@@ -38,6 +43,8 @@ HBM_PEAK_GBS = 8000.0         # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0
 HBM_ACHIEVABLE_GBS = 6300.0   # what a plain streaming kernel reaches on this part (same guide) -- `frac_of_achievable`
 RN16_WIN, EPC_WIN = 250, 1370
 PER_WINDOW_WS = 24 * 3 + 48 + 144      # window table + two compact lists + result + scores (bytes)
+DUMP_BYTES = 64_000_000       # --dump-outputs: at most this many bytes of arrays in all
+DUMP_SEED = 20261015          # --dump-outputs: the row sample of tables that do not fit (fixed: the same rows run after run)
 
 
 def _usable_cores():
@@ -241,6 +248,46 @@ def streaming_leg(torch, rfid, wl, args, device):
         ctx.close()
 
 
+def timed_path_outputs(ctx, budget):
+    """What a caller of the timed path receives from its last pass: the window table and the decoded results (ordered by
+    trace and window; the pass runs without scores) and the per-trace statistics.  -> {name: array}, one array per record
+    field: float fields as float32 (bit for bit), integer fields as float64 (exact).  When the arrays would exceed `budget`
+    bytes, every table keeps the same share of its rows, drawn with a fixed seed (the same rows for the same shapes);
+    `windows_row` / `stats_row` are the rows kept (the results share the windows' rows)."""
+    w, r, _ = ctx.batch_windows(want_scores=False)
+    st = ctx.batch_stats()
+    groups = [("windows", (("windows", w), ("results", r))), ("stats", (("stats", st),))]
+
+    def fields(a):
+        return [f for f in a.dtype.names if not f.endswith("_")]
+
+    def row_bytes(a):
+        return sum((4 if a.dtype[f].base.kind == "f" else 8) * int(np.prod(a.dtype[f].shape)) for f in fields(a))
+
+    sizes = [(len(tabs[0][1]), 8 + sum(row_bytes(a) for _, a in tabs)) for _, tabs in groups]
+    total = sum(n * b for n, b in sizes)
+    budget -= 256 * sum(1 + sum(len(fields(a)) for _, a in tabs) for _, tabs in groups)     # (each file's .npy header)
+    share = 1.0 if total <= budget else budget / total
+    out = {}
+    for (gname, tabs), (n, _) in zip(groups, sizes):
+        if share < 1.0:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, int(n * share), replace=False))
+        else:
+            rows = np.arange(n)
+        out[gname + "_row"] = rows.astype(np.float64)
+        for tname, a in tabs:
+            for f in fields(a):
+                v = a[f][rows]
+                out["%s_%s" % (tname, f)] = np.ascontiguousarray(v, dtype=np.float32 if v.dtype.kind == "f" else np.float64)
+    return out
+
+
+def write_outputs(dirpath, arrays, prefix=""):
+    os.makedirs(dirpath, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirpath, prefix + name + ".npy"), a)
+
+
 WAKE_S = 0.08      # seconds of the workload's own passes before the warm-up steps (see measure())
 
 
@@ -388,12 +435,14 @@ def device_state_static(torch, device):
     return out
 
 
-def measure(torch, wl, steps, warmup, barrier, gather_elapsed=None, n_series=None, back_to_back=True, wake_s=None):
+def measure(torch, wl, steps, warmup, barrier, gather_elapsed=None, n_series=None, back_to_back=True, wake_s=None,
+            full=True, collect=None):
     """`warmup` untimed passes, then exactly `steps` timed passes of the workload's whole chain, enqueued one behind the other
     and waited for once (bracketed by `barrier()`, which synchronises the device; back_to_back=False: every pass waited for
-    by itself, as rounds 1-3 timed it -- the profiled runs use that, a kernel trace then holds no queueing), then an untimed
-    series of the same passes read out through HIP events per kernel.
-    -> dict(elapsed, step_s, k_ms, k_min, k_med, alg, key, n_launch, rep, st, parity_ok, parity_text, roof, ...)"""
+    by itself, as rounds 1-3 timed it -- the profiled runs use that, a kernel trace then holds no queueing), then (full) an
+    untimed series of the same passes read out through HIP events per kernel.  collect(): called right behind the timed
+    region, its value returned as `outputs`.  full=False stops there (the passes' statistics read once).
+    -> dict(elapsed, step_s, k_ms, k_min, k_med, alg, key, n_launch, rep, st, parity_ok, parity_text, roof, outputs, ...)"""
     ctx, data, stride, L, B = wl["ctx"], wl["data"], wl["stride"], wl["L"], wl["B"]
     ctx.batch_plan(B, L)
     ptr = data.data_ptr()
@@ -434,6 +483,13 @@ def measure(torch, wl, steps, warmup, barrier, gather_elapsed=None, n_series=Non
         every = gather_elapsed(elapsed)               # control plane only: every rank's time; the job's = the slowest
         ms_by_rank = [1e3 * t / steps for t in every]
         elapsed = max(every)
+    outputs = collect() if collect is not None else None
+    b2b_ms = (1e3 * elapsed / steps) if back_to_back else None
+    if not full:
+        st = ctx.batch_stats()
+        return dict(elapsed=elapsed, step_s=step_s, b2b_ms=b2b_ms, wake={"passes": wake_n, "ms": round(wake_ms, 1)},
+                    ms_by_rank=ms_by_rank, st=st, n_epc_ok=int(st["n_epc_correct"].sum()), n_windows=int(st["n_windows"].sum()),
+                    outputs=outputs)
 
     # ---- kernel durations: HIP events on the ctx stream around each launch, read in a separate (untimed)
     #      series of the same passes so that the event reads stay out of the timed region -----------------
@@ -477,7 +533,6 @@ def measure(torch, wl, steps, warmup, barrier, gather_elapsed=None, n_series=Non
     dev_state = sampler.summary(r0, r1)
     if isinstance(dev_state, dict):
         dev_state["replay_ms_per_step"] = round(1e3 * (r1 - r0) / steps, 4)
-    b2b_ms = (1e3 * elapsed / steps) if back_to_back else None
     k_ms = {k: statistics.fmean(v) for k, v in k_series.items()}
     k_min = {k: min(v) for k, v in k_series.items()}
     k_med = {k: statistics.median(v) for k, v in k_series.items()}
@@ -551,7 +606,8 @@ def measure(torch, wl, steps, warmup, barrier, gather_elapsed=None, n_series=Non
                           % len(k_series["gate_ms"])}
 
     return dict(elapsed=elapsed, step_s=step_s, b2b_ms=b2b_ms, dev_state=dev_state, wake={"passes": wake_n, "ms": round(wake_ms, 1)}, ms_by_rank=ms_by_rank, k_ms=k_ms, alg=alg, key=key, roof=roof, rep=rep, st=st,
-                n_epc_ok=n_epc_ok, n_windows=n_windows, n_rn16=n_rn16, n_epc=n_epc, parity_ok=parity_ok, parity_text=parity_text)
+                n_epc_ok=n_epc_ok, n_windows=n_windows, n_rn16=n_rn16, n_epc=n_epc, parity_ok=parity_ok, parity_text=parity_text,
+                outputs=outputs)
 
 
 def other_configs(torch, rfid, synth, args, device, rank):
@@ -657,6 +713,11 @@ def main():
     ap.add_argument("--no-back-to-back", action="store_true", help="time every pass waited for by itself (as rounds 1-3 did) instead of the K passes enqueued one behind the other: the profiled runs use it, a kernel trace then holds no queueing")
     ap.add_argument("--stream-replicas", type=int, default=160, help="replicas concatenated into the host-resident stream")
     ap.add_argument("--stream-chunk", type=int, default=32_000_000, help="raw samples per rfid_stream_work call")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-kernel times and roofline, the passes "
+                    "each waited for, the device's state, the result check, the streaming leg, configs[2] / configs[3], the CPU "
+                    "baseline (the --no-* options above apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (window table, "
+                    "decoded results, per-trace statistics; float32 / float64, at most 64 MB in all) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 10 if args.config in ("1", "3stream") else (6 if args.config == "2" else 3)
@@ -698,7 +759,7 @@ def main():
     ctl_device = device if backend == "nccl" else torch.device("cpu")   # where the control-plane tensors live
     n_gpus = world
 
-    dev_static = device_state_static(torch, device) if rank == 0 else {}
+    dev_static = device_state_static(torch, device) if rank == 0 and args.full else {}
     if args.config == "1":
         wl = workload_replicas(torch, rfid, synth, args, device, rank, args.streams or 1024, "configs[1]")
     elif args.config == "4shard":
@@ -727,30 +788,14 @@ def main():
         dist.all_gather(every, mine)
         return [float(t.item()) for t in every]
 
+    def collect():
+        return timed_path_outputs(ctx, DUMP_BYTES / world)
+
     m = measure(torch, wl, args.steps, args.warmup, barrier, gather_elapsed if dist is not None else None,
-                back_to_back=not args.no_back_to_back, wake_s=None if args.wake_ms is None else args.wake_ms / 1e3)
-    elapsed, step_s, k_ms, alg, key, roof, rep = m["elapsed"], m["step_s"], m["k_ms"], m["alg"], m["key"], m["roof"], m["rep"]
-    n_epc_ok, n_windows, n_rn16, n_epc = m["n_epc_ok"], m["n_windows"], m["n_rn16"], m["n_epc"]
-    parity_ok, parity_text = m["parity_ok"], m["parity_text"]
-
-    # every rank's check and device, gathered over the control plane: the job fails if ANY rank's results are wrong
-    dev_name = torch.cuda.get_device_name(device)
-    try:      # (a box without the amdgpu.ids table gives an empty marketing name: the architecture and the CU count say which part it is)
-        pr = torch.cuda.get_device_properties(device)
-        arch = getattr(pr, "gcnArchName", "") or ""
-        dev_name = ("%s %s, %d CUs, %.0f GB" % (dev_name, arch.split(":")[0], pr.multi_processor_count, pr.total_memory / 1e9)).strip()
-    except Exception:
-        pass
-    devices = ["%s (cuda:%d)" % (dev_name, dev_index)]
-    parity_by_rank = [parity_text]
-    if dist is not None:
-        got = [None] * world
-        dist.all_gather_object(got, {"device": devices[0], "parity": parity_text, "ok": bool(parity_ok)})
-        devices = [g["device"] for g in got]
-        parity_by_rank = [g["parity"] for g in got]
-        parity_ok = all(g["ok"] for g in got)
-
-    dominant = max(alg, key=lambda k: k_ms[key[k]])
+                back_to_back=not args.no_back_to_back, wake_s=None if args.wake_ms is None else args.wake_ms / 1e3,
+                full=args.full, collect=collect if args.dump_outputs else None)
+    elapsed, step_s = m["elapsed"], m["step_s"]
+    n_epc_ok, n_windows = m["n_epc_ok"], m["n_windows"]
     total_raw = float(B) * L * args.steps * n_gpus
     out = {
         "metric": "I/Q Msamples/s through matched_filter->gate->tag_decoder (+ EPC decodes/s), 40 kHz FM0",
@@ -761,56 +806,87 @@ def main():
         "timed_region": ("the K passes enqueued one behind the other, one wait at the end (barrier + device synchronisation on both sides)"
                          if m["b2b_ms"] is not None else "every pass waited for by itself (--no-back-to-back)"),
         "device_wake": dict(m["wake"], note="the same passes run for %.0f ms of wall time before the W warm-up steps (the device's clocks after the host's set-up work); untimed" % m["wake"]["ms"]),
-        "passes_each_waited_for": {"ms_per_step": round(statistics.fmean(step_s) * 1e3, 4), "min_ms_per_step": round(min(step_s) * 1e3, 4),
-                                   "median_ms_per_step": round(statistics.median(step_s) * 1e3, 4),
-                                   "note": ("the same K passes, each submitted and waited for by itself (the timed region of rounds 1-3); "
-                                            "outside the timed region" if m["b2b_ms"] is not None else "this IS the timed region")},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "config": {"workload": wl["describe"], "streams_per_gpu": B, "raw_samples_per_stream": L,
                    "hbm_bytes_traces": int(8 * stride * B),
                    "parallelism": "traces sharded per GPU, no collective"},
         "epc_decodes_per_s": round(n_epc_ok * n_gpus * args.steps / elapsed, 1),
-        "decoder_gated_msamples_per_s": round((n_rn16 * RN16_WIN + n_epc * EPC_WIN) / (k_ms["decode_ms"] * 1e-3) / 1e6, 1)
-        if k_ms["decode_ms"] > 0 else None,
         "windows_per_step": n_windows,
-        "parity_check": parity_text if all(t == parity_text for t in parity_by_rank) else
-                        "; ".join("rank %d: %s" % (r, t) for r, t in enumerate(parity_by_rank)),
-        "roofline": roof(dominant),
-        "roofline_by_kernel": {k: roof(k) for k in alg},
-        "front_end_ms": round(k_ms["front_ms"], 4),
         "ms_per_step_by_rank": [round(v, 4) for v in m["ms_by_rank"]],
-        "devices_by_rank": devices,
-        "control_plane": ("torch.distributed/%s: barrier + all_gather of the ranks' times and checks" % backend) if dist is not None
-                         else "single process",
-        "device_state": dict(under_load=m["dev_state"], **dev_static,
-                             note="rank 0's device; under_load = sysfs (pp_dpm_sclk / pp_dpm_mclk starred level, hwmon power and "
-                                  "temperatures) sampled every 4 ms by a thread while the SAME K passes ran once more behind all "
-                                  "measured series (replay_ms_per_step: that run's own time -- the reads perturb it, which is why they are not "
-                                  "inside the timed region); the rest read once before the workload was built"),
+        "control_plane": ("torch.distributed/%s: barrier + all_gather of the ranks' times%s" % (backend, " and checks" if args.full else ""))
+                         if dist is not None else "single process",
+        "full": bool(args.full),
     }
-    if rep["pieces"]:
-        out["long_stream"] = dict(rep, note="traces cut along time into pieces processed at once (avg_ampl, state machine, dc_est) "
-                                  "from guessed start values; accepted only when every piece's run is exact or provably covers its "
-                                  "true start (verified = 1), i.e. the windows ARE those of the sequential scan; no host "
-                                  "synchronisation inside a pass")
+    if args.full or m["b2b_ms"] is None:
+        out["passes_each_waited_for"] = {
+            "ms_per_step": round(statistics.fmean(step_s) * 1e3, 4), "min_ms_per_step": round(min(step_s) * 1e3, 4),
+            "median_ms_per_step": round(statistics.median(step_s) * 1e3, 4),
+            "note": ("the same K passes, each submitted and waited for by itself (the timed region of rounds 1-3); "
+                     "outside the timed region" if m["b2b_ms"] is not None else "this IS the timed region")}
     if B == 1:
         out["single_stream"] = {"raw_msamples_per_s": round(L / (elapsed / args.steps) / 1e6, 2),
                                 "x_realtime_at_2Msps": round(L / (elapsed / args.steps) / 2e6, 1)}
-    # the legs below belong to the single-GPU line (the contract's cpu_baseline is "on rank 0 at N = 1 only"; with N > 1 the
-    # other ranks would sit in the closing barrier while rank 0 works through them)
-    solo = n_gpus == 1
-    if rank == 0 and solo and args.config == "1" and not args.no_stream_leg:
-        out["streaming"] = streaming_leg(torch, rfid, wl, args, device)
-    if rank == 0 and solo and args.config == "1" and not args.no_other_configs:
-        # the other single-GPU BASELINE configurations, each a short measurement of its own OUTSIDE the headline's timed
-        # region (rank 0's GPU only): configs[3]'s per-GPU stream always, configs[2] when the device has room for it
-        out["other_configs"] = other_configs(torch, rfid, synth, args, device, rank)
-    if rank == 0 and solo and not args.no_cpu_baseline:
-        x, what = wl["sample"]()
-        out["cpu_baseline"] = cpu_baseline(x, args.cpu_seconds, fixed_q=wl["fixed_q"], what=what)
-    elif rank == 0:
-        out["cpu_baseline"] = None
+    parity_ok, parity_by_rank = True, []
+    if args.full:
+        k_ms, alg, key, roof, rep = m["k_ms"], m["alg"], m["key"], m["roof"], m["rep"]
+        n_rn16, n_epc = m["n_rn16"], m["n_epc"]
+        parity_ok, parity_text = m["parity_ok"], m["parity_text"]
+
+        # every rank's check and device, gathered over the control plane: the job fails if ANY rank's results are wrong
+        dev_name = torch.cuda.get_device_name(device)
+        try:      # (a box without the amdgpu.ids table gives an empty marketing name: the architecture and the CU count say which part it is)
+            pr = torch.cuda.get_device_properties(device)
+            arch = getattr(pr, "gcnArchName", "") or ""
+            dev_name = ("%s %s, %d CUs, %.0f GB" % (dev_name, arch.split(":")[0], pr.multi_processor_count, pr.total_memory / 1e9)).strip()
+        except Exception:
+            pass
+        devices = ["%s (cuda:%d)" % (dev_name, dev_index)]
+        parity_by_rank = [parity_text]
+        if dist is not None:
+            got = [None] * world
+            dist.all_gather_object(got, {"device": devices[0], "parity": parity_text, "ok": bool(parity_ok)})
+            devices = [g["device"] for g in got]
+            parity_by_rank = [g["parity"] for g in got]
+            parity_ok = all(g["ok"] for g in got)
+
+        dominant = max(alg, key=lambda k: k_ms[key[k]])
+        out.update({
+            "decoder_gated_msamples_per_s": round((n_rn16 * RN16_WIN + n_epc * EPC_WIN) / (k_ms["decode_ms"] * 1e-3) / 1e6, 1)
+            if k_ms["decode_ms"] > 0 else None,
+            "parity_check": parity_text if all(t == parity_text for t in parity_by_rank) else
+                            "; ".join("rank %d: %s" % (r, t) for r, t in enumerate(parity_by_rank)),
+            "roofline": roof(dominant),
+            "roofline_by_kernel": {k: roof(k) for k in alg},
+            "front_end_ms": round(k_ms["front_ms"], 4),
+            "devices_by_rank": devices,
+            "device_state": dict(under_load=m["dev_state"], **dev_static,
+                                 note="rank 0's device; under_load = sysfs (pp_dpm_sclk / pp_dpm_mclk starred level, hwmon power and "
+                                      "temperatures) sampled every 4 ms by a thread while the SAME K passes ran once more behind all "
+                                      "measured series (replay_ms_per_step: that run's own time -- the reads perturb it, which is why they are not "
+                                      "inside the timed region); the rest read once before the workload was built"),
+        })
+        if rep["pieces"]:
+            out["long_stream"] = dict(rep, note="traces cut along time into pieces processed at once (avg_ampl, state machine, dc_est) "
+                                      "from guessed start values; accepted only when every piece's run is exact or provably covers its "
+                                      "true start (verified = 1), i.e. the windows ARE those of the sequential scan; no host "
+                                      "synchronisation inside a pass")
+        # the legs below belong to the single-GPU line (the contract's cpu_baseline is "on rank 0 at N = 1 only"; with N > 1 the
+        # other ranks would sit in the closing barrier while rank 0 works through them)
+        solo = n_gpus == 1
+        if rank == 0 and solo and args.config == "1" and not args.no_stream_leg:
+            out["streaming"] = streaming_leg(torch, rfid, wl, args, device)
+        if rank == 0 and solo and args.config == "1" and not args.no_other_configs:
+            # the other single-GPU BASELINE configurations, each a short measurement of its own OUTSIDE the headline's timed
+            # region (rank 0's GPU only): configs[3]'s per-GPU stream always, configs[2] when the device has room for it
+            out["other_configs"] = other_configs(torch, rfid, synth, args, device, rank)
+        if rank == 0 and solo and not args.no_cpu_baseline:
+            x, what = wl["sample"]()
+            out["cpu_baseline"] = cpu_baseline(x, args.cpu_seconds, fixed_q=wl["fixed_q"], what=what)
+        elif rank == 0:
+            out["cpu_baseline"] = None
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, m["outputs"], prefix=("rank%d_" % rank) if world > 1 else "")
     if rank == 0:
         print(json.dumps(out))
     ctx.close()

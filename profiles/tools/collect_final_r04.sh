@@ -2,10 +2,10 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 O=$R/gpurun_out/final_r04c; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp RFID_LS_CALIBRATE=0
-( cd /tmp; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_1 -o t -- python $R/bench.py --config 1 --steps 5 --warmup 2 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/trace_1.log 2>&1 )
+( cd /tmp; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_1 -o t -- python $R/bench.py --full --config 1 --steps 5 --warmup 2 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/trace_1.log 2>&1 )
 cp $O/trace_1/t_kernel_stats.csv $O/kernel_stats_1.csv
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  ( cd /tmp; timeout 400 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_1_$ctr -o f -- python $R/bench.py --config 1 --steps 2 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/pmc_1_$ctr.log 2>&1 )
+  ( cd /tmp; timeout 400 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_1_$ctr -o f -- python $R/bench.py --full --config 1 --steps 2 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/pmc_1_$ctr.log 2>&1 )
 done
 python - $O 1 > $O/pmc_1.csv <<'PY'
 import csv, collections, sys

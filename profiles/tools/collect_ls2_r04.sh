@@ -4,15 +4,15 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 O=$R/gpurun_out/final_r04b; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 for cfg in 2 3stream; do
-  timeout 600 python bench.py --config $cfg > $O/bench_$cfg.json 2> $O/bench_$cfg.err
+  timeout 600 python bench.py --full --config $cfg > $O/bench_$cfg.json 2> $O/bench_$cfg.err
 done
 export RFID_LS_CALIBRATE=0
 for cfg in 2 3stream; do
-  ( cd /tmp; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$cfg -o t -- python $R/bench.py --config $cfg --steps 5 --warmup 2 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/trace_$cfg.log 2>&1 )
+  ( cd /tmp; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$cfg -o t -- python $R/bench.py --full --config $cfg --steps 5 --warmup 2 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/trace_$cfg.log 2>&1 )
   cp $O/trace_$cfg/t_kernel_stats.csv $O/kernel_stats_$cfg.csv 2>/dev/null
 done
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  ( cd /tmp; timeout 400 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_2_$ctr -o f -- python $R/bench.py --config 2 --steps 1 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/pmc_2_$ctr.log 2>&1 )
+  ( cd /tmp; timeout 400 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_2_$ctr -o f -- python $R/bench.py --full --config 2 --steps 1 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/pmc_2_$ctr.log 2>&1 )
 done
 python - $O 2 > $O/pmc_2.csv <<'PY'
 import csv, collections, sys
@@ -36,4 +36,4 @@ PY
 rm -rf $O/trace_* $O/pmc_2_FETCH_SIZE $O/pmc_2_WRITE_SIZE
 ls -la $O
 unset RFID_LS_CALIBRATE
-timeout 600 python bench.py --steps 20 --warmup 5 > $O/bench_1.json 2> $O/bench_1.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_1.json 2> $O/bench_1.err

@@ -9,19 +9,19 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 O=$R/gpurun_out/final_r03; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 for cfg in 1 2 3stream 4shard; do
-  timeout 600 python bench.py --config $cfg > $O/bench_$cfg.json 2> $O/bench_$cfg.err
+  timeout 600 python bench.py --full --config $cfg > $O/bench_$cfg.json 2> $O/bench_$cfg.err
 done
-timeout 300 python bench.py --streams 4096 --no-cpu-baseline --no-stream-leg > $O/bench_1_4096_traces.json 2> $O/bench_1_4096.err
+timeout 300 python bench.py --full --streams 4096 --no-cpu-baseline --no-stream-leg > $O/bench_1_4096_traces.json 2> $O/bench_1_4096.err
 # the profiled runs: without the front-end calibration rfid_ctx_create does (two small batches through both front ends --
 # their launches would sit in the per-kernel averages); the choice of front end is the same for these workloads
 export RFID_LS_CALIBRATE=0
 for cfg in 1 2 3stream 4shard; do
-  ( cd /tmp; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$cfg -o t -- python $R/bench.py --config $cfg --steps 5 --warmup 2 --no-cpu-baseline --no-stream-leg > $O/trace_$cfg.log 2>&1 )
+  ( cd /tmp; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_$cfg -o t -- python $R/bench.py --full --config $cfg --steps 5 --warmup 2 --no-cpu-baseline --no-stream-leg > $O/trace_$cfg.log 2>&1 )
   cp $O/trace_$cfg/t_kernel_stats.csv $O/kernel_stats_$cfg.csv 2>/dev/null
 done
 for cfg in 1 2 3stream; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
-    ( cd /tmp; timeout 400 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_${cfg}_$ctr -o f -- python $R/bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-stream-leg > $O/pmc_${cfg}_$ctr.log 2>&1 )
+    ( cd /tmp; timeout 400 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_${cfg}_$ctr -o f -- python $R/bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-stream-leg > $O/pmc_${cfg}_$ctr.log 2>&1 )
   done
   python - $O $cfg > $O/pmc_$cfg.csv <<'PY'
 import csv, collections, sys

@@ -2,7 +2,7 @@
 # per-launch timeline of configs[2] passes enqueued back to back (both streams): where the next pass's filter parts run
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/lstrace_b2b; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp RFID_LS_CALIBRATE=0 GPU_MAX_HW_QUEUES=8
-( cd /tmp; timeout 400 rocprofv3 --kernel-trace --output-format csv -d $O/t -o t -- python $R/bench.py --config 2 --steps 4 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs > $O/log.txt 2>&1 )
+( cd /tmp; timeout 400 rocprofv3 --kernel-trace --output-format csv -d $O/t -o t -- python $R/bench.py --full --config 2 --steps 4 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs > $O/log.txt 2>&1 )
 python - $O/t/t_kernel_trace.csv > $O/timeline.txt <<'PY'
 import csv, sys
 rows = [r for r in csv.DictReader(open(sys.argv[1])) if "rfidk" in r["Kernel_Name"]]

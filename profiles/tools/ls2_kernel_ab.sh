@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; tag=$1; O=$R/gpurun_out/lsprof_$tag; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp RFID_LS_CALIBRATE=0
 L=$R/gen2-uhf-rfid-reader_amd/lib/librfid_mi355x.so; cp $L /tmp/keep_ls.so; [ -n "$2" ] && cp $R/$2 $L
-( cd /tmp; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -o t -- python $R/bench.py --config ${CFG:-2} --steps 5 --warmup 2 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/log.txt 2>&1 )
+( cd /tmp; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/t -o t -- python $R/bench.py --full --config ${CFG:-2} --steps 5 --warmup 2 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/log.txt 2>&1 )
 python - $O/t/t_kernel_stats.csv $tag <<'PY'
 import csv, sys
 rows = [r for r in csv.DictReader(open(sys.argv[1])) if "rfidk" in r["Name"] and "synth" not in r["Name"]]

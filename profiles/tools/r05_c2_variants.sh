@@ -12,7 +12,7 @@ for spec in "$@"; do
   tag=$(echo $spec | tr ':=,' '___')
   for cfg in ${CFGS:-2}; do
     steps=6; [ $cfg = 3stream ] && steps=20
-    ( timeout 300 env $envs python bench.py --config $cfg --steps $steps --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs > $O/bench_${cfg}_$tag.json 2> $O/bench_${cfg}_$tag.err )
+    ( timeout 300 env $envs python bench.py --full --config $cfg --steps $steps --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs > $O/bench_${cfg}_$tag.json 2> $O/bench_${cfg}_$tag.err )
     python - $O/bench_${cfg}_$tag.json "$cfg $spec" <<'PY'
 import json, sys
 try:

@@ -10,7 +10,7 @@ cp $L /tmp/keep_main.so
 {
 echo "== configs[2] (bench.py --config 2 --steps 6 --warmup 1)"
 BENCH_ARGS="--config 2 --steps 6 --warmup 1"
-run() { tag=$1; shift; ( timeout 300 env "$@" python bench.py $BENCH_ARGS --no-cpu-baseline --no-stream-leg --no-other-configs > $O/bench_$tag.json 2> $O/bench_$tag.err ); line_print $tag; }
+run() { tag=$1; shift; ( timeout 300 env "$@" python bench.py --full $BENCH_ARGS --no-cpu-baseline --no-stream-leg --no-other-configs > $O/bench_$tag.json 2> $O/bench_$tag.err ); line_print $tag; }
 line_print() {
   python - $O/bench_$1.json $1 <<'PY'
 import json, sys

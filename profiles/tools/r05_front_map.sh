@@ -7,7 +7,7 @@ export TMPDIR=/tmp RFID_LS_CALIBRATE=0
 BA="--config 1 --no-cpu-baseline --no-stream-leg --no-other-configs"
 for v in fused:1 pieces:2; do
   tag=${v%%:*}; ls=${v#*:}
-  timeout 300 env RFID_LONG_STREAM=$ls python bench.py $BA --steps 10 --warmup 2 > $O/bench_1_$tag.json 2> $O/bench_1_$tag.err
+  timeout 300 env RFID_LONG_STREAM=$ls python bench.py --full $BA --steps 10 --warmup 2 > $O/bench_1_$tag.json 2> $O/bench_1_$tag.err
   python - $O/bench_1_$tag.json $tag <<'PY'
 import json, sys
 try:
@@ -18,13 +18,13 @@ except Exception as e:
     print(sys.argv[2], "FAILED", repr(e))
 PY
 done 2>&1 | tee $O/summary.txt
-( cd /tmp; timeout 300 env RFID_LONG_STREAM=2 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_pieces -o s -- python $R/bench.py $BA --steps 5 --warmup 1 --no-back-to-back > $O/stats_pieces.log 2>&1 )
+( cd /tmp; timeout 300 env RFID_LONG_STREAM=2 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_pieces -o s -- python $R/bench.py --full $BA --steps 5 --warmup 1 --no-back-to-back > $O/stats_pieces.log 2>&1 )
 cp $O/stats_pieces/s_kernel_stats.csv $O/kernel_stats_1_pieces.csv 2>/dev/null; rm -rf $O/stats_pieces
 for v in fused:1 pieces:2; do
   tag=${v%%:*}; ls=${v#*:}
   for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES" "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
     st=$(echo $set | tr ' ' '_' | cut -c1-30)
-    ( cd /tmp; timeout 300 env RFID_LONG_STREAM=$ls rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/sq_${tag}_$st -o f -- python $R/bench.py $BA --steps 1 --warmup 1 --no-back-to-back > $O/sq_${tag}_$st.log 2>&1 )
+    ( cd /tmp; timeout 300 env RFID_LONG_STREAM=$ls rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/sq_${tag}_$st -o f -- python $R/bench.py --full $BA --steps 1 --warmup 1 --no-back-to-back > $O/sq_${tag}_$st.log 2>&1 )
   done
   python - $O $tag > $O/sq_$tag.txt <<'PY'
 import csv, collections, glob, sys

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/$1; cfg=$2; shift; shift; mkdir -p $O
 export TMPDIR=/tmp RFID_LS_CALIBRATE=0
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  ( cd /tmp; timeout 400 env "$@" rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_${cfg}_$ctr -o f -- python $R/bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/pmc_${cfg}_$ctr.log 2>&1 )
+  ( cd /tmp; timeout 400 env "$@" rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $O/pmc_${cfg}_$ctr -o f -- python $R/bench.py --full --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/pmc_${cfg}_$ctr.log 2>&1 )
 done
 python - $O $cfg > $O/pmc_$cfg.csv <<'PY'
 import csv, collections, sys

@@ -3,7 +3,7 @@
 # usage: r05_stats2.sh <outdir under gpurun_out> <tag> [ENV=VAL ...]
 R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/$1; tag=$2; shift; shift; mkdir -p $O
 export TMPDIR=/tmp RFID_LS_CALIBRATE=0
-( cd /tmp; timeout 400 env "$@" rocprofv3 --kernel-trace --stats --output-format csv -d $O/t_$tag -o t -- python $R/bench.py --config ${CFG:-2} --steps 5 --warmup 2 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/stats_$tag.log 2>&1 )
+( cd /tmp; timeout 400 env "$@" rocprofv3 --kernel-trace --stats --output-format csv -d $O/t_$tag -o t -- python $R/bench.py --full --config ${CFG:-2} --steps 5 --warmup 2 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $O/stats_$tag.log 2>&1 )
 cp $O/t_$tag/t_kernel_stats.csv $O/kernel_stats_$tag.csv 2>/dev/null
 python - $O/kernel_stats_$tag.csv $tag <<'PY' | tee $O/stats_$tag.txt
 import csv, sys

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/${1:-dec}; mkdir -p $O; export
 L=$R/gen2-uhf-rfid-reader_amd/lib/librfid_mi355x.so; cp $L /tmp/keep.so
 for streams in 1024 4096; do for rep in 1 2; do for v in base table; do
   cp $R/scratch/lib_dec_$v.so $L
-  python $R/bench.py --streams $streams --no-cpu-baseline --no-stream-leg --no-other-configs > $O/b.json 2>/dev/null
+  python $R/bench.py --full --streams $streams --no-cpu-baseline --no-stream-leg --no-other-configs > $O/b.json 2>/dev/null
   python - $O/b.json $v $rep $streams <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
@@ -16,9 +16,9 @@ PY
 done; done; done
 for v in base table; do
   cp $R/scratch/lib_dec_$v.so $L
-  ( cd /tmp; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/t_$v -o t -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > /dev/null 2>&1 )
+  ( cd /tmp; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/t_$v -o t -- python $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > /dev/null 2>&1 )
   echo "$v rocprofv3 (Name,Calls,TotalNs,AvgNs,%,MinNs):"; grep "decode_all" $O/t_$v/t_kernel_stats.csv | cut -d, -f1-6 | cut -c1-120
-  ( cd /tmp; timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d $O/p_$v -o p -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > /dev/null 2>&1 )
+  ( cd /tmp; timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU --kernel-trace --output-format csv -d $O/p_$v -o p -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > /dev/null 2>&1 )
   python - $O/p_$v/p_counter_collection.csv $v <<'PY'
 import csv, sys, collections
 agg = collections.defaultdict(list)

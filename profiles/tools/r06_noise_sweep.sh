@@ -5,7 +5,7 @@ out=${1:-gpurun_out/noise}
 mkdir -p $out
 for cfg in 3stream 2; do
   for sg in 0.002 0.03 0.06; do
-    timeout 900 python bench.py --config $cfg --sigma $sg --no-cpu-baseline > $out/bench_${cfg}_s${sg}.json 2> $out/bench_${cfg}_s${sg}.err
+    timeout 900 python bench.py --full --config $cfg --sigma $sg --no-cpu-baseline > $out/bench_${cfg}_s${sg}.json 2> $out/bench_${cfg}_s${sg}.err
     echo "rc=$? cfg=$cfg sigma=$sg" >> $out/summary.txt
     python - $out/bench_${cfg}_s${sg}.json >> $out/summary.txt <<'PY'
 import json, sys
@@ -24,7 +24,7 @@ done
 for cfg in 3stream 2; do
   for ph in 0.6 0.3; do
     sg=0.06
-    timeout 900 python bench.py --config $cfg --sigma $sg --leak-phase $ph --no-cpu-baseline > $out/bench_${cfg}_s${sg}_ph${ph}.json 2> $out/bench_${cfg}_s${sg}_ph${ph}.err
+    timeout 900 python bench.py --full --config $cfg --sigma $sg --leak-phase $ph --no-cpu-baseline > $out/bench_${cfg}_s${sg}_ph${ph}.json 2> $out/bench_${cfg}_s${sg}_ph${ph}.err
     echo "rc=$? cfg=$cfg sigma=$sg leak-phase=$ph" >> $out/summary.txt
     python - $out/bench_${cfg}_s${sg}_ph${ph}.json >> $out/summary.txt <<'PY'
 import json, sys

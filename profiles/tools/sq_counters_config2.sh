@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: sqset.sh <tag> "<counters>"   (configs[2])
 R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$R/gpurun_out/sqset_$1; rm -rf $OUT; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp RFID_LS_CALIBRATE=0
-timeout 300 rocprofv3 --pmc $2 --kernel-trace --output-format csv -d $OUT/c -o f -- python $R/bench.py --config 2 --steps 1 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $OUT/log.txt 2>&1
+timeout 300 rocprofv3 --pmc $2 --kernel-trace --output-format csv -d $OUT/c -o f -- python $R/bench.py --full --config 2 --steps 1 --warmup 1 --no-cpu-baseline --no-stream-leg --no-other-configs --no-back-to-back > $OUT/log.txt 2>&1
 python - $OUT <<'PY'
 import csv, collections, glob, sys
 agg=collections.defaultdict(list)

@@ -21,7 +21,7 @@ def test_bench_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(RFID_BENCH_SHARE_DEVICES="1", RFID_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, os.path.join(ROOT_DIR, "bench.py"), "--gpus", "2", "--streams", "48", "--steps", "2",
-                          "--warmup", "1", "--no-cpu-baseline", "--no-stream-leg"], cwd=ROOT_DIR, env=env,
+                          "--warmup", "1", "--full", "--no-cpu-baseline", "--no-stream-leg"], cwd=ROOT_DIR, env=env,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

@@ -25,7 +25,7 @@ def _bench(args, env_extra, timeout=900):
 def test_bench_control_plane_on_rccl_single_rank():
     """`bench.py --gpus 1` with RFID_BENCH_FORCE_DIST=1: one rank goes through init_process_group / barrier / all_gather /
     all_gather_object on the `nccl` (= RCCL) backend -- the calls the driver's 8-GPU run meets for the first time."""
-    d = _bench(["--gpus", "1", "--streams", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-stream-leg",
+    d = _bench(["--gpus", "1", "--streams", "64", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-stream-leg",
                 "--no-other-configs"],
                dict(RFID_BENCH_FORCE_DIST="1", RFID_BENCH_BACKEND="nccl", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1",
                     MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", HSA_ENABLE_IPC_MODE_LEGACY="0"))
@@ -36,9 +36,9 @@ def test_bench_control_plane_on_rccl_single_rank():
 
 
 def test_bench_other_configs_leg():
-    """The default line carries short measurements of configs[3] (always) and configs[2] (when HBM allows), each with its
+    """The --full line carries short measurements of configs[3] (always) and configs[2] (when HBM allows), each with its
     own result check.  Here at reduced sizes of the headline (64 traces) so that the test stays short."""
-    d = _bench(["--streams", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-stream-leg"], {})
+    d = _bench(["--streams", "64", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-stream-leg"], {})
     oc = d["other_configs"]
     c3 = oc["configs[3] per GPU"]
     assert c3["parity_check"].startswith("ok") and c3["ms_per_step"] > 0 and "FAILED" not in c3
@@ -46,6 +46,33 @@ def test_bench_other_configs_leg():
     c2 = oc["configs[2]"]
     if "skipped" not in c2:
         assert c2["parity_check"].startswith("ok") and c2["windows_per_step"] == 320000 and "FAILED" not in c2
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) prints the headline line and nothing that takes runs of its own; --dump-outputs writes the
+    last timed step's window table, decoded results and per-trace statistics as float32 / float64 .npy files (64 MB at
+    most), the same bytes from run to run, and they hold the workload's truth (every replica 70 of 71 EPCs)."""
+    runs = [_bench(["--streams", "64", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / str(k))], {})
+            for k in range(2)]
+    d = runs[0]
+    assert all(k in d for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["full"] is False
+    assert not any(k in d for k in ("roofline", "device_state", "parity_check", "streaming", "other_configs", "cpu_baseline"))
+    names = sorted(os.listdir(tmp_path / "0"))
+    assert names == sorted(os.listdir(tmp_path / "1")) and "windows_start.npy" in names and "stats_n_epc_correct.npy" in names
+    total = 0
+    out = {}
+    for n in names:
+        a, b = np.load(tmp_path / "0" / n), np.load(tmp_path / "1" / n)
+        assert a.dtype in (np.float32, np.float64), n
+        assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), n
+        total += os.path.getsize(tmp_path / "0" / n)
+        out[n[:-4]] = a
+    assert total <= 64_000_000
+    assert len(out["windows_start"]) == d["windows_per_step"] == 64 * 142
+    assert len(out["stats_n_epc_correct"]) == 64 and (out["stats_n_epc_correct"] == 70).all()
+    epc = out["windows_type"] == 1
+    assert int(epc.sum()) == 64 * 71 and int(out["results_crc_ok"][epc].sum()) == 64 * 70
 
 
 def test_gate_keyed_look_ahead_offline_binary(tmp_path, oracle_mod, synth_mod):
