@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY: importable from tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg.  The product package never imports this module.
-Parity status: unpinned (see oracle/rfid_oracle.h).
+Parity status: pinned to the reference's own blocks by tests/test_reference_blocks.py (see oracle/rfid_oracle.h).
 """
 from __future__ import annotations
 

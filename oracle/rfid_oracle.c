@@ -1,6 +1,6 @@
 /*
  * rfid_oracle.c -- CPU ORACLE (test infrastructure, NOT product code).
- * See rfid_oracle.h for scope, usage rules and the "parity unpinned" statement.
+ * See rfid_oracle.h for scope, usage rules and the parity statement.
  *
  * Every function cites the reference lines it restates (paths relative to
  * /root/reference/gr-rfid/).  Arithmetic types and operation order follow the

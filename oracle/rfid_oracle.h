@@ -9,14 +9,25 @@
  * `cpu_baseline` leg -- as the checker / reported baseline.  The product
  * library (librfid_mi355x.so) never links, loads or calls anything in oracle/.
  *
- * PARITY STATUS: **parity unpinned**.
- *   - The reference ships no golden vectors, known-answer tests or fixtures for
- *     this path (gr-rfid/lib/qa_rfid.cc:30-36 is an empty suite); its one known
- *     answer (README.md:48-53) needs misc/data/file_source_test, which is absent
- *     from the checkout (.MISSING_LARGE_BLOBS:2).
- *   - The reference's .cc files need GNU Radio + Boost headers that this image
- *     lacks, so by the build rules it is "unbuildable here": no oracle/_ref.
- *   - What IS pinned: CRC-16 against the published CRC-16/GENIBUS check value,
+ * PARITY STATUS: **pinned to the reference's own blocks** (gate, tag_decoder, reader).
+ *   - `make -C oracle refblocks` compiles the reference's lib/{gate,tag_decoder,
+ *     reader}_impl.cc and global_vars.cc untouched (Release flags) against the
+ *     stand-in headers of oracle/refshim and links them with oracle/ref_blocks.cc,
+ *     the single-threaded schedule this file models; one binary per set of the
+ *     compile-time constants FIXED_Q / MAX_NUM_QUERIES / NUMBER_UNIQUE_TAGS.
+ *     tests/test_reference_blocks.py compares it with this oracle bit for bit on
+ *     the fixtures and on synthetic traces: gated samples, window starts, RN16
+ *     and EPC bits, h_est, T, reader_state after every window, tag_reads,
+ *     unique_tags_round, magn_squared_samples, the whole reader TX stream (also
+ *     from every gen2_logic_status, at 1 / 2 / 0.8 MHz) and print_results().
+ *   - NOT pinned: the matched filter's summation order (GNU Radio runs VOLK,
+ *     whose order is the build machine's; tests/test_fir_boundary.py bounds it),
+ *     a real GNU Radio scheduler (the pin runs the oracle's schedule, under which
+ *     the reference is chunk-invariant), and the reference's one known answer
+ *     (README.md:48-53), whose trace misc/data/file_source_test is absent from
+ *     the checkout (.MISSING_LARGE_BLOBS:2).  The reference ships no other golden
+ *     vectors (gr-rfid/lib/qa_rfid.cc:30-36 is an empty suite).
+ *   - Also pinned: CRC-16 against the published CRC-16/GENIBUS check value,
  *     the 20 half-period candidates against BASELINE.md section 5, the C/C++
  *     library semantics the reference leans on (tests/test_toolchain_semantics.py)
  *     and end-to-end decode of generator ground truth (README-shaped 71/72/70/1).

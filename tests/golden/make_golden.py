@@ -1,7 +1,8 @@
 """Generates the committed golden fixtures in tests/golden/*.npz.
 
-The reference has no golden vectors for this path and cannot be run here (it needs GNU
-Radio), so these vectors are produced by the CPU oracle (oracle/rfid_oracle.c) on synthetic
+The reference has no golden vectors for this path, so these vectors are produced by the CPU
+oracle (oracle/rfid_oracle.c; pinned to the reference's own blocks by
+tests/test_reference_blocks.py, which also runs those blocks on these fixtures) on synthetic
 traces: inputs (raw complex64 I/Q) plus every value the path computes for them.  They freeze
 the oracle's behaviour (a guard against drift) and give the GPU tests inputs that do not
 depend on numpy's RNG.  Run:  python tests/golden/make_golden.py

@@ -1,6 +1,6 @@
 """Pins for the CPU oracle (oracle/rfid_oracle.c).  The reference ships no golden vectors for
-this path and cannot be built in this image ("parity unpinned", see oracle/rfid_oracle.h), so
-the oracle is anchored on: published constants, the generator's ground truth, the README's
+this path; besides the bit-for-bit comparison with the reference's own blocks
+(tests/test_reference_blocks.py, see oracle/rfid_oracle.h) the oracle is anchored on: published constants, the generator's ground truth, the README's
 known-answer shape, self-consistency across scheduler chunk sizes, and committed fixtures."""
 import ctypes as C
 

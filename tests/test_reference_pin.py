@@ -1,7 +1,8 @@
-"""The pin hooks.  Parity of this repo is UNPINNED: the reference holds no golden vectors for the path, its one known
-answer needs a trace file that is missing from the checkout, and its sources cannot be compiled in this image (no GNU
-Radio, no Boost) -- so the oracle (oracle/rfid_oracle.c) is checked against published constants and against itself only.
-These tests turn that around the day the environment allows it:
+"""The pin hooks that need more than this image has.  The oracle (oracle/rfid_oracle.c) IS pinned to the reference's own
+gate / tag_decoder / reader blocks, compiled untouched against stand-in headers and run under the oracle's schedule
+(tests/test_reference_blocks.py).  What that leaves unpinned -- a real GNU Radio scheduler and VOLK's filter, and the
+reference's one known answer, whose trace file is missing from the checkout -- these tests take up where the
+environment allows it:
 
   * with a real GNU Radio 3.7 (gnuradio-config-info on PATH): `make -C oracle ref` compiles the reference's OWN sources
     against the real headers together with oracle/ref_harness.cc; the harness is run (single-threaded scheduler) on the
@@ -32,7 +33,7 @@ def test_the_hook_is_wired():
         assert "unbuildable" in out.stdout and not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "ref_harness"))
 
 
-@pytest.mark.skipif(not HAVE_GR, reason="no GNU Radio in this image: the reference cannot be compiled (parity stays unpinned)")
+@pytest.mark.skipif(not HAVE_GR, reason="no GNU Radio in this image: the real-scheduler harness cannot be compiled (tests/test_reference_blocks.py pins the blocks)")
 @pytest.mark.parametrize("path", FIXTURES, ids=[os.path.basename(p)[:-4] for p in FIXTURES])
 def test_reference_blocks_against_the_oracle(tmp_path, oracle_mod, path):
     g = np.load(path)
