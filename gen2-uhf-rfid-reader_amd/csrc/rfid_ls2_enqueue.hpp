@@ -6,9 +6,9 @@
 // before including this file.
 #pragma once
 #include <stddef.h>
-#ifndef LS2_FIN_WPB        // waves per workgroup of the dc_est finishing walk: 1 on the device (its workgroups meet device-wide); the
-#define LS2_FIN_WPB 1      // test suite's emulator runs one workgroup at a time and defines 16 (one workgroup of sixteen waves per trace)
-#endif
+#ifndef LS2_FIN_WPB        // waves per workgroup of the dc_est finishing walk: 1 on the device (its workgroups meet device-wide).  The test
+#define LS2_FIN_WPB 1      // suite's emulator is built with 16 (one workgroup of sixteen waves per trace; more with ls2_fin_waves_force())
+#endif                     // and with the device's 1, where it keeps a launch's workgroups resident at once and interleaves them
 #ifndef LS2_LAUNCH_FRONT   // (the includer may give the first pass's launch a form of its own)
 #define LS2_LAUNCH_FRONT LS2_LAUNCH
 #endif
@@ -53,9 +53,12 @@ struct Ls2Layout {
   int dcand_cap;
 };
 // wmax: complete windows a trace can hold (the caller's window table): sizes the dc_est stage's table of gate openings
-// waves per trace of the dc_est finishing walk (its workgroups meet: rfid_ls2.hpp).  The test suite's emulator runs one workgroup at
-// a time: one workgroup of LS2_FIN_WPB waves per trace there
+inline int &ls2_fin_waves_force();
+// waves per trace of the dc_est finishing walk (its workgroups meet: rfid_ls2.hpp).  Built with LS2_FIN_WPB > 1 (the test suite's
+// emulator): one workgroup of LS2_FIN_WPB waves per trace, unless the test hook asks for more
 inline int ls2_fin_waves(int B) {
+  const int f = ls2_fin_waves_force();
+  if (f > 0 && f % LS2_FIN_WPB == 0) return f;
   if (LS2_FIN_WPB > 1) return LS2_FIN_WPB;
   int g = LS2_FIN_TOTAL / (B < 1 ? 1 : B);
   if (g > LS2_FIN_GMAX) g = LS2_FIN_GMAX;
@@ -137,6 +140,7 @@ inline int &ls2_fsm_lanes_min() { static int v = 8192; return v; }   // from thi
 inline int &ls2_chain_slots() { static int v = 2048; return v; }   // slots per workgroup of a chain launch (tests shrink it)
 inline int &ls2_dcb_top_min() { static int v = 64; return v; }   // the dc_est chain walks over groups of blocks when a trace has more blocks than this (tests: 0)
 inline int &ls2_dcb_bias() { static int v = 0; return v; }   // (tests: Ls2Args::dcb_bias)
+inline int &ls2_fin_waves_force() { static int v = 0; return v; }   // waves per trace of the finishing walk when > 0 and a multiple of LS2_FIN_WPB (tests: any G; the library: 0)
 
 #ifdef LS2_LAUNCH
 // One pass (its first launch zeroes Ls2Ctl, the chain flags, the votes, the window buckets and flat_count).  `a` complete but for

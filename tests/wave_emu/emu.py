@@ -17,14 +17,57 @@ sys.path.insert(0, HERE)
 from rfid import _capi as capi  # noqa: E402  (struct dtypes only)
 import build as _build  # noqa: E402
 
-_lib = None
+_libs = {}
+EMU_DEADLOCK = -100   # (emu_driver.cpp: a launch of the call deadlocked or did not end)
+
+SCHEDULES = {"seq": 0, "in-order": 1, "reversed": 2, "random": 3, "late": 4}
+# seq: the workgroups of a launch one after the other in index order (the default).  The others keep them all resident at once,
+# interleaved: the lowest / highest index that can make progress first, a seeded random pick after every wave-level step, or the
+# lower half of each trace's workgroups dispatched only once the others wait or are done (rfid_device_env.h here)
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        _lib = C.CDLL(_build.build())
-    return _lib
+class EmuDeadlock(RuntimeError):
+    """Every live workgroup of a launch waited (at a grid meeting, a flag or a barrier) with nothing left to run -- or, under the
+    concurrent schedules, a workgroup took more wave-level steps than sweep_limit() allows without finishing (it does not end)."""
+
+
+def sweep_limit(n: int = 0, fin_wpb: int = 16) -> int:
+    """wave-level steps a workgroup may take under the concurrent schedules (n > 0 sets it) -> the limit before"""
+    f = lib(fin_wpb).emu_sweep_limit
+    f.restype = C.c_long
+    return int(f(C.c_long(n)))
+
+
+def lib(fin_wpb: int = 16):
+    """fin_wpb: waves per workgroup of the dc_est finishing walk the emulator is built with (16, or the device's 1)"""
+    if fin_wpb not in _libs:
+        L = C.CDLL(_build.build(fin_wpb=fin_wpb))
+        for name in ("emu_gate_stream", "emu_decode_one", "emu_chain_scan2", "emu_mf_stream", "emu_selftest", "emu_chain_scan",
+                     "emu_synth_replicas"):   # (the calls whose result is only a status)
+            getattr(L, name).errcheck = lambda rc, fn, args, L=L: _raise_deadlock(L, fn.__name__) if rc == EMU_DEADLOCK else rc
+        _libs[fin_wpb] = L
+    return _libs[fin_wpb]
+
+
+def _raise_deadlock(L, what):
+    buf = C.create_string_buffer(8192)
+    L.emu_last_error(buf, len(buf))
+    raise EmuDeadlock("%s: %s" % (what, buf.value.decode(errors="replace")))
+
+
+def grid_meet_selftest(gx: int, gy: int = 1, leave=False, schedule: str = "in-order", seed: int = 0, fin_wpb: int = 16):
+    """gx x gy one-wave workgroups meet twice; leave: the last of each row returns between the meetings (True), or loops for
+    ever there ("loop") -> [gy][gx] ones"""
+    L = lib(fin_wpb)
+    L.emu_schedule(SCHEDULES[schedule], C.c_ulonglong(seed))
+    out = np.zeros((gy, gx), dtype=np.int32)
+    try:
+        rc = L.emu_grid_meet_selftest(gx, gy, 2 if leave == "loop" else (1 if leave else 0), C.c_void_p(out.ctypes.data))
+    finally:
+        L.emu_schedule(0, C.c_ulonglong(0))
+    if rc != 0:
+        _raise_deadlock(L, "grid_meet_selftest")
+    return out
 
 
 def batch_process(raw: np.ndarray, lens=None, fixed_q=0, max_num_queries=1000, number_unique_tags=100,
@@ -59,6 +102,8 @@ def batch_process(raw: np.ndarray, lens=None, fixed_q=0, max_num_queries=1000, n
         C.c_void_p(windows.ctypes.data), C.c_void_p(results.ctypes.data), C.c_void_p(scores.ctypes.data),
         C.c_long(cap), C.byref(n), C.c_void_p(stats.ctypes.data),
         C.c_void_p(y.ctypes.data) if y is not None else None, C.c_long(gate_chunk))
+    if rc == EMU_DEADLOCK:
+        _raise_deadlock(lib(), "batch_process")
     assert rc == 0
     k = n.value
     return dict(windows=windows[:k], results=results[:k], scores=scores[:k], stats=stats, y=y)
@@ -71,9 +116,12 @@ LS2_CTL_FIELDS = (["fail", "ok", "n_pieces", "n_heads"] + [f"avg_count{r}" for r
 
 def ls2_process(raw: np.ndarray, lens=None, fixed_q=0, max_num_queries=1000, number_unique_tags=100, min_piece=512,
                 target=131072, state=None, hold_last=False, cuts=None, y_skip=0, chain_slots=64, generous=True, dc_rounds=-1, fsm_lanes=False, dc_two_levels=False, dc_bias=0,
-                fused=False):
+                fused=False, fin_wpb=16, fin_waves=0, schedule="seq", seed=0):
     """batch_process() with the long-stream front end (rfid_ls2.hpp) in place of the sequential gate scan.
+    fin_wpb / fin_waves: the emulator build (waves per workgroup of the finishing walk) and the walk's waves per trace (0: as the
+    library chooses); schedule / seed: how a launch's workgroups are run (SCHEDULES).  A deadlock raises EmuDeadlock.
     -> dict(windows, results, scores, stats, ctl, ok[, consumed])"""
+    lb = lib(fin_wpb)
     raw = np.ascontiguousarray(raw, dtype=np.complex64)
     if raw.ndim == 1:
         raw = raw[None, :]
@@ -92,26 +140,34 @@ def ls2_process(raw: np.ndarray, lens=None, fixed_q=0, max_num_queries=1000, num
     lens_arr = None
     if lens is not None:
         lens_arr = np.ascontiguousarray(lens, dtype=np.int64)
-    lib().emu_ls2_fsm_lanes_min(0 if fsm_lanes else 1 << 30)
-    lib().emu_ls2_dcb_bias(int(dc_bias))   # (ulps added to the first round's centres: what the rounding drift of a long trace does to the ring means)
-    lib().emu_ls2_dcb_top_min(0 if dc_two_levels else 64)   # (the dc_est chain's second level, as on traces of more than 4 096 idle-grid slots)
-    lib().emu_ls2_chain_slots(int(chain_slots))   # (several workgroups per trace in the chain launches, as on long traces)
-    nw = lib().emu_ls2_ctl_words()
+    lb.emu_ls2_fsm_lanes_min(0 if fsm_lanes else 1 << 30)
+    lb.emu_ls2_dcb_bias(int(dc_bias))   # (ulps added to the first round's centres: what the rounding drift of a long trace does to the ring means)
+    lb.emu_ls2_dcb_top_min(0 if dc_two_levels else 64)   # (the dc_est chain's second level, as on traces of more than 4 096 idle-grid slots)
+    lb.emu_ls2_chain_slots(int(chain_slots))   # (several workgroups per trace in the chain launches, as on long traces)
+    lb.emu_ls2_fin_waves(int(fin_waves))
+    lb.emu_schedule(SCHEDULES[schedule], C.c_ulonglong(seed))
+    nw = lb.emu_ls2_ctl_words()
     ctl = np.zeros(nw, dtype=np.int32)
     consumed = np.zeros(1, dtype=np.int32)
     pcs = np.full((4096, 8), -1, dtype=np.int32)
     cuts_arr = None if cuts is None else np.ascontiguousarray(cuts, dtype=np.int32)
-    ok = lib().emu_ls2_process(
-        C.c_void_p(view.ctypes.data), B, C.c_long(stride), C.c_long(L),
-        C.c_void_p(lens_arr.ctypes.data) if lens_arr is not None else None,
-        fixed_q, max_num_queries, number_unique_tags,
-        C.c_void_p(windows.ctypes.data), C.c_void_p(results.ctypes.data), C.c_void_p(scores.ctypes.data),
-        C.c_long(cap), C.byref(n), C.c_void_p(stats.ctypes.data), int(min_piece), int(target),
-        C.c_void_p(ctl.ctypes.data), nw,
-        C.c_void_p(state.ctypes.data) if state is not None else None, 1 if hold_last else 0, C.c_void_p(consumed.ctypes.data),
-        C.c_void_p(pcs.ctypes.data), len(pcs) - 1,
-        C.c_void_p(cuts_arr.ctypes.data) if cuts_arr is not None else None, 0 if cuts_arr is None else len(cuts_arr), int(y_skip), 1 if generous else 0, int(dc_rounds),
-        1 if fused else 0)
+    try:
+        ok = lb.emu_ls2_process(
+            C.c_void_p(view.ctypes.data), B, C.c_long(stride), C.c_long(L),
+            C.c_void_p(lens_arr.ctypes.data) if lens_arr is not None else None,
+            fixed_q, max_num_queries, number_unique_tags,
+            C.c_void_p(windows.ctypes.data), C.c_void_p(results.ctypes.data), C.c_void_p(scores.ctypes.data),
+            C.c_long(cap), C.byref(n), C.c_void_p(stats.ctypes.data), int(min_piece), int(target),
+            C.c_void_p(ctl.ctypes.data), nw,
+            C.c_void_p(state.ctypes.data) if state is not None else None, 1 if hold_last else 0, C.c_void_p(consumed.ctypes.data),
+            C.c_void_p(pcs.ctypes.data), len(pcs) - 1,
+            C.c_void_p(cuts_arr.ctypes.data) if cuts_arr is not None else None, 0 if cuts_arr is None else len(cuts_arr), int(y_skip), 1 if generous else 0, int(dc_rounds),
+            1 if fused else 0)
+    finally:
+        lb.emu_schedule(0, C.c_ulonglong(0))
+        lb.emu_ls2_fin_waves(0)
+    if ok == EMU_DEADLOCK:
+        _raise_deadlock(lb, "ls2_process")
     assert ok >= 0
     k = n.value
     npc = int(np.argmax(pcs[:, 0] < 0)) if (pcs[:, 0] < 0).any() else len(pcs)
@@ -204,6 +260,8 @@ def synth_gen2(plan, sigma: float = 0.0, seed: int = 0, replica: int = 0) -> np.
     fn.restype = C.c_long
     n = fn(C.byref(p), C.c_void_p(slots.ctypes.data), C.c_long(len(slots)), C.c_void_p(out.ctypes.data),
            C.c_long(plan.n_raw), C.c_float(sigma), C.c_ulonglong(seed), C.c_long(replica))
+    if n == EMU_DEADLOCK:
+        _raise_deadlock(lib(), "synth_gen2")
     assert n == plan.n_raw, (n, plan.n_raw)
     return out.copy()
 

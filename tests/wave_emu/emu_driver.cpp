@@ -3,12 +3,21 @@
 // Runs the unmodified kernel source gen2-uhf-rfid-reader_amd/csrc/rfid_kernels.hpp on a
 // lock-step 64-lane host emulator so the kernel logic (indices, state machine, ring
 // handling, reductions) can be compared with the oracle in the GPU-less CI container.
-// Built by tests/wave_emu/build.py into tests/wave_emu/librfid_wave_emu.so; nothing in the
-// product imports or links it.
+// Built by tests/wave_emu/build.py into tests/wave_emu/librfid_wave_emu.so (and, with the
+// device's LS2_FIN_WPB = 1, librfid_wave_emu_wpb1.so); nothing in the product imports or links it.
+// How the workgroups of a launch are run (one at a time, or resident at once under a seeded
+// schedule) is emu_schedule()'s: see emu::launch below.
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <semaphore.h>
+#include <sys/mman.h>
+
+#include <algorithm>
 #include <functional>
+#include <random>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include <rfid_device_env.h>
@@ -16,18 +25,20 @@
 #include "rfid_kernels.hpp"
 #include "rfid_gen2_host.h"
 #define LS2_DCB_SNAPS_N 2   // (a unit's gate openings go through LDS two at a time here: the in-between writes are exercised)
-#define LS2_FIN_WPB 16   // (one workgroup at a time here: the finishing walk's waves of a trace share ONE workgroup)
+#ifndef LS2_FIN_WPB       // (build.py builds both: 16 -- the finishing walk's waves of a trace share one workgroup by default, or two and
+#define LS2_FIN_WPB 16    // more with ls2_fin_waves_force() -- and the device's 1, one-wave workgroups that meet, under a concurrent schedule)
+#endif
 #define LS2_LAUNCH(kernel, gx, gy, block, args) \
-  emu::launch(emu::Idx3{(unsigned)(gx), (unsigned)(gy), 1}, emu::Idx3{(unsigned)(block), 1, 1}, [&]() { rfidk::kernel(args); })
+  emu::launch(emu::Idx3{(unsigned)(gx), (unsigned)(gy), 1}, emu::Idx3{(unsigned)(block), 1, 1}, [&]() { rfidk::kernel(args); }, #kernel)
 #include "rfid_ls2_enqueue.hpp"
 
 namespace emu {
 
-Block *g_blk = nullptr;
-Fiber *g_cur = nullptr;
-Idx3 g_block_idx, g_grid_dim, g_block_dim;
-ucontext_t g_sched;
-static const std::function<void()> *g_body = nullptr;
+thread_local Block *g_blk = nullptr;
+thread_local Fiber *g_cur = nullptr;
+thread_local Idx3 g_block_idx, g_grid_dim, g_block_dim;
+thread_local ucontext_t g_sched;
+static thread_local const std::function<void()> *g_body = nullptr;
 
 void yield() { swapcontext(&g_cur->ctx, &g_sched); }
 
@@ -37,74 +48,279 @@ static void fiber_entry() {
   swapcontext(&g_cur->ctx, &g_sched);
 }
 
-void launch(Idx3 grid, Idx3 block, const std::function<void()> &body) {
-  g_grid_dim = grid;
-  g_block_dim = block;
-  g_body = &body;
-  const int nthreads = (int)(block.x * block.y * block.z);
-  const int nwaves = (nthreads + 63) / 64;
+// ---- schedules ----
+// 0: one workgroup at a time in index order, on the calling thread (the default).  The others keep every workgroup of a launch
+// resident at once (up to RESIDENT_LANES lanes; the rest is dispatched in order as workgroups finish), each on a thread of its own:
+// 1 in order (the lowest-index workgroup that can make progress runs), 2 reversed (the highest), 3 random (a seeded pick among the
+// workgroups that can make progress, after every wave-level step), 4 late dispatch (as 1, but the lower half of each trace's
+// workgroups -- blockIdx.x < gridDim.x / 2; the upper half for an odd seed -- is dispatched only once all the others wait or are done)
+enum { SCHED_SEQ = 0, SCHED_IN_ORDER = 1, SCHED_REVERSED = 2, SCHED_RANDOM = 3, SCHED_LATE = 4 };
+static int g_kind = SCHED_SEQ;
+static uint64_t g_seed = 0, g_launch_no = 0;
+constexpr size_t STACK = 256 * 1024;          // per fiber: reserved, committed as it is touched
+// lanes resident at once under the concurrent schedules: 256 one-wave workgroups (a quarter of the finishing walk's 1 024 on the
+// device -- each resident workgroup is a thread with its own copy of every kernel's LDS).  A launch whose workgroups must all be
+// resident to finish (the walk with G x B > 256) is reported as a deadlock, naming how many were resident
+constexpr int RESIDENT_LANES = 16384;
+constexpr int MAX_SLOTS = 256;
+// wave-level steps (sweeps) one workgroup may take under the concurrent schedules before its launch is reported as one that does not
+// end (a livelock: a workgroup that keeps going without ever waiting, e.g. on records no other workgroup will write).  The longest
+// workgroup of the suite's concurrent runs takes some 5 000 (50 x less)
+static long g_sweep_limit = 250000;
+static bool g_failed = false;                 // a launch deadlocked or did not end: the launches behind it in the run return at once
+static std::string g_error;
+
+// a resident workgroup: its fibers with their stacks and, under the concurrent schedules, the OS thread that runs them
+struct Slot {
   Block B;
+  char *stacks = nullptr;
+  size_t n_stacks = 0;
+  Idx3 grid, block, idx;
+  const std::function<void()> *body = nullptr;
+  long sweeps = 0;
+  bool live = false;
+  uint64_t stalled_at = ~0ull;      // the scheduler's epoch at its last step without progress
+  // hand-off (concurrent schedules)
+  std::thread th;
+  sem_t go;
+  int cmd = 0, quantum = 1;
+  bool progressed = false;
+};
+static sem_t g_back;
+static std::vector<Slot *> g_pool;
+
+static void ensure_stacks(Slot &S, size_t n) {
+  if (n <= S.n_stacks) return;
+  if (S.stacks) munmap(S.stacks, S.n_stacks * STACK);
+  void *p = mmap(nullptr, n * STACK, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+  if (p == MAP_FAILED) { perror("[emu] fiber stacks"); abort(); }
+  S.stacks = (char *)p;
+  S.n_stacks = n;
+}
+
+// (on the slot's own thread: the thread-local state is that thread's)
+static void start_wg(Slot &S) {
+  g_grid_dim = S.grid; g_block_dim = S.block; g_block_idx = S.idx; g_body = S.body;
+  const int nthreads = (int)(S.block.x * S.block.y * S.block.z), nwaves = (nthreads + 63) / 64;
+  Block &B = S.B;
+  ensure_stacks(S, (size_t)nthreads);
   B.nthreads = nthreads;
   B.fibers.resize((size_t)nthreads);
-  for (auto &f : B.fibers) f.stack.resize(256 * 1024);
-  for (unsigned bz = 0; bz < grid.z; ++bz)
-    for (unsigned by = 0; by < grid.y; ++by)
-      for (unsigned bx = 0; bx < grid.x; ++bx) {
-        g_block_idx = Idx3{bx, by, bz};
-        B.xbuf.assign((size_t)nwaves * 2 * 64, 0);
-        B.wave_arrived.assign((size_t)nwaves, 0);
-        B.wave_gen.assign((size_t)nwaves, 0);
-        B.block_arrived = 0;
-        B.block_gen = 0;
-        g_blk = &B;
-        for (int t = 0; t < nthreads; ++t) {
-          Fiber &f = B.fibers[(size_t)t];
-          f.tid = Idx3{(unsigned)t, 0, 0};
-          f.done = false;
-          f.wave_calls = 0;
-          f.block_calls = 0;
-          getcontext(&f.ctx);
-          f.ctx.uc_stack.ss_sp = f.stack.data();
-          f.ctx.uc_stack.ss_size = f.stack.size();
-          f.ctx.uc_link = &g_sched;
-          makecontext(&f.ctx, fiber_entry, 0);
+  B.xbuf.assign((size_t)nwaves * 2 * 64, 0);
+  B.wave_arrived.assign((size_t)nwaves, 0);
+  B.wave_gen.assign((size_t)nwaves, 0);
+  B.block_arrived = 0;
+  B.block_gen = 0;
+  for (int t = 0; t < nthreads; ++t) {
+    Fiber &f = B.fibers[(size_t)t];
+    f.stack = S.stacks + (size_t)t * STACK;
+    f.tid = Idx3{(unsigned)t, 0, 0};
+    f.done = false;
+    f.wave_calls = f.block_calls = f.grid_calls = 0;
+    f.at = "start";
+    getcontext(&f.ctx);
+    f.ctx.uc_stack.ss_sp = f.stack;
+    f.ctx.uc_stack.ss_size = STACK;
+    f.ctx.uc_link = &g_sched;
+    makecontext(&f.ctx, fiber_entry, 0);
+  }
+  S.sweeps = 0;
+  S.live = true;
+}
+
+// every live fiber of the workgroup once; -> whether any of them got further than re-checking its wait condition
+static bool sweep(Slot &S) {
+  Block &B = S.B;
+  g_blk = &B;
+  const int nthreads = B.nthreads, nwaves = (nthreads + 63) / 64;
+  // watchdog (a kernel that never finishes under lock-step emulation): report where the waves stand
+  if (++S.sweeps == 3000000L && getenv("RFID_EMU_WATCHDOG")) {
+    for (int w = 0; w < nwaves; ++w) {
+      const Fiber &f0 = B.fibers[(size_t)w * 64];
+      fprintf(stderr, "[emu watchdog] wave %d: lane0 done=%d wave_calls=%llu arrived=%d gen=%llu", w, (int)f0.done,
+              (unsigned long long)f0.wave_calls, B.wave_arrived[(size_t)w], (unsigned long long)B.wave_gen[(size_t)w]);
+      for (int l = 1; l < 64 && w * 64 + l < nthreads; ++l)
+        if (B.fibers[(size_t)w * 64 + l].wave_calls != f0.wave_calls || B.fibers[(size_t)w * 64 + l].done != f0.done) {
+          fprintf(stderr, " | lane %d: done=%d wave_calls=%llu", l, (int)B.fibers[(size_t)w * 64 + l].done,
+                  (unsigned long long)B.fibers[(size_t)w * 64 + l].wave_calls);
+          break;
         }
-        int remaining = nthreads;
-        long sweeps = 0;
-        while (remaining > 0) {
-          // watchdog (a kernel that never finishes under lock-step emulation): report where the waves stand
-          if (++sweeps == 3000000L && getenv("RFID_EMU_WATCHDOG")) {
-            for (int w = 0; w < nwaves; ++w) {
-              const Fiber &f0 = B.fibers[(size_t)w * 64];
-              fprintf(stderr, "[emu watchdog] wave %d: lane0 done=%d wave_calls=%llu arrived=%d gen=%llu", w, (int)f0.done,
-                      (unsigned long long)f0.wave_calls, B.wave_arrived[(size_t)w], (unsigned long long)B.wave_gen[(size_t)w]);
-              for (int l = 1; l < 64 && w * 64 + l < nthreads; ++l)
-                if (B.fibers[(size_t)w * 64 + l].wave_calls != f0.wave_calls || B.fibers[(size_t)w * 64 + l].done != f0.done) {
-                  fprintf(stderr, " | lane %d: done=%d wave_calls=%llu", l, (int)B.fibers[(size_t)w * 64 + l].done,
-                          (unsigned long long)B.fibers[(size_t)w * 64 + l].wave_calls);
-                  break;
-                }
-              fprintf(stderr, "\n");
-            }
-            abort();
-          }
-          remaining = 0;
-          for (int t = 0; t < nthreads; ++t) {
-            Fiber &f = B.fibers[(size_t)t];
-            if (f.done) continue;
-            g_cur = &f;
-            swapcontext(&g_sched, &f.ctx);
-            if (!f.done) remaining++;
-          }
-        }
-      }
+      fprintf(stderr, "\n");
+    }
+    abort();
+  }
+  bool moved = false;
+  int remaining = 0;
+  for (int t = 0; t < nthreads; ++t) {
+    Fiber &f = B.fibers[(size_t)t];
+    if (f.done) continue;
+    const uint64_t p0 = f.position();
+    g_cur = &f;
+    swapcontext(&g_sched, &f.ctx);
+    if (f.position() != p0) moved = true;
+    if (!f.done) remaining++;
+  }
   g_blk = nullptr;
   g_cur = nullptr;
+  S.live = remaining > 0;
+  return moved;
+}
+
+static void slot_main(Slot *S) {
+  for (;;) {
+    sem_wait(&S->go);
+    if (S->cmd == 0) {
+      start_wg(*S);
+      S->progressed = true;
+    } else {
+      bool any = false;
+      for (int q = 0; q < S->quantum; ++q) {
+        const bool m = sweep(*S);
+        any = any || m;
+        if (!m || !S->live) break;
+      }
+      S->progressed = any;
+    }
+    sem_post(&g_back);
+  }
+}
+
+static Slot *pool_slot(size_t k) {
+  if (g_pool.empty()) sem_init(&g_back, 0, 0);
+  while (g_pool.size() <= k) {
+    Slot *S = new Slot;
+    sem_init(&S->go, 0, 0);
+    S->th = std::thread(slot_main, S);
+    S->th.detach();
+    g_pool.push_back(S);
+  }
+  return g_pool[k];
+}
+static void on_slot(Slot *S, int cmd, int quantum) {
+  S->cmd = cmd; S->quantum = quantum;
+  sem_post(&S->go);
+  sem_wait(&g_back);
+}
+
+static void report_deadlock(const char *name, Idx3 grid, Idx3 block, const std::vector<Slot *> &stuck, const char *why = nullptr) {
+  char line[512];
+  snprintf(line, sizeof(line), "%s in %s (grid %u x %u, %u threads): %s --", why ? "no end" : "deadlock", name, grid.x, grid.y, block.x,
+           why ? why : "every live workgroup waits");
+  std::string m = line;
+  int shown = 0;
+  for (const Slot *S : stuck) {
+    if (shown++ == 24) { m += " ..."; break; }
+    const Fiber *f0 = nullptr;
+    int live = 0;
+    for (const Fiber &f : S->B.fibers) if (!f.done) { live++; if (!f0) f0 = &f; }
+    snprintf(line, sizeof(line), " wg (%u,%u): %d lanes live, lane %u at %s (wave ops %llu, block syncs %llu, grid waits %llu);",
+             S->idx.x, S->idx.y, live, f0 ? f0->tid.x : 0u, f0 ? f0->at : "-", f0 ? (unsigned long long)f0->wave_calls : 0ull,
+             f0 ? (unsigned long long)f0->block_calls : 0ull, f0 ? (unsigned long long)f0->grid_calls : 0ull);
+    m += line;
+  }
+  g_error = m;
+  g_failed = true;
+}
+
+static Slot g_seq_slot;   // (schedule 0: on the calling thread)
+
+void launch(Idx3 grid, Idx3 block, const std::function<void()> &body, const char *name) {
+  if (g_failed) return;
+  const long total = (long)grid.x * grid.y * grid.z;
+  if (total <= 0) return;
+  auto idx_of = [&](long i) { return Idx3{(unsigned)(i % grid.x), (unsigned)((i / grid.x) % grid.y), (unsigned)(i / ((long)grid.x * grid.y))}; };
+  if (g_kind == SCHED_SEQ) {
+    Slot &S = g_seq_slot;
+    S.grid = grid; S.block = block; S.body = &body;
+    for (long i = 0; i < total; ++i) {
+      S.idx = idx_of(i);
+      start_wg(S);
+      while (S.live)
+        if (!sweep(S) && S.live) {   // (nothing else runs: it waits for ever)
+          report_deadlock(name, grid, block, std::vector<Slot *>{&S});
+          S.live = false;
+          return;
+        }
+    }
+    return;
+  }
+  const int nthreads = (int)(block.x * block.y * block.z);
+  int cap = RESIDENT_LANES / (nthreads > 0 ? nthreads : 1);
+  cap = cap < 1 ? 1 : (cap > MAX_SLOTS ? MAX_SLOTS : cap);
+  std::mt19937_64 rng(g_seed * 0x9E3779B97F4A7C15ull + (++g_launch_no));
+  // dispatch order; late: held back until every dispatched workgroup waits or is done
+  std::vector<long> pending, late;
+  for (long j = 0; j < total; ++j) {
+    const long i = j;   // (dispatch is in index order, as the device's; `reversed` runs the highest-index RESIDENT workgroup first)
+    const unsigned x = idx_of(i).x;
+    if (g_kind == SCHED_LATE && grid.x >= 2 && ((g_seed & 1) ? x >= (grid.x + 1) / 2 : x < grid.x / 2)) late.push_back(i);
+    else pending.push_back(i);
+  }
+  size_t next = 0;
+  bool late_released = false;
+  std::vector<Slot *> active, free_slots;
+  for (int k = cap - 1; k >= 0; --k) free_slots.push_back(pool_slot((size_t)k));
+  uint64_t epoch = 0;
+  const int quantum = (g_kind == SCHED_RANDOM) ? 1 : 256;
+  for (;;) {
+    while (!free_slots.empty() && next < pending.size()) {
+      Slot *S = free_slots.back();
+      free_slots.pop_back();
+      S->grid = grid; S->block = block; S->body = &body; S->idx = idx_of(pending[next++]);
+      S->stalled_at = ~0ull;
+      on_slot(S, 0, 0);
+      active.push_back(S);
+      epoch++;
+    }
+    if (active.empty() && next == pending.size()) {
+      if (late_released || late.empty()) break;
+    }
+    std::vector<Slot *> can;
+    for (Slot *S : active) if (S->stalled_at != epoch) can.push_back(S);
+    if (can.empty()) {
+      if (!late_released && !late.empty()) {
+        late_released = true;
+        pending.insert(pending.end(), late.begin(), late.end());
+        continue;
+      }
+      report_deadlock(name, grid, block, active);
+      if (next < pending.size()) {   // (residency: the workgroups that would have let them go on were never dispatched)
+        char why[160];
+        snprintf(why, sizeof(why), " [%zu of the launch's %ld workgroups resident, at most %d at once]", active.size(), total, cap);
+        g_error += why;
+      }
+      for (Slot *S : active) S->live = false;
+      return;
+    }
+    Slot *S = (g_kind == SCHED_RANDOM) ? can[(size_t)(rng() % can.size())] : (g_kind == SCHED_REVERSED) ? can.back() : can.front();
+    on_slot(S, 1, quantum);
+    if (S->progressed) epoch++;
+    else S->stalled_at = epoch;
+    if (S->live && S->sweeps >= g_sweep_limit) {
+      char why[200];
+      snprintf(why, sizeof(why), "workgroup (%u,%u) took %ld wave-level steps without finishing (limit %ld)", S->idx.x, S->idx.y, S->sweeps,
+               g_sweep_limit);
+      report_deadlock(name, grid, block, active, why);
+      for (Slot *R : active) R->live = false;
+      return;
+    }
+    if (!S->live) {
+      active.erase(std::find(active.begin(), active.end(), S));
+      free_slots.push_back(S);
+    }
+  }
 }
 
 }  // namespace emu
 
 using namespace rfidk;
+
+constexpr int EMU_DEADLOCK = -100;   // a launch of the run deadlocked or did not end (emu_last_error says where)
+// every entry point that launches starts a run: no failure of an earlier run carries over, and the schedule depends on the seed alone
+struct EmuRun {
+  EmuRun() { emu::g_failed = false; emu::g_launch_no = 0; }
+  int rc(int ok) const { return emu::g_failed ? EMU_DEADLOCK : ok; }
+};
 
 extern "C" {
 
@@ -114,6 +330,7 @@ int emu_batch_process(const float *raw, int B, long stride, long n_raw, const in
                       int max_num_queries, int number_unique_tags, rfid_window *windows,
                       rfid_decode_result *results, rfid_scores *scores, long cap, long *n_windows,
                       rfid_stream_stats *stats, float *y_out, long gate_chunk) {
+  EmuRun run;
   const long n_dec = n_raw / DECIM;
   long y_stride = (n_dec + 1) & ~1L;
   if (y_stride < 2) y_stride = 2;
@@ -195,7 +412,7 @@ int emu_batch_process(const float *raw, int B, long stride, long n_raw, const in
     }
   }
   *n_windows = total;
-  return 0;
+  return run.rc(0);
 }
 
 // The long-stream front end (rfid_ls2.hpp) in place of the sequential gate scan: mf -> pieces / avg_ampl / state machine /
@@ -209,6 +426,7 @@ int emu_ls2_process(const float *raw, int B, long stride, long n_raw, const int6
                     rfid_stream_stats *stats, int min_piece, int target, int *ctl_out, int ctl_cap,
                     void *state_blob, int hold_last, int *consumed_out, int *pieces_out, int pieces_cap,
                     const int *cuts, int n_cuts, int y_skip, int generous, int dc_rounds, int fused) {
+  EmuRun run;
   const long n_dec_all = n_raw / DECIM;
   const long n_dec = n_dec_all - y_skip;   // (y_skip: leading outputs that only exist to give the filter its history)
   long y_stride = (n_dec_all + 1) & ~1L;
@@ -334,9 +552,42 @@ int emu_ls2_process(const float *raw, int B, long stride, long n_raw, const int6
     }
   }
   *n_windows = total;
-  return ok;
+  return run.rc(ok);
 }
 int emu_ls2_ctl_words(void) { return (int)(sizeof(Ls2Ctl) / 4); }
+// waves per trace of the finishing walk (0: as the library chooses; else a multiple of LS2_FIN_WPB)
+void emu_ls2_fin_waves(int n) { ls2_fin_waves_force() = n; }
+int emu_fin_wpb(void) { return LS2_FIN_WPB; }
+// how the workgroups of a launch are run (rfid_device_env.h here; emu::launch): 0 one at a time in index order, 1 in order, 2
+// reversed, 3 random, 4 late dispatch -- all of a launch's workgroups resident at once for 1 - 4
+void emu_schedule(int kind, unsigned long long seed) { emu::g_kind = kind; emu::g_seed = seed; emu::g_launch_no = 0; }
+// wave-level steps a workgroup may take under the concurrent schedules (emu::g_sweep_limit) -> the limit before
+long emu_sweep_limit(long n) { const long o = emu::g_sweep_limit; if (n > 0) emu::g_sweep_limit = n; return o; }
+// the report of the last launch that deadlocked (empty if none since the last run began) -> its length
+int emu_last_error(char *buf, int cap) {
+  if (cap > 0) { snprintf(buf, (size_t)cap, "%s", emu::g_failed ? emu::g_error.c_str() : ""); }
+  return emu::g_failed ? (int)emu::g_error.size() : 0;
+}
+// self-test of the deadlock report: `gx` x `gy` one-wave workgroups meet twice (as the finishing walk does); with `leave` set the last
+// workgroup of each row returns before the second meeting, so the others wait for ever (leave 2: it loops for ever instead).  out[gy][gx]: 1 per workgroup through
+// both meetings.  -> 0, or EMU_DEADLOCK
+int emu_grid_meet_selftest(int gx, int gy, int leave, int *out) {
+  EmuRun run;
+  std::vector<int> bar((size_t)gy, 0);
+  emu::launch(emu::Idx3{(unsigned)gx, (unsigned)gy, 1}, emu::Idx3{64, 1, 1}, [&]() {
+    const int tid = (int)threadIdx.x, s = (int)blockIdx.y;
+    int *counter = bar.data() + s;
+    wv::block_sync();
+    wv::grid_meet(counter, (int)gridDim.x, tid);
+    wv::block_sync();
+    if (leave == 1 && blockIdx.x == gridDim.x - 1) return;
+    if (leave == 2 && blockIdx.x == gridDim.x - 1) for (;;) wv::wave_sync();   // (goes on for ever without waiting: no end)
+    wv::grid_meet(counter, 2 * (int)gridDim.x, tid);
+    wv::block_sync();
+    if (tid == 0) out[(size_t)s * gx + blockIdx.x] = 1;
+  }, "grid_meet_selftest");
+  return run.rc(0);
+}
 // slots per workgroup of the chain launches (the library: 4096): small values make the emulated traces span several workgroups
 void emu_ls2_chain_slots(int n) { ls2_chain_slots() = n; }
 void emu_ls2_dcb_top_min(int n) { ls2_dcb_top_min() = n; }
@@ -348,6 +599,7 @@ void emu_ls2_fsm_lanes_min(int n) { ls2_fsm_lanes_min() = n; }
 // seek_type: -1 none, 0 SEEK_RN16, 1 SEEK_EPC applied before the scan (gate_impl.cc:112-123).
 int emu_gate_stream(void *state_blob, const float *in, int n_in, int seek_type, float *out, int *consumed,
                     int *written, int *gate_open) {
+  EmuRun run;
   GateState *st = reinterpret_cast<GateState *>(state_blob);
   if (seek_type >= 0) {
     st->n_samples = 0;
@@ -366,13 +618,14 @@ int emu_gate_stream(void *state_blob, const float *in, int n_in, int seek_type, 
   *consumed = io[0];
   *written = io[1];
   *gate_open = st->gate_open;
-  return 0;
+  return run.rc(0);
 }
 
 int emu_gate_state_size(void) { return (int)sizeof(GateState); }
 
 // matched filter in streaming form (staging = 24 history samples + new samples)
 int emu_mf_stream(const float *staging, int n_staging, int in_off, int n_out, float *out) {
+  EmuRun run;
   if (n_out <= 0) return 0;
   std::vector<float4> ybuf((size_t)(n_out / 2 + 2));
   MfArgs ma;
@@ -383,11 +636,12 @@ int emu_mf_stream(const float *staging, int n_staging, int in_off, int n_out, fl
   const int tiles = (n_out + MF_TILE - 1) / MF_TILE;
   emu::launch(emu::Idx3{(unsigned)tiles, 1, 1}, emu::Idx3{MF_THREADS, 1, 1}, [&]() { mf_boxcar25_decim5_kernel(ma); });
   memcpy(out, ybuf.data(), sizeof(float2) * (size_t)n_out);
-  return 0;
+  return run.rc(0);
 }
 
 // one window through decode_windows_kernel (input already DC-free, as the decoder block sees it)
 int emu_decode_one(const float *win, int type, rfid_decode_result *res, rfid_scores *scores) {
+  EmuRun run;
   const int wlen = type ? EPC_WIN : RN16_WIN;
   rfid_window w;
   w.stream = 0; w.seq = 0; w.start = 0; w.type = type; w.dc_re = 0.0f; w.dc_im = 0.0f;
@@ -398,32 +652,35 @@ int emu_decode_one(const float *win, int type, rfid_decode_result *res, rfid_sco
   rfidh::t_candidates(da.t_cand, 400000);
   memset(scores, 0, sizeof(*scores));
   emu::launch(emu::Idx3{1, 1, 1}, emu::Idx3{64, 1, 1}, [&]() { decode_windows_kernel(da); });
-  return 0;
+  return run.rc(0);
 }
 
 // primitives self-test kernel
 int emu_selftest(const float *x, const float *num, const float *den, float carry, float *chain_out,
                  float *div_out, float *hyp_out, float *shr_out) {
+  EmuRun run;
   SelfTestArgs a;
   a.x = x; a.num = num; a.den = den; a.carry = carry; a.chain_out = chain_out; a.div_out = div_out;
   a.hyp_out = hyp_out; a.shr_out = shr_out; a.scan_out = nullptr;
   emu::launch(emu::Idx3{1, 1, 1}, emu::Idx3{64, 1, 1}, [&]() { selftest_kernel(a); });
-  return 0;
+  return run.rc(0);
 }
 
 // in-order sum: the integer-scan form against the chain; scan_out[64] = 1 when the scan was provably exact
 int emu_chain_scan(const float *x, float carry, float *chain_out, float *scan_out) {
+  EmuRun run;
   std::vector<float> z(64, 1.0f), o(64 * 3);
   SelfTestArgs a;
   a.x = x; a.num = z.data(); a.den = z.data(); a.carry = carry; a.chain_out = chain_out; a.div_out = o.data();
   a.hyp_out = o.data() + 64; a.shr_out = o.data() + 128; a.scan_out = scan_out;
   emu::launch(emu::Idx3{1, 1, 1}, emu::Idx3{64, 1, 1}, [&]() { selftest_kernel(a); });
-  return 0;
+  return run.rc(0);
 }
 
 // chain_add_auto2 (long-stream front end: the in-order sums from two carries at once) on one step; scanned[0] = 1 when the
 // shared integer-scan form applied
 int emu_chain_scan2(const float *x, float ca, float cb, float *out_a, float *out_b, int *scanned) {
+  EmuRun run;
   struct Args { const float *x; float ca, cb; float *oa, *ob; int *sc; } a = {x, ca, cb, out_a, out_b, scanned};
   emu::launch(emu::Idx3{1, 1, 1}, emu::Idx3{64, 1, 1}, [&]() {
     const int lane = wv::lane_id();
@@ -433,12 +690,13 @@ int emu_chain_scan2(const float *x, float ca, float cb, float *out_a, float *out
     chain_add_auto2(a.ca, a.cb, a.x[lane], lane, va, vb);
     a.oa[lane] = va; a.ob[lane] = vb;
   });
-  return 0;
+  return run.rc(0);
 }
 
 // synthetic-replica generator (workload generator, not on the receive path)
 int emu_synth_replicas(const float *base, long n_raw, float *out, long out_stride, int n_streams, float sigma,
                        unsigned long long seed, long first_replica) {
+  EmuRun run;
   if (n_raw <= 0 || n_streams <= 0) return 0;
   SynthArgs a;
   a.base = reinterpret_cast<const float2 *>(base); a.out = reinterpret_cast<float2 *>(out); a.n_raw = n_raw;
@@ -448,12 +706,13 @@ int emu_synth_replicas(const float *base, long n_raw, float *out, long out_strid
   const long blocks = (n_raw + per_block - 1) / per_block;
   emu::launch(emu::Idx3{(unsigned)blocks, (unsigned)n_streams, 1}, emu::Idx3{SYNTH_THREADS, 1, 1},
               [&]() { synth_replicas_kernel(a); });
-  return 0;
+  return run.rc(0);
 }
 
 // Gen2 trace synthesiser (workload generator): the same host layout as rfid_synth_gen2, the kernel emulated
 long emu_synth_gen2(const rfid_synth_gen2_params *p, const rfid_synth_slot *slots, long n_slots, float *out, long out_cap,
                     float sigma, unsigned long long seed, long replica) {
+  EmuRun run;
   std::vector<Gen2SlotDev> dev;
   const int64_t total = rfidh::gen2_layout(*p, slots, n_slots, &dev);
   if (total < 0 || total > out_cap) return -1;
@@ -464,7 +723,7 @@ long emu_synth_gen2(const rfid_synth_gen2_params *p, const rfid_synth_slot *slot
   for (int k = 0; k < G2_MAX_TAGS; ++k) { a.h_re[k] = p->h_re[k]; a.h_im[k] = p->h_im[k]; }
   a.sigma = sigma; a.key0 = (uint32_t)seed; a.key1 = (uint32_t)(seed >> 32); a.replica = (uint64_t)replica;
   emu::launch(emu::Idx3{(unsigned)dev.size(), 1, 1}, emu::Idx3{G2_THREADS, 1, 1}, [&]() { synth_gen2_kernel(a); });
-  return (long)total;
+  return run.rc(0) ? (long)EMU_DEADLOCK : (long)total;
 }
 
 void emu_philox4x32_10(const uint32_t *ctr, const uint32_t *key, uint32_t *out) {

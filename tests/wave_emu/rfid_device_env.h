@@ -6,6 +6,15 @@
 // every workgroup runs as a set of cooperative fibers (ucontext) that advance in lock step
 // at each wave-level operation.  It is never compiled into, linked with or loaded by
 // librfid_mi355x.so and is not a fallback of any kind: the product has no CPU path.
+//
+// Workgroups of a launch run one after the other in index order (the default), or -- the
+// concurrent schedules of emu_schedule() -- resident at once, each on an OS thread of its own
+// (LDS is `static thread_local`: private to the workgroup), interleaved by a seeded schedule:
+// a single baton passes between the threads, so only one fiber runs at any moment and a run is
+// reproducible.  grid_meet / await wait for real; a schedule step in which every live
+// workgroup waits ends the launch with a deadlock report (emu_last_error), not a hang.
+// The emulator is SEQUENTIALLY CONSISTENT: every store is seen by every later load.  It cannot
+// find a missing fence or an acquire / release error -- the GPU tests are the check for those.
 #pragma once
 #include <math.h>
 #include <stdio.h>
@@ -29,11 +38,16 @@ struct Idx3 { unsigned x, y, z; };
 
 struct Fiber {
   ucontext_t ctx;
-  std::vector<char> stack;
+  char *stack = nullptr;     // (the workgroup slot's lazily committed stacks)
   Idx3 tid;
   bool done = false;
   uint64_t wave_calls = 0;   // number of wave collectives this fiber has entered
   uint64_t block_calls = 0;  // number of block barriers this fiber has entered
+  uint64_t grid_calls = 0;   // number of grid meetings / flag waits / back-offs this fiber has entered
+  const char *at = "start";  // the last of those (for a deadlock report)
+  // every yield lies inside one of those operations, each of which counts on entry: a fiber that was resumed and yields with
+  // the same count has only found its wait condition still false -- it changed nothing
+  uint64_t position() const { return wave_calls + block_calls + grid_calls + (done ? 1 : 0); }
 };
 
 struct Block {
@@ -47,13 +61,14 @@ struct Block {
   uint64_t block_gen = 0;
 };
 
-extern Block *g_blk;
-extern Fiber *g_cur;
-extern Idx3 g_block_idx, g_grid_dim, g_block_dim;
-extern ucontext_t g_sched;
+// per OS thread: the workgroup it runs (concurrent schedules: one thread per resident workgroup)
+extern thread_local Block *g_blk;
+extern thread_local Fiber *g_cur;
+extern thread_local Idx3 g_block_idx, g_grid_dim, g_block_dim;
+extern thread_local ucontext_t g_sched;
 
 void yield();
-void launch(Idx3 grid, Idx3 block, const std::function<void()> &body);
+void launch(Idx3 grid, Idx3 block, const std::function<void()> &body, const char *name = "kernel");
 
 static inline int lanes_in_wave(int wave) {
   int rem = g_blk->nthreads - wave * 64;
@@ -64,6 +79,7 @@ static inline int lanes_in_wave(int wave) {
 static inline void wave_barrier() {
   const int wave = (int)(g_cur->tid.x / 64);
   const uint64_t my = g_cur->wave_calls++;
+  g_cur->at = "wave op";
   if (++g_blk->wave_arrived[wave] == lanes_in_wave(wave)) {
     g_blk->wave_arrived[wave] = 0;
     g_blk->wave_gen[wave] = my + 1;
@@ -95,7 +111,7 @@ static inline float u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 #define RFID_KERNEL(threads) static inline
 #define RFID_KERNEL_OCC(threads, waves) static inline
 #define RFID_DEVICE static inline
-#define RFID_SHARED static
+#define RFID_SHARED alignas(16) static thread_local   // (LDS: one copy per workgroup thread; 16-byte loads and stores go through it)
 #define __device__
 
 namespace wv {
@@ -178,6 +194,7 @@ static inline int f2i(float v) { return (int)v; }
 static inline void block_sync() {
   emu::Block *B = emu::g_blk;
   const uint64_t my = emu::g_cur->block_calls++;
+  emu::g_cur->at = "block_sync";
   int live = 0;
   for (auto &f : B->fibers) if (!f.done) live++;
   if (++B->block_arrived >= live) {
@@ -232,20 +249,30 @@ static inline void pk_add(float2 &acc, const float2 q) {
 }
 static inline void set_priority_high() {}
 template <int P> static inline void set_priority() {}
-static inline void backoff() { emu::yield(); }
+static inline void backoff() { emu::g_cur->grid_calls++; emu::g_cur->at = "backoff"; emu::yield(); }   // (counts as progress: a spin of its own)
 static inline void load4_i32(const int *p, int &a, int &b, int &c, int &d) { a = p[0]; b = p[1]; c = p[2]; d = p[3]; }
 static inline int atomic_add(int *p, int v) { int o = *p; *p = o + v; return o; }
 static inline int atomic_min(int *p, int v) { int o = *p; if (v < o) *p = v; return o; }
 static inline int atomic_max(int *p, int v) { int o = *p; if (v > o) *p = v; return o; }
-// (the emulator runs one workgroup at a time: a launch whose workgroups meet has exactly one here)
-static inline void grid_meet(int *, int, int) { fprintf(stderr, "[emu] grid_meet with more than one workgroup\n"); abort(); }
+// the device form: thread 0 counts in and waits for `target` arrivals, the others wait at the block_sync that follows
+static inline void grid_meet(int *counter, int target, int tid) {
+  emu::g_cur->grid_calls++;
+  emu::g_cur->at = "grid_meet";
+  if (tid == 0) {
+    ++*(volatile int *)counter;
+    while (*(const volatile int *)counter < target) emu::yield();
+  }
+}
 static inline uint64_t load_u64_agent(const uint64_t *p) { return *(const volatile uint64_t *)p; }
 static inline void store_u64_agent(uint64_t *p, uint64_t v) { *(volatile uint64_t *)p = v; }
 static inline void system_release_fence() {}
 static inline void store_i32_system_release(int *p, int v) { *(volatile int *)p = v; }
 static inline void publish(int *flag, int v) { *(volatile int *)flag = v; }
-// (the emulator runs the workgroups of a launch one after the other in index order: a flag of a lower block is set by now)
-static inline void await(const int *flag, int v) { if (*(const volatile int *)flag != v) { fprintf(stderr, "[emu] await on a flag that was never published\n"); abort(); } }
+static inline void await(const int *flag, int v) {
+  emu::g_cur->grid_calls++;
+  emu::g_cur->at = "await";
+  while (*(const volatile int *)flag != v) emu::yield();
+}
 static inline void atomic_or64(uint64_t *p, uint64_t v) { *p |= v; }
 static inline void atomic_and64(uint64_t *p, uint64_t v) { *p &= v; }
 static inline void global_release() {}
