@@ -20,6 +20,7 @@
 
 #include "rfid_host_math.h"
 #include "rfid_kernels.hpp"
+#include "rfid_inventory.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
 // the launch list of the long-stream front end, on the stream named by the enclosing scope's `ls2_stream`
@@ -68,6 +69,7 @@ struct RfidKnobs {
   int dc_rounds = -1;      // RFID_LS2_DC_ROUNDS     0..64: dc_est rounds a long-stream pass enqueues behind the first (-1: by the pass's size -- 0 / 3 / 10; what they leave, the finishing walk takes)
   int la_upload_kernel = 1;  // RFID_LA_UPLOAD_KERNEL  look-ahead: 1 a call's samples are fetched from page-locked memory by a launch, 0 by a transfer
   int front_lds_kb = -1;   // RFID_LS_FRONT_LDS_KB   0..64: extra LDS per workgroup of the long-stream first pass (caps its waves per CU); -1: 10 for long traces
+  int inventory_slots = 0; // RFID_INVENTORY_SLOTS   2..1024 (a power of two): table slots per trace of the inventory stage, read by rfid_batch_plan_inventory (0: the next power of two >= 2 x max_tags_per_trace).  A small table makes frames collide: the stage's later rounds
 };
 
 struct rfid_ctx {
@@ -283,6 +285,17 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
+  // ---- inventory stage (rfid_batch_plan_inventory): lives and dies with the plan ----
+  struct Inventory {
+    void *blk = nullptr;              // one allocation, carved up
+    int max_tags = 0, slots = 0;
+    rfid_tag_entry *d_ent = nullptr, *d_packed = nullptr;   // [B_plan][max_tags] each
+    int *d_counts = nullptr, *d_over = nullptr, *d_off = nullptr, *d_head = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool enqueued = false;            // an rfid_batch_inventory is behind the events
+    int n_streams = 0;                // traces it covered
+  } inv;
+  bool stats_current = false;         // d_stats holds the statistics of the results in d_res (rfid_batch_stats ran behind the last decode)
   int n_chunks_last = 0;   // > 0 when the last pass used the overlapped path
   int fused_last = 0;      // 1 when the last rfid_batch_process pass used front_end_fused_kernel
   float front_ms = 0.0f;
@@ -323,6 +336,7 @@ const KnobEntry g_knob_table[] = {
   {"dc_rounds", "RFID_LS2_DC_ROUNDS", &RfidKnobs::dc_rounds, -1, 64},
   {"la_upload_kernel", "RFID_LA_UPLOAD_KERNEL", &RfidKnobs::la_upload_kernel, 0, 1},
   {"front_lds_kb", "RFID_LS_FRONT_LDS_KB", &RfidKnobs::front_lds_kb, -1, 64},
+  {"inventory_slots", "RFID_INVENTORY_SLOTS", &RfidKnobs::inventory_slots, 0, 1024},
 };
 int clamp_int(long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 // the environment, once per context: values out of range are clamped, anything that is not a number is ignored
@@ -401,6 +415,9 @@ void init_reader_state(rfid_ctx *c) {  // global_vars.cc:34-54
 }
 
 void free_plan(rfid_ctx *c) {
+  if (c->inv.blk) (void)hipFree(c->inv.blk);
+  c->inv.blk = nullptr; c->inv.max_tags = 0; c->inv.enqueued = false;
+  c->stats_current = false;
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
   if (c->alt_y_blk) (void)hipFree(c->alt_y_blk);
@@ -906,6 +923,8 @@ int rfid_ctx_destroy(rfid_ctx *c) {
   if (c->ls2_host) (void)hipHostFree(c->ls2_host);
   for (int i = 0; i < 5; ++i)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
+  for (int i = 0; i < 2; ++i)
+    if (c->inv.ev[i]) (void)hipEventDestroy(c->inv.ev[i]);
   if (c->stream2) {
     (void)hipStreamSynchronize(c->stream2);
     for (int i = 0; i <= rfid_ctx::MAX_CHUNKS; ++i)
@@ -1264,6 +1283,7 @@ static int rfid_batch_gate_impl(rfid_ctx *c, const int *skip_if) {
   a.state = c->d_gstate; a.n_streams = c->B; a.wtab = c->d_wtab; a.wmax = c->wmax; a.wcount = c->d_wcount;
   a.flat = c->d_flat; a.flat_count = c->d_flat_count; a.flat_cap = c->flat_cap; a.mode = 0;
   a.gated = nullptr; a.gated_cap = 0; a.io = nullptr;
+  c->stats_current = false;
   if (!c->ev_valid[1]) { HIPCHK(c, hipEventRecord(c->ev[1], c->stream)); c->ev_valid[1] = true; }
   hipLaunchKernelGGL(gate_scan_kernel, dim3((unsigned)((c->B + GATE_STREAMS_PER_WG - 1) / GATE_STREAMS_PER_WG)), dim3(GATE_THREADS), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
@@ -1303,6 +1323,7 @@ int rfid_batch_decode(rfid_ctx *c, int want_scores) {
   d.ticket = c->d_ticket + (c->ticket_flip & 1);        // (both zero after rfid_ctx_create; every launch zeroes the other one)
   d.ticket_next = c->d_ticket + ((c->ticket_flip & 1) ^ 1);
   c->ticket_flip ^= 1;
+  c->stats_current = false;
   hipLaunchKernelGGL(decode_all_kernel, dim3((unsigned)grid), dim3(64), 0, ts, d);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[3], ts));
@@ -1328,6 +1349,102 @@ int rfid_batch_stats(rfid_ctx *c) {
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[4], ts));
   c->ev_valid[4] = true;
+  c->stats_current = true;
+  return RFID_OK;
+}
+
+// ---- inventory stage: the distinct EPC frames of every trace, built on the device (csrc/rfid_inventory.hpp) ----
+int rfid_batch_plan_inventory(rfid_ctx *c, int max_tags) {
+  if (!c || max_tags < 1) return RFID_ERR_INVALID;
+  if (!c->B_plan) return RFID_ERR_STATE;
+  constexpr int SLOTS_MAX = 1024;
+  if (max_tags > SLOTS_MAX / 2) return fail(c, RFID_ERR_UNSUPPORTED, "rfid_batch_plan_inventory: at most 512 tags per trace");
+  if ((int64_t)max_tags * c->B_plan > 0x7fffffffLL / (int64_t)sizeof(rfid_tag_entry)) return RFID_ERR_UNSUPPORTED;
+  int slots = c->knobs.inventory_slots;
+  if (slots == 0) for (slots = 2; slots < 2 * max_tags; slots *= 2) {}
+  if (slots < 2 || slots > SLOTS_MAX || (slots & (slots - 1))) return fail(c, RFID_ERR_INVALID, "rfid_batch_plan_inventory: inventory_slots is not a power of two in 2..1024");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  rfid_ctx::Inventory &v = c->inv;
+  if (v.blk) HIPCHK(c, hipFree(v.blk));
+  v.blk = nullptr; v.max_tags = 0; v.enqueued = false;
+  for (int i = 0; i < 2; ++i)
+    if (!v.ev[i]) HIPCHK(c, hipEventCreate(&v.ev[i]));
+  auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t sz_e = up256(sizeof(rfid_tag_entry) * (size_t)max_tags * (size_t)c->B_plan), sz_i = up256(sizeof(int) * (size_t)c->B_plan);
+  hipError_t e = hipMalloc(&v.blk, 2 * sz_e + 3 * sz_i + 256);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    v.blk = nullptr;
+    return fail(c, RFID_ERR_HIP, "rfid_batch_plan_inventory: workspace allocation", e);
+  }
+  char *b = (char *)v.blk;
+  v.d_ent = (rfid_tag_entry *)b; b += sz_e; v.d_packed = (rfid_tag_entry *)b; b += sz_e;
+  v.d_counts = (int *)b; b += sz_i; v.d_over = (int *)b; b += sz_i; v.d_off = (int *)b; b += sz_i; v.d_head = (int *)b;
+  v.max_tags = max_tags; v.slots = slots;
+  return RFID_OK;
+}
+
+int rfid_batch_inventory(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Inventory &v = c->inv;
+  if (!c->B || !v.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_inventory: no plan with an inventory workspace (rfid_batch_plan_inventory)");
+  if (!c->stats_current) return fail(c, RFID_ERR_STATE, "rfid_batch_inventory: no pass with statistics yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  // the result set and the statistics c->d_* name are the last pass's; with two sets in flight its decoder and statistics
+  // ran on the second stream: the main stream waits for them, and everything later on it waits for this
+  { int rj = join_tails(c); if (rj) return rj; }
+  InvArgs a;
+  a.res = c->d_res; a.wcount = c->d_wcount; a.stats = c->d_stats; a.wmax = c->wmax; a.n_streams = c->B;
+  a.max_tags = v.max_tags; a.slots = v.slots; a.out = v.d_ent; a.counts = v.d_counts; a.overflow = v.d_over;
+  InvPackArgs p;
+  p.in = v.d_ent; p.counts = v.d_counts; p.overflow = v.d_over; p.n_streams = c->B; p.max_tags = v.max_tags;
+  p.offsets = v.d_off; p.head = v.d_head; p.packed = v.d_packed;
+  HIPCHK(c, hipEventRecord(v.ev[0], c->stream));
+  // one wave per trace; sixteen when a trace can hold thousands of windows (as the statistics kernel)
+  const dim3 block(c->wmax > 2048 ? 64 * INV_MAX_WAVES : 64);
+  if (v.slots <= 128) hipLaunchKernelGGL(inventory_kernel<128>, dim3((unsigned)c->B), block, 0, c->stream, a);
+  else hipLaunchKernelGGL(inventory_kernel<1024>, dim3((unsigned)c->B), block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  const int scan_threads = (c->B >= INV_SCAN_THREADS) ? INV_SCAN_THREADS : ((c->B + 63) & ~63);
+  hipLaunchKernelGGL(inventory_offsets_kernel, dim3(1), dim3((unsigned)scan_threads), 0, c->stream, p);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(inventory_pack_kernel, dim3((unsigned)c->B), dim3(64), 0, c->stream, p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(v.ev[1], c->stream));
+  v.enqueued = true;
+  v.n_streams = c->B;
+  return RFID_OK;
+}
+
+int rfid_batch_get_inventory(rfid_ctx *c, rfid_tag_entry *entries, int64_t cap, int64_t *n, int32_t *counts) {
+  if (!c || !n || cap < 0 || (cap > 0 && !entries)) return RFID_ERR_INVALID;
+  rfid_ctx::Inventory &v = c->inv;
+  if (!v.blk || !v.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_inventory: no rfid_batch_inventory behind this plan");
+  HIPCHK(c, hipSetDevice(c->device));
+  int head[2] = {0, 0};
+  HIPCHK(c, hipMemcpyAsync(head, v.d_head, sizeof(head), hipMemcpyDeviceToHost, c->stream));
+  if (counts) HIPCHK(c, hipMemcpyAsync(counts, v.d_counts, sizeof(int) * (size_t)v.n_streams, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n = head[0];
+  if (head[1] != INV_EMPTY) {
+    snprintf(c->err, sizeof(c->err), "rfid_batch_get_inventory: trace %d holds more than max_tags_per_trace = %d distinct frames", head[1], v.max_tags);
+    return RFID_ERR_CAPACITY;
+  }
+  if (head[0] > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_inventory: cap is smaller than the number of entries");
+  if (head[0] > 0) {
+    HIPCHK(c, hipMemcpyAsync(entries, v.d_packed, sizeof(rfid_tag_entry) * (size_t)head[0], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return RFID_OK;
+}
+
+int rfid_batch_inventory_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  if (!c->inv.blk || !c->inv.enqueued) return RFID_ERR_STATE;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(c->inv.ev[1]));
+  HIPCHK(c, hipEventElapsedTime(ms, c->inv.ev[0], c->inv.ev[1]));
   return RFID_OK;
 }
 

@@ -73,7 +73,10 @@ STATS_DTYPE = np.dtype([("n_queries_sent", "<i4"), ("cur_inventory_round", "<i4"
                         ("n_epc_correct", "<i4"), ("n_unique_tags", "<i4"), ("n_windows", "<i4"),
                         ("n_windows_used", "<i4"), ("status", "<i4"), ("tag_reads", "<i4", (256,))])
 STREAM_WINDOW_DTYPE = np.dtype([("start", "<i8"), ("type", "<i4"), ("reserved_", "<i4"), ("dc_re", "<f4"), ("dc_im", "<f4")])
-assert STREAM_WINDOW_DTYPE.itemsize == 24
+TAG_ENTRY_DTYPE = np.dtype([("stream", "<i4"), ("reads", "<i4"), ("frame", "<u4", (4,)), ("first_seq", "<i4"),
+                            ("last_seq", "<i4"), ("best_seq", "<i4"), ("best_h_re", "<f4"), ("best_h_im", "<f4"),
+                            ("tag_id", "<i4")])
+assert STREAM_WINDOW_DTYPE.itemsize == 24 and TAG_ENTRY_DTYPE.itemsize == 48
 assert WINDOW_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 48
 assert SCORES_DTYPE.itemsize == 144 and STATS_DTYPE.itemsize == 1056
 
@@ -130,6 +133,10 @@ SIGNATURES = {
     "rfid_batch_decode": (_i, [_vp, _i]),
     "rfid_batch_stats": (_i, [_vp]),
     "rfid_batch_process": (_i, [_vp, _vp, _i64, _i64, _vp, _i]),
+    "rfid_batch_plan_inventory": (_i, [_vp, _i]),
+    "rfid_batch_inventory": (_i, [_vp]),
+    "rfid_batch_get_inventory": (_i, [_vp, _vp, _i64, C.POINTER(_i64), _vp]),
+    "rfid_batch_inventory_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

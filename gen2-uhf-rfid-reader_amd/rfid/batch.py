@@ -39,6 +39,8 @@ class BatchDecoder:
         self._dev = None
         self._pinned = None
         self._lens_dev = None
+        self._inv_tags = 0
+        self.last_inventory = None    # (entries, per-trace counts) of the last decode(..., inventory=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -49,6 +51,7 @@ class BatchDecoder:
         if self._planned[0] < n_traces or self._planned[1] < max_len:
             self.ctx.batch_plan(max(n_traces, self._planned[0]), max(max_len, self._planned[1]))
             self._planned = (max(n_traces, self._planned[0]), max(max_len, self._planned[1]))
+            self._inv_tags = 0        # (a new plan drops the inventory workspace)
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -57,10 +60,13 @@ class BatchDecoder:
             self._pinned = torch.empty(need, dtype=torch.float32, pin_memory=True)
         return stride
 
-    def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None):
+    def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
+               inventory: bool = False, max_tags: int = 64):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
-        `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call."""
+        `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
+        of every trace (up to max_tags per trace) are listed on the device behind the pass and kept as
+        `self.last_inventory` = (entries, per-trace counts); the return value is the same."""
         torch = self._torch
         n = len(traces)
         lens = np.array([len(t) for t in traces], dtype=np.int64)
@@ -78,9 +84,16 @@ class BatchDecoder:
             self._lens_dev = torch.from_numpy(lens).to(dev.device, non_blocking=True)
             torch.cuda.current_stream().synchronize()
         t1 = time.perf_counter()
+        if inventory and self._inv_tags != int(max_tags):
+            self.ctx.batch_plan_inventory(int(max_tags))
+            self._inv_tags = int(max_tags)
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
+        if inventory:
+            self.ctx.batch_inventory_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
+        if inventory:
+            self.last_inventory = self.ctx.batch_inventory_fetch()
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -116,24 +129,76 @@ def format_results(stats_row) -> str:
     return "\n".join(lines) + "\n"
 
 
+def merge_inventory(entries: np.ndarray) -> np.ndarray:
+    """Per-trace inventory entries (Context.batch_inventory) -> one entry per distinct frame over all traces: reads
+    summed, `stream` / `first_seq` / `last_seq` / `best_*` those of the trace that read it best (largest |best h|,
+    the lowest trace on ties); ordered by frame.  Host side: the tables are tiny."""
+    entries = np.asarray(entries)
+    if len(entries) == 0:
+        return entries.copy()
+    frames = np.ascontiguousarray(entries["frame"])
+    _, first, inverse = np.unique(frames, axis=0, return_index=True, return_inverse=True)
+    inverse = np.asarray(inverse).reshape(-1)
+    norm = entries["best_h_re"].astype(np.float64) ** 2 + entries["best_h_im"].astype(np.float64) ** 2
+    out = entries[first].copy()
+    for g in range(len(first)):
+        idx = np.flatnonzero(inverse == g)
+        out[g] = entries[idx[int(np.argmax(norm[idx]))]]
+        out[g]["reads"] = int(entries["reads"][idx].sum())
+    return out
+
+
+def frame_fields(frame) -> tuple:
+    """rfid_tag_entry.frame -> (PC as an int, EPC as 24 hex digits), bits MSB first as sent."""
+    w = np.asarray(frame, dtype=np.uint32)
+    j = np.arange(128)
+    bits = ((w[j >> 5] >> (j & 31)) & 1).astype(np.uint8)
+    val = lambda b: int("".join(map(str, b.tolist())), 2)
+    return val(bits[:16]), "%024x" % val(bits[16:112])
+
+
+def format_inventory(entries: np.ndarray) -> str:
+    """One line per entry: EPC (24 hex digits), PC, reads, first / last window seq, 20 log10 |best h|."""
+    lines = ["| EPC                       PC    reads  first   last   best |h| dB"]
+    for e in entries:
+        pc, epc = frame_fields(e["frame"])
+        mag = float(np.hypot(np.float64(e["best_h_re"]), np.float64(e["best_h_im"])))
+        db = 20.0 * np.log10(mag) if mag > 0 else float("-inf")
+        lines.append("| %s  %04x  %5d  %5d  %5d  %8.2f" % (epc, pc, int(e["reads"]), int(e["first_seq"]), int(e["last_seq"]), db))
+    lines.append(" --------------------------")
+    return "\n".join(lines) + "\n"
+
+
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--fixed-q", type=int, default=0)
     ap.add_argument("--max-queries", type=int, default=1000)
+    ap.add_argument("--inventory", action="store_true", help="list the distinct EPCs of every trace (built on the device)")
+    ap.add_argument("--max-tags", type=int, default=64, help="distinct EPCs per trace the inventory has room for (1..512)")
     args = ap.parse_args(argv)
     dec = BatchDecoder(device=args.device, fixed_q=args.fixed_q, max_num_queries=args.max_queries)
     try:
         timing = {}
-        stats, _, _, _ = dec.decode_files(args.files, timing=timing)
+        stats, _, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags)
         for path, row in zip(args.files, stats):
             print(path)
             print(format_results(row), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
               (len(args.files), timing["raw_samples"] / 1e6, timing["total_s"], timing["h2d_s"], timing["gpu_s"]))
+        if args.inventory:
+            entries, counts = dec.last_inventory
+            k = 0
+            for path, c in zip(args.files, counts):
+                print("%s: %d tags" % (path, int(c)))
+                print(format_inventory(entries[k:k + int(c)]), end="")
+                k += int(c)
+            merged = merge_inventory(entries)
+            print("all traces: %d tags" % len(merged))
+            print(format_inventory(merged), end="")
     finally:
         dec.close()
     return 0

@@ -292,6 +292,37 @@ class Context:
                                                        s.ctypes.data if s is not None else None, k, C.byref(n)))
         return w, r, s
 
+    def batch_plan_inventory(self, max_tags: int) -> None:
+        """Reserves the inventory workspace of the current plan: up to max_tags distinct EPC frames per trace."""
+        self._chk(self._lib.rfid_batch_plan_inventory(self._h, int(max_tags)))
+
+    def batch_inventory_enqueue(self) -> None:
+        """Asynchronous: the inventory of the last pass, behind its statistics (rfid_batch_inventory)."""
+        self._chk(self._lib.rfid_batch_inventory(self._h))
+
+    def batch_inventory_fetch(self):
+        """-> (entries, per-trace counts) of the last batch_inventory_enqueue (synchronises)."""
+        n = C.c_int64(0)
+        counts = np.zeros(max(self._active, 1), dtype=np.int32)
+        ent = np.zeros(0, dtype=capi.TAG_ENTRY_DTYPE)
+        st = self._lib.rfid_batch_get_inventory(self._h, None, 0, C.byref(n), counts.ctypes.data)
+        if st == capi.ERR_CAPACITY and n.value > 0:      # (the size is known now; a trace that overflowed fails again below)
+            ent = np.zeros(n.value, dtype=capi.TAG_ENTRY_DTYPE)
+            st = self._lib.rfid_batch_get_inventory(self._h, ent.ctypes.data, len(ent), C.byref(n), counts.ctypes.data)
+        self._chk(st)
+        return ent, counts[: self._active]
+
+    def batch_inventory(self):
+        """The distinct EPC frames of every trace of the last pass, built on the device: -> (structured array of
+        capi.TAG_ENTRY_DTYPE ordered by (stream, first_seq), entries per trace)."""
+        self.batch_inventory_enqueue()
+        return self.batch_inventory_fetch()
+
+    def batch_inventory_ms(self) -> float:
+        ms = C.c_float(0.0)
+        self._chk(self._lib.rfid_batch_inventory_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

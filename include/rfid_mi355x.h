@@ -121,6 +121,21 @@ typedef struct rfid_stream_stats {
   int32_t tag_reads[256];
 } rfid_stream_stats;
 
+/* one DISTINCT EPC frame of one trace: what the inventory stage (rfid_batch_inventory) lists.  The reads it covers are
+ * those tag_reads[] counts -- EPC windows with a verified CRC before the TERMINATED cut-off (window index <
+ * n_windows_used) -- keyed by all 128 frame bits instead of the one byte tag_reads[] is keyed by. */
+typedef struct rfid_tag_entry {      /* 48 bytes */
+  int32_t  stream;                   /* trace index */
+  int32_t  reads;                    /* CRC-verified reads of this frame before the cut-off */
+  uint32_t frame[4];                 /* the 128 frame bits, packed as rfid_decode_result::bits
+                                        (PC 0..15, EPC 16..111, CRC-16 112..127) */
+  int32_t  first_seq, last_seq;      /* window seq of the first / last such read */
+  int32_t  best_seq;                 /* the read with the largest h_re*h_re + h_im*h_im (binary32, this expression,
+                                        no fused multiply-add; earliest seq on ties) */
+  float    best_h_re, best_h_im;     /* its h_est, copied bit for bit */
+  int32_t  tag_id;                   /* frame bits 104..111, as rfid_decode_result::tag_id */
+} rfid_tag_entry;
+
 /* timing of the last rfid_batch_* pass, from HIP events on the ctx stream */
 typedef struct rfid_batch_timing {
   float mf_ms, gate_ms, decode_ms, stats_ms; /* kernel time per pass (summed over the launches of a pass) */
@@ -399,7 +414,7 @@ RFID_API int rfid_batch_set_long_stream(rfid_ctx *ctx, int mode);
 RFID_API int rfid_batch_ls_report(const rfid_ctx *ctx, rfid_ls_report *out);
 /* The switches the environment can set (INTEGRATION.md section 13 lists them: RFID_LONG_STREAM, RFID_OVERLAP,
  * RFID_LS_CALIBRATE, RFID_LS_DEBUG, RFID_LA_PROFILE, RFID_LA_UPLOAD_KERNEL, RFID_LS_FRONT_LDS_KB and the test hooks
- * RFID_FRONT_UNFUSED / RFID_FRONT_CHUNKS / RFID_LS2_FSM_LANES_MIN / RFID_LS2_DC_ROUNDS).  The environment is read ONCE,
+ * RFID_FRONT_UNFUSED / RFID_FRONT_CHUNKS / RFID_LS2_FSM_LANES_MIN / RFID_LS2_DC_ROUNDS / RFID_INVENTORY_SLOTS).  The environment is read ONCE,
  * by rfid_ctx_create; these two change / read a value of a living context by its lower-case name without the RFID_
  * prefix ("overlap", "front_chunks", ...; LS2_FSM_LANES_MIN is "fsm_lanes_min", LS2_DC_ROUNDS "dc_rounds").  RFID_ERR_INVALID: unknown name or a
  * value outside the knob's range.  A change that concerns buffers (overlap) takes effect with the next rfid_batch_plan. */
@@ -423,6 +438,25 @@ RFID_API int rfid_batch_get_mf(rfid_ctx *ctx, int stream, rfid_cf32 *out, int64_
  * exactly what the gate block writes to its output (lib/gate_impl.cc:176,187; debug tap = the file_sink_gate of
  * apps/reader.py:70).  *n = window length (250 / 1370). */
 RFID_API int rfid_batch_get_gated(rfid_ctx *ctx, int stream, int seq, rfid_cf32 *out, int64_t cap, int64_t *n);
+/* ---- (2b) batch inventory: the tags that were read, per trace, built on the device -------------------------------- */
+/* The statistics of a pass count reads per ONE byte of the EPC (tag_reads[256], the reference's std::map); these calls
+ * list every distinct 128-bit frame of every trace (rfid_tag_entry) without the results leaving HBM: a pass hands the
+ * host 48 bytes per tag instead of 48 bytes per window.  Results are independent of the order in which the device gets
+ * to the windows (integer atomics only): the same pass gives the same bytes.
+ * rfid_batch_plan_inventory reserves the workspace of the current plan for up to max_tags_per_trace distinct frames per
+ * trace (1..512; RFID_ERR_UNSUPPORTED above); a new rfid_batch_plan drops it. */
+RFID_API int rfid_batch_plan_inventory(rfid_ctx *ctx, int max_tags_per_trace);
+/* enqueues the inventory of the LAST pass behind its statistics (asynchronous, no host synchronisation): the traces of
+ * rfid_batch_set_streams, the result set and statistics of that pass also when two result sets alternate.
+ * RFID_ERR_STATE: no plan / no inventory workspace / no pass with statistics yet */
+RFID_API int rfid_batch_inventory(rfid_ctx *ctx);
+/* synchronises; entries ordered by (stream, first_seq); *n = total; counts (nullable): entries per trace, n_streams ints.
+ * RFID_ERR_CAPACITY: cap too small (nothing lost: *n says how many there are, call again; entries may be NULL with
+ * cap = 0), or a trace overflowed max_tags_per_trace (rfid_last_error names the first such trace; such traces list
+ * nothing, plan a larger inventory and run it again) */
+RFID_API int rfid_batch_get_inventory(rfid_ctx *ctx, rfid_tag_entry *entries, int64_t cap, int64_t *n, int32_t *counts);
+/* synchronises; device time of the last rfid_batch_inventory (HIP events), from its first launch to the end of its last */
+RFID_API int rfid_batch_inventory_ms(rfid_ctx *ctx, float *ms);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 

@@ -1,0 +1,198 @@
+"""The inventory stage on the device (rfid_batch_plan_inventory / rfid_batch_inventory / rfid_batch_get_inventory): the distinct
+128-bit EPC frames of every trace of a pass.  Every expected inventory is worked out in numpy from the ORACLE's per-window dumps
+(tests/inventory_ref.py); every comparison is exact -- integers, frame words, best_h_* by bit pattern."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import inventory_ref as ref
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+BIG = (1 << 31) - 2
+
+# six tags, two pairs share the byte tag_reads[] is keyed by
+TAGS6 = (0x27, 0x27, 0x31, 0x31, 0x4C, 0x5A)
+
+
+def _upload(traces):
+    import torch
+    L = max(map(len, traces))
+    stride = (L + 1) & ~1
+    host = np.zeros((len(traces), stride), dtype=np.complex64)
+    lens = np.array([len(t) for t in traces], dtype=np.int64)
+    for i, t in enumerate(traces):
+        host[i, : len(t)] = t
+    dev = torch.from_numpy(host.view(np.float32)).to("cuda:0")
+    dlens = torch.from_numpy(lens).to("cuda:0")
+    torch.cuda.synchronize()
+    return host, lens, L, stride, dev, dlens
+
+
+@pytest.mark.parametrize("mode", [0, 2], ids=["fused-front-end", "long-stream"])
+def test_ragged_batch_of_eight_traces(oracle_mod, synth_mod, mode):
+    """40 rounds, FIXED_Q = 3, six tags of which two pairs end in the same byte, sigma = 0.03; eight traces of different lengths.
+    The pass three times: byte-identical entry arrays.  Then the same pass through a 16-slot table (six frames: probes collide)."""
+    import rfid
+    ts = [synth_mod.make_trace(n_rounds=40 - 3 * k, fixed_q=3, tag_ids=TAGS6, seed=900 + k, sigma=0.03, t1_jitter_raw=3).samples for k in range(8)]
+    host, lens, L, stride, dev, dlens = _upload(ts)
+    refs = [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=3, max_num_queries=BIG)) for b in range(8)]
+    want, want_counts = ref.expected_batch([o.dumps for o in refs])
+    # the input does what the case is about, by the oracle alone
+    for b in range(8):
+        e = want[want["stream"] == b]
+        ids = np.bincount(e["tag_id"], minlength=256)
+        assert len(e) >= 6 and ids[0x27] >= 2 and ids[0x31] >= 2 and (e["reads"] >= 2).sum() >= 4, (b, e)
+    ctx = rfid.Context(device=0, fixed_q=3, max_num_queries=BIG)
+    try:
+        ctx.batch_set_long_stream(mode)
+        ctx.batch_plan(8, L)
+        ctx.batch_plan_inventory(16)
+        blobs = []
+        for rep in range(3):
+            ctx.batch_process_ptr(dev.data_ptr(), stride, L, dlens.data_ptr())
+            ent, counts = ctx.batch_inventory()
+            st = ctx.batch_stats()
+            ref.assert_equal(ent, counts, want, want_counts, (mode, rep))
+            ref.cross_check(ent, counts, st)
+            blobs.append(ent.tobytes())
+        assert blobs[0] == blobs[1] == blobs[2]
+        print("inventory of 8 traces: %.4f ms, %d entries" % (ctx.batch_inventory_ms(), len(ent)))
+        ctx.set_knob("inventory_slots", 16)
+        ctx.batch_plan_inventory(16)
+        ent, counts = ctx.batch_inventory()
+        ref.assert_equal(ent, counts, want, want_counts, "16 slots")
+        ctx.set_knob("inventory_slots", 4)
+        ctx.batch_plan_inventory(4)
+        with pytest.raises(rfid.capi.RfidError) as e:
+            ctx.batch_inventory()
+        assert e.value.status == rfid.capi.ERR_CAPACITY and "trace 0" in str(e.value)
+    finally:
+        ctx.close()
+
+
+@pytest.mark.parametrize("overlap", [1, 2], ids=["one-result-set", "two-result-sets"])
+def test_1024_replicas_list_the_base_traces_frame(oracle_mod, synth_mod, overlap):
+    """The 1 024-trace shape (noise replicas of the 71-round trace, one EPC corrupted): every trace lists ONE frame with 70 reads, the
+    base trace's; first / last / strongest read against the oracle on a replica from each end of the buffer.  With two result sets
+    alternating (RFID_OVERLAP=2) the inventory of every pass is that pass's."""
+    import rfid
+    import torch
+    B = 1024
+    t = synth_mod.make_trace(n_rounds=71, fixed_q=0, tag_ids=(0x27,), sigma=0.0, seed=7, corrupt_rounds=(36,), noise=False, render=False)
+    truth = np.array(t.plan.slots["epc"][0], dtype=np.uint32)
+    ctx = rfid.Context(device=0)
+    data = None
+    try:
+        ctx.set_knob("overlap", overlap)
+        L = ctx.synth_gen2_size(t.plan)
+        stride = (L + 1) & ~1
+        base = torch.zeros(2 * stride, dtype=torch.float32, device="cuda:0")
+        data = torch.empty((B, 2 * stride), dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        ctx.synth_gen2_ptr(t.plan, base.data_ptr(), stride)
+        ctx.synth_replicas_ptr(base.data_ptr(), L, data.data_ptr(), stride, B, 0.002, 777, first_replica=0)
+        ctx.batch_sync()
+        ctx.batch_plan(B, L)
+        ctx.batch_plan_inventory(4)
+        blobs = []
+        for rep in range(3):
+            ctx.batch_process_ptr(data.data_ptr(), stride, L, 0)
+            ent, counts = ctx.batch_inventory()
+            blobs.append(ent.tobytes())
+        assert blobs[0] == blobs[1] == blobs[2]
+        st = ctx.batch_stats()
+        assert (counts == 1).all() and len(ent) == B and np.array_equal(ent["stream"], np.arange(B))
+        assert (ent["reads"] == 70).all() and (ent["tag_id"] == 0x27).all() and (ent["frame"] == truth).all()
+        ref.cross_check(ent, counts, st)
+        for b in (0, B - 1):
+            x = data[b, : 2 * L].cpu().numpy().view(np.complex64)
+            o = oracle_mod.run_trace(x)
+            want = ref.expected(o.dumps, b)
+            ref.assert_equal(ent[b:b + 1], counts[b:b + 1], want, np.array([1], dtype=np.int32), b)
+        print("inventory of 1024 traces: %.4f ms; statistics of the pass %.4f ms" % (ctx.batch_inventory_ms(), ctx.batch_timing()["stats_ms"]))
+    finally:
+        ctx.close()
+        del data
+        torch.cuda.empty_cache()
+
+
+def test_one_long_trace(oracle_mod, synth_mod):
+    """One trace, FIXED_Q = 4, 2 000 rounds, 8 tags, generated on the device from its slot table: 64 000 windows through the
+    16-wave path, against the oracle over the same samples."""
+    import rfid
+    import torch
+    t = synth_mod.make_trace(n_rounds=2000, fixed_q=4, tag_ids=tuple(0x11 + 0x10 * k for k in range(8)), sigma=0.0, seed=2024,
+                             noise=False, render=False)
+    ctx = rfid.Context(device=0, fixed_q=4, max_num_queries=BIG)
+    try:
+        L = ctx.synth_gen2_size(t.plan)
+        stride = (L + 1) & ~1
+        data = torch.zeros(2 * stride, dtype=torch.float32, device="cuda:0")
+        torch.cuda.synchronize()
+        ctx.synth_gen2_ptr(t.plan, data.data_ptr(), stride, sigma=0.002, seed=99)
+        ctx.batch_sync()
+        ctx.batch_plan(1, L)
+        ctx.batch_plan_inventory(64)
+        blobs = []
+        for rep in range(3):
+            ctx.batch_process_ptr(data.data_ptr(), stride, L, 0)
+            ent, counts = ctx.batch_inventory()
+            blobs.append(ent.tobytes())
+        assert blobs[0] == blobs[1] == blobs[2]
+        st = ctx.batch_stats()
+        assert st[0]["n_windows"] == 2 * len(t.slots) > 2048
+        cfg = oracle_mod.config(fixed_q=4, max_num_queries=BIG)
+        s = oracle_mod.Stream(cfg)
+        piece = 48_000_000
+        for pos in range(0, L, piece):
+            n = min(piece, L - pos)
+            s.feed_raw(data[2 * pos: 2 * (pos + n)].cpu().numpy().view(np.complex64))
+        o = s.result()
+        s.close()
+        want, want_counts = ref.expected_batch([o.dumps])
+        assert len(want) >= 8 and int(want["reads"].sum()) > 10000
+        ref.assert_equal(ent, counts, want, want_counts)
+        ref.cross_check(ent, counts, st)
+        print("inventory of one trace of %d windows: %.4f ms; statistics of the pass %.4f ms" %
+              (st[0]["n_windows"], ctx.batch_inventory_ms(), ctx.batch_timing()["stats_ms"]))
+    finally:
+        ctx.close()
+
+
+def test_command_line_lists_the_epcs(oracle_mod, synth_mod, tmp_path):
+    """python -m rfid.batch --inventory on two trace files, in a fresh child process: the print_results block is byte-identical to
+    the one without the flag, the new block lists the EPCs the oracle read."""
+    from rfid import batch as rb
+    paths, wants = [], []
+    for k in range(2):
+        x = synth_mod.make_trace(n_rounds=6 + k, fixed_q=2, tag_ids=(0x27, 0x27, 0x31), seed=104 + 8 * k, sigma=0.02).samples
+        p = str(tmp_path / ("trace%d.bin" % k))
+        rb.write_trace_file(p, x)
+        paths.append(p)
+        wants.append(ref.expected(oracle_mod.run_trace(x, oracle_mod.config(fixed_q=2)).dumps, k))
+    env = dict(os.environ, PYTHONPATH=os.path.join(ROOT, "gen2-uhf-rfid-reader_amd"))
+    outs = []
+    for extra in ([], ["--inventory", "--max-tags", "8"]):
+        r = subprocess.run([sys.executable, "-m", "rfid.batch", "--fixed-q", "2"] + extra + paths, env=env, capture_output=True,
+                           text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        outs.append(r.stdout)
+    plain, inv = outs
+    n_old = plain.rindex("2 traces, ")                      # (the closing line carries wall times)
+    assert inv[:n_old] == plain[:n_old] and inv[n_old:].startswith("2 traces, ")
+    block = inv[n_old:].split("\n", 1)[1]
+    expect = ""
+    for p, w in zip(paths, wants):
+        assert len(w) == 3
+        expect += "%s: %d tags\n" % (p, len(w)) + rb.format_inventory(w)
+    merged = rb.merge_inventory(np.concatenate(wants))
+    expect += "all traces: %d tags\n" % len(merged) + rb.format_inventory(merged)
+    assert block == expect
+    for w in wants:
+        for e in w:
+            assert rb.frame_fields(e["frame"])[1] in block
