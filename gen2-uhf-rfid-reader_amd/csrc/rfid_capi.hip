@@ -21,6 +21,7 @@
 #include "rfid_host_math.h"
 #include "rfid_kernels.hpp"
 #include "rfid_inventory.hpp"
+#include "rfid_tracks.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
 // the launch list of the long-stream front end, on the stream named by the enclosing scope's `ls2_stream`
@@ -295,6 +296,18 @@ struct rfid_ctx {
     bool enqueued = false;            // an rfid_batch_inventory is behind the events
     int n_streams = 0;                // traces it covered
   } inv;
+  bool inv_current = false;           // an rfid_batch_inventory was enqueued behind the statistics of the LAST pass (Inventory::enqueued
+                                      // survives a new pass: rfid_batch_get_inventory may still fetch the earlier one)
+  // ---- tracks stage (rfid_batch_plan_tracks): lives and dies with the inventory workspace ----
+  struct Tracks {
+    void *blk = nullptr;              // one allocation, carved up
+    rfid_tag_read *d_reads = nullptr; // [cap]
+    int64_t cap = 0;                  // B_plan x ceil(wmax / 2)
+    int64_t *d_off = nullptr;         // [B_plan x max_tags + 1]
+    int *d_base = nullptr, *d_head = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool enqueued = false;            // an rfid_batch_tracks is behind the events
+  } trk;
   bool stats_current = false;         // d_stats holds the statistics of the results in d_res (rfid_batch_stats ran behind the last decode)
   int n_chunks_last = 0;   // > 0 when the last pass used the overlapped path
   int fused_last = 0;      // 1 when the last rfid_batch_process pass used front_end_fused_kernel
@@ -414,7 +427,14 @@ void init_reader_state(rfid_ctx *c) {  // global_vars.cc:34-54
   c->rs.cur_slot_number = 1;
 }
 
+void free_tracks(rfid_ctx *c) {
+  if (c->trk.blk) (void)hipFree(c->trk.blk);
+  c->trk.blk = nullptr; c->trk.cap = 0; c->trk.enqueued = false;
+}
+
 void free_plan(rfid_ctx *c) {
+  free_tracks(c);
+  c->inv_current = false;
   if (c->inv.blk) (void)hipFree(c->inv.blk);
   c->inv.blk = nullptr; c->inv.max_tags = 0; c->inv.enqueued = false;
   c->stats_current = false;
@@ -925,6 +945,8 @@ int rfid_ctx_destroy(rfid_ctx *c) {
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
   for (int i = 0; i < 2; ++i)
     if (c->inv.ev[i]) (void)hipEventDestroy(c->inv.ev[i]);
+  for (int i = 0; i < 2; ++i)
+    if (c->trk.ev[i]) (void)hipEventDestroy(c->trk.ev[i]);
   if (c->stream2) {
     (void)hipStreamSynchronize(c->stream2);
     for (int i = 0; i <= rfid_ctx::MAX_CHUNKS; ++i)
@@ -1284,6 +1306,7 @@ static int rfid_batch_gate_impl(rfid_ctx *c, const int *skip_if) {
   a.flat = c->d_flat; a.flat_count = c->d_flat_count; a.flat_cap = c->flat_cap; a.mode = 0;
   a.gated = nullptr; a.gated_cap = 0; a.io = nullptr;
   c->stats_current = false;
+  c->inv_current = false;
   if (!c->ev_valid[1]) { HIPCHK(c, hipEventRecord(c->ev[1], c->stream)); c->ev_valid[1] = true; }
   hipLaunchKernelGGL(gate_scan_kernel, dim3((unsigned)((c->B + GATE_STREAMS_PER_WG - 1) / GATE_STREAMS_PER_WG)), dim3(GATE_THREADS), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
@@ -1324,6 +1347,7 @@ int rfid_batch_decode(rfid_ctx *c, int want_scores) {
   d.ticket_next = c->d_ticket + ((c->ticket_flip & 1) ^ 1);
   c->ticket_flip ^= 1;
   c->stats_current = false;
+  c->inv_current = false;
   hipLaunchKernelGGL(decode_all_kernel, dim3((unsigned)grid), dim3(64), 0, ts, d);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[3], ts));
@@ -1350,6 +1374,7 @@ int rfid_batch_stats(rfid_ctx *c) {
   HIPCHK(c, hipEventRecord(c->ev[4], ts));
   c->ev_valid[4] = true;
   c->stats_current = true;
+  c->inv_current = false;
   return RFID_OK;
 }
 
@@ -1366,6 +1391,8 @@ int rfid_batch_plan_inventory(rfid_ctx *c, int max_tags) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   rfid_ctx::Inventory &v = c->inv;
+  free_tracks(c);                      // (sized by this workspace, and reading it)
+  c->inv_current = false;
   if (v.blk) HIPCHK(c, hipFree(v.blk));
   v.blk = nullptr; v.max_tags = 0; v.enqueued = false;
   for (int i = 0; i < 2; ++i)
@@ -1414,6 +1441,7 @@ int rfid_batch_inventory(rfid_ctx *c) {
   HIPCHK(c, hipEventRecord(v.ev[1], c->stream));
   v.enqueued = true;
   v.n_streams = c->B;
+  c->inv_current = true;
   return RFID_OK;
 }
 
@@ -1445,6 +1473,100 @@ int rfid_batch_inventory_ms(rfid_ctx *c, float *ms) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventSynchronize(c->inv.ev[1]));
   HIPCHK(c, hipEventElapsedTime(ms, c->inv.ev[0], c->inv.ev[1]));
+  return RFID_OK;
+}
+
+// ---- tracks stage: every tag's reads in time order, behind the inventory of a pass (csrc/rfid_tracks.hpp) ----
+int rfid_batch_plan_tracks(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  if (!c->B_plan || !c->inv.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_tracks: no plan with an inventory workspace (rfid_batch_plan_inventory)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  rfid_ctx::Tracks &t = c->trk;
+  free_tracks(c);
+  for (int i = 0; i < 2; ++i)
+    if (!t.ev[i]) HIPCHK(c, hipEventCreate(&t.ev[i]));
+  // EPC windows are every other window: at most ceil(wmax / 2) reads per trace
+  const int64_t cap = (int64_t)((c->wmax + 1) / 2) * c->B_plan;      // (< 2^31: wmax x B_plan is, rfid_batch_plan)
+  auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t sz_r = up256(sizeof(rfid_tag_read) * (size_t)cap), sz_o = up256(sizeof(int64_t) * ((size_t)c->inv.max_tags * (size_t)c->B_plan + 1)),
+               sz_i = up256(sizeof(int) * (size_t)c->B_plan);
+  hipError_t e = hipMalloc(&t.blk, sz_r + sz_o + sz_i + 256);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    t.blk = nullptr;
+    return fail(c, RFID_ERR_HIP, "rfid_batch_plan_tracks: workspace allocation", e);
+  }
+  char *b = (char *)t.blk;
+  t.d_reads = (rfid_tag_read *)b; b += sz_r; t.d_off = (int64_t *)b; b += sz_o; t.d_base = (int *)b; b += sz_i; t.d_head = (int *)b;
+  t.cap = cap;
+  return RFID_OK;
+}
+
+int rfid_batch_tracks(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Inventory &v = c->inv;
+  rfid_ctx::Tracks &t = c->trk;
+  if (!c->B || !v.blk || !t.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_tracks: no plan with a tracks workspace (rfid_batch_plan_tracks)");
+  if (!v.enqueued || !c->inv_current || !c->stats_current) return fail(c, RFID_ERR_STATE, "rfid_batch_tracks: no rfid_batch_inventory behind the last pass");
+  HIPCHK(c, hipSetDevice(c->device));
+  // as rfid_batch_inventory: c->d_* name the last pass's result set; its tails ran on the second stream when two sets alternate
+  { int rj = join_tails(c); if (rj) return rj; }
+  const int n = v.n_streams;          // the traces the inventory covered
+  TrkScanArgs p;
+  p.ent = v.d_ent; p.counts = v.d_counts; p.inv_head = v.d_head; p.n_streams = n; p.max_tags = v.max_tags;
+  p.base = t.d_base; p.head = t.d_head; p.offsets = t.d_off;
+  TrkArgs a;
+  a.res = c->d_res; a.wtab = c->d_wtab; a.wcount = c->d_wcount; a.stats = c->d_stats; a.wmax = c->wmax; a.n_streams = n;
+  a.ent = v.d_ent; a.counts = v.d_counts; a.ent_off = v.d_off; a.max_tags = v.max_tags; a.slots = v.slots;
+  a.base = t.d_base; a.out = t.d_reads; a.cap = t.cap; a.offsets = t.d_off;
+  HIPCHK(c, hipEventRecord(t.ev[0], c->stream));
+  const int scan_threads = (n >= INV_SCAN_THREADS) ? INV_SCAN_THREADS : ((n + 63) & ~63);
+  hipLaunchKernelGGL(tracks_offsets_kernel, dim3(1), dim3((unsigned)scan_threads), 0, c->stream, p);
+  HIPCHK(c, hipGetLastError());
+  // one wave per trace; sixteen when a trace can hold thousands of windows (as the inventory kernel).  The small
+  // instantiation: a table of up to 128 slots and up to 64 entries per trace
+  const bool small = v.slots <= 128 && v.max_tags <= 64;
+  const bool wide = c->wmax > 2048;
+  const dim3 grid((unsigned)n);
+  if (small && !wide) hipLaunchKernelGGL((tracks_kernel<128, 64, 1>), grid, dim3(64), 0, c->stream, a);
+  else if (!wide) hipLaunchKernelGGL((tracks_kernel<1024, 512, 1>), grid, dim3(64), 0, c->stream, a);
+  else if (small) hipLaunchKernelGGL((tracks_kernel<128, 64, INV_MAX_WAVES>), grid, dim3(64 * INV_MAX_WAVES), 0, c->stream, a);
+  else hipLaunchKernelGGL((tracks_kernel<1024, 512, INV_MAX_WAVES>), grid, dim3(64 * INV_MAX_WAVES), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(t.ev[1], c->stream));
+  t.enqueued = true;
+  return RFID_OK;
+}
+
+int rfid_batch_get_tracks(rfid_ctx *c, rfid_tag_read *reads, int64_t cap, int64_t *n, int64_t *offsets) {
+  if (!c || !n || cap < 0 || (cap > 0 && !reads)) return RFID_ERR_INVALID;
+  rfid_ctx::Inventory &v = c->inv;
+  rfid_ctx::Tracks &t = c->trk;
+  if (!v.blk || !t.blk || !t.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_tracks: no rfid_batch_tracks behind this plan");
+  HIPCHK(c, hipSetDevice(c->device));
+  int head[2] = {0, 0}, total = 0;
+  HIPCHK(c, hipMemcpyAsync(head, v.d_head, sizeof(head), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&total, t.d_head, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n = total;
+  if (head[1] != INV_EMPTY) {
+    snprintf(c->err, sizeof(c->err), "rfid_batch_get_tracks: trace %d holds more than max_tags_per_trace = %d distinct frames", head[1], v.max_tags);
+    return RFID_ERR_CAPACITY;
+  }
+  if (total > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_tracks: cap is smaller than the number of reads");
+  if (total > 0) HIPCHK(c, hipMemcpyAsync(reads, t.d_reads, sizeof(rfid_tag_read) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+  if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, t.d_off, sizeof(int64_t) * ((size_t)head[0] + 1), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
+}
+
+int rfid_batch_tracks_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  if (!c->trk.blk || !c->trk.enqueued) return RFID_ERR_STATE;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(c->trk.ev[1]));
+  HIPCHK(c, hipEventElapsedTime(ms, c->trk.ev[0], c->trk.ev[1]));
   return RFID_OK;
 }
 

@@ -76,7 +76,10 @@ STREAM_WINDOW_DTYPE = np.dtype([("start", "<i8"), ("type", "<i4"), ("reserved_",
 TAG_ENTRY_DTYPE = np.dtype([("stream", "<i4"), ("reads", "<i4"), ("frame", "<u4", (4,)), ("first_seq", "<i4"),
                             ("last_seq", "<i4"), ("best_seq", "<i4"), ("best_h_re", "<f4"), ("best_h_im", "<f4"),
                             ("tag_id", "<i4")])
+TAG_READ_DTYPE = np.dtype([("stream", "<i4"), ("entry", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("h_re", "<f4"),
+                           ("h_im", "<f4"), ("T", "<f4"), ("index", "<i4")])
 assert STREAM_WINDOW_DTYPE.itemsize == 24 and TAG_ENTRY_DTYPE.itemsize == 48
+assert TAG_READ_DTYPE.itemsize == 32
 assert WINDOW_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 48
 assert SCORES_DTYPE.itemsize == 144 and STATS_DTYPE.itemsize == 1056
 
@@ -137,6 +140,10 @@ SIGNATURES = {
     "rfid_batch_inventory": (_i, [_vp]),
     "rfid_batch_get_inventory": (_i, [_vp, _vp, _i64, C.POINTER(_i64), _vp]),
     "rfid_batch_inventory_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_batch_plan_tracks": (_i, [_vp]),
+    "rfid_batch_tracks": (_i, [_vp]),
+    "rfid_batch_get_tracks": (_i, [_vp, _vp, _i64, C.POINTER(_i64), _vp]),
+    "rfid_batch_tracks_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

@@ -40,7 +40,9 @@ class BatchDecoder:
         self._pinned = None
         self._lens_dev = None
         self._inv_tags = 0
+        self._trk_planned = False
         self.last_inventory = None    # (entries, per-trace counts) of the last decode(..., inventory=True)
+        self.last_tracks = None       # (reads, offsets) of the last decode(..., tracks=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -51,7 +53,8 @@ class BatchDecoder:
         if self._planned[0] < n_traces or self._planned[1] < max_len:
             self.ctx.batch_plan(max(n_traces, self._planned[0]), max(max_len, self._planned[1]))
             self._planned = (max(n_traces, self._planned[0]), max(max_len, self._planned[1]))
-            self._inv_tags = 0        # (a new plan drops the inventory workspace)
+            self._inv_tags = 0        # (a new plan drops the inventory workspace, and the tracks workspace with it)
+            self._trk_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -61,12 +64,14 @@ class BatchDecoder:
         return stride
 
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
-               inventory: bool = False, max_tags: int = 64):
+               inventory: bool = False, max_tags: int = 64, tracks: bool = False):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
         of every trace (up to max_tags per trace) are listed on the device behind the pass and kept as
-        `self.last_inventory` = (entries, per-trace counts); the return value is the same."""
+        `self.last_inventory` = (entries, per-trace counts); the return value is the same.  tracks=True (implies
+        inventory=True): every tag's reads in time order are listed behind the inventory and kept as `self.last_tracks` =
+        (reads, offsets), offsets aligned with the entries."""
         torch = self._torch
         n = len(traces)
         lens = np.array([len(t) for t in traces], dtype=np.int64)
@@ -84,16 +89,25 @@ class BatchDecoder:
             self._lens_dev = torch.from_numpy(lens).to(dev.device, non_blocking=True)
             torch.cuda.current_stream().synchronize()
         t1 = time.perf_counter()
+        inventory = inventory or tracks
         if inventory and self._inv_tags != int(max_tags):
             self.ctx.batch_plan_inventory(int(max_tags))
             self._inv_tags = int(max_tags)
+            self._trk_planned = False
+        if tracks and not self._trk_planned:
+            self.ctx.batch_plan_tracks()
+            self._trk_planned = True
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
         if inventory:
             self.ctx.batch_inventory_enqueue()
+        if tracks:
+            self.ctx.batch_tracks_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
             self.last_inventory = self.ctx.batch_inventory_fetch()
+        if tracks:
+            self.last_tracks = self.ctx.batch_tracks_fetch()
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -169,8 +183,31 @@ def format_inventory(entries: np.ndarray) -> str:
     return "\n".join(lines) + "\n"
 
 
+TRACKS_HEADER = "file,epc,pc,seq,t_s,h_re,h_im,mag_db,phase_rad,T"
+TRACKS_RATE = 400e3       # samples per second behind the decimation of a 2 Msps trace: what rfid_window::start counts
+
+
+def format_tracks(entries: np.ndarray, reads: np.ndarray, offsets: np.ndarray, names: Sequence[str]) -> str:
+    """CSV text, one line per read in the order of `reads` (grouped by tag, time order inside a tag):
+    file,epc,pc,seq,t_s,h_re,h_im,mag_db,phase_rad,T with t_s = start / 400e3.  entries / offsets: the packed inventory
+    and the offsets aligned with it (Context.batch_inventory_fetch / batch_tracks_fetch); names[stream]: the trace's file.
+    Floats are printed with %.9g: binary32 values survive the round trip."""
+    lines = [TRACKS_HEADER]
+    for i, e in enumerate(entries):
+        pc, epc = frame_fields(e["frame"])
+        name = names[int(e["stream"])]
+        for r in reads[int(offsets[i]):int(offsets[i + 1])]:
+            re, im = np.float64(r["h_re"]), np.float64(r["h_im"])
+            mag = float(np.hypot(re, im))
+            db = 20.0 * np.log10(mag) if mag > 0 else float("-inf")
+            lines.append("%s,%s,%04x,%d,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g" %
+                         (name, epc, pc, int(r["seq"]), int(r["start"]) / TRACKS_RATE, float(r["h_re"]), float(r["h_im"]), db,
+                          float(np.arctan2(im, re)), float(r["T"])))
+    return "\n".join(lines) + "\n"
+
+
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -179,11 +216,16 @@ def main(argv=None) -> int:
     ap.add_argument("--max-queries", type=int, default=1000)
     ap.add_argument("--inventory", action="store_true", help="list the distinct EPCs of every trace (built on the device)")
     ap.add_argument("--max-tags", type=int, default=64, help="distinct EPCs per trace the inventory has room for (1..512)")
+    ap.add_argument("--tracks", metavar="OUT.csv", default=None,
+                    help="write every tag's reads in time order (t_s, h_est, T) to this CSV file; implies --inventory")
     args = ap.parse_args(argv)
+    if args.tracks:
+        args.inventory = True
     dec = BatchDecoder(device=args.device, fixed_q=args.fixed_q, max_num_queries=args.max_queries)
     try:
         timing = {}
-        stats, _, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags)
+        stats, _, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
+                                            tracks=bool(args.tracks))
         for path, row in zip(args.files, stats):
             print(path)
             print(format_results(row), end="")
@@ -199,6 +241,10 @@ def main(argv=None) -> int:
             merged = merge_inventory(entries)
             print("all traces: %d tags" % len(merged))
             print(format_inventory(merged), end="")
+        if args.tracks:
+            reads, offsets = dec.last_tracks
+            with open(args.tracks, "w") as f:
+                f.write(format_tracks(dec.last_inventory[0], reads, offsets, args.files))
     finally:
         dec.close()
     return 0

@@ -323,6 +323,46 @@ class Context:
         self._chk(self._lib.rfid_batch_inventory_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
+    def batch_plan_tracks(self) -> None:
+        """Reserves the tracks workspace of the current plan (behind batch_plan_inventory; a new plan or a new
+        batch_plan_inventory drops it)."""
+        self._chk(self._lib.rfid_batch_plan_tracks(self._h))
+
+    def batch_tracks_enqueue(self) -> None:
+        """Asynchronous: the tracks of the last pass, behind its inventory (rfid_batch_tracks)."""
+        self._chk(self._lib.rfid_batch_tracks(self._h))
+
+    def batch_tracks_fetch(self):
+        """-> (reads, offsets) of the last batch_tracks_enqueue (synchronises): capi.TAG_READ_DTYPE ordered by
+        (stream, entry, seq); int64 offsets aligned with the entries of batch_inventory_fetch -- reads
+        offsets[i]:offsets[i + 1] are entry i's."""
+        n = C.c_int64(0)
+        reads = np.zeros(0, dtype=capi.TAG_READ_DTYPE)
+        st = self._lib.rfid_batch_get_tracks(self._h, None, 0, C.byref(n), None)
+        if st == capi.ERR_CAPACITY and n.value > 0:      # (the size is known now; a trace that overflowed fails again below)
+            reads = np.zeros(n.value, dtype=capi.TAG_READ_DTYPE)
+        if st in (capi.OK, capi.ERR_CAPACITY):
+            ne = C.c_int64(0)
+            si = self._lib.rfid_batch_get_inventory(self._h, None, 0, C.byref(ne), None)
+            if si not in (capi.OK, capi.ERR_CAPACITY):
+                self._chk(si)
+            offsets = np.zeros(ne.value + 1, dtype=np.int64)
+            st = self._lib.rfid_batch_get_tracks(self._h, reads.ctypes.data if len(reads) else None, len(reads), C.byref(n),
+                                                 offsets.ctypes.data)
+        self._chk(st)
+        return reads, offsets
+
+    def batch_tracks(self):
+        """Every tag's reads of the last pass in time order, built on the device behind batch_inventory():
+        -> (reads, offsets), see batch_tracks_fetch."""
+        self.batch_tracks_enqueue()
+        return self.batch_tracks_fetch()
+
+    def batch_tracks_ms(self) -> float:
+        ms = C.c_float(0.0)
+        self._chk(self._lib.rfid_batch_tracks_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

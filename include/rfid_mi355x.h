@@ -136,6 +136,18 @@ typedef struct rfid_tag_entry {      /* 48 bytes */
   int32_t  tag_id;                   /* frame bits 104..111, as rfid_decode_result::tag_id */
 } rfid_tag_entry;
 
+/* one CRC-verified EPC read before the TERMINATED cut-off: what the tracks stage (rfid_batch_tracks) lists for every
+ * read the inventory counts -- when it happened and the channel estimate the decoder formed for it */
+typedef struct rfid_tag_read {       /* 32 bytes */
+  int32_t stream;                    /* trace index */
+  int32_t entry;                     /* which tag: index into THIS trace's inventory list (order of first_seq), 0-based */
+  int32_t seq;                       /* the EPC window's seq (rfid_window::seq) */
+  int32_t start;                     /* rfid_window::start of that window: 400 ksps index of its first gated sample */
+  float   h_re, h_im;                /* rfid_decode_result::h_re / h_im of that window, copied bit for bit */
+  float   T;                         /* rfid_decode_result::T, bit for bit */
+  int32_t index;                     /* rfid_decode_result::index (tag_sync's return value) */
+} rfid_tag_read;
+
 /* timing of the last rfid_batch_* pass, from HIP events on the ctx stream */
 typedef struct rfid_batch_timing {
   float mf_ms, gate_ms, decode_ms, stats_ms; /* kernel time per pass (summed over the launches of a pass) */
@@ -457,6 +469,25 @@ RFID_API int rfid_batch_inventory(rfid_ctx *ctx);
 RFID_API int rfid_batch_get_inventory(rfid_ctx *ctx, rfid_tag_entry *entries, int64_t cap, int64_t *n, int32_t *counts);
 /* synchronises; device time of the last rfid_batch_inventory (HIP events), from its first launch to the end of its last */
 RFID_API int rfid_batch_inventory_ms(rfid_ctx *ctx, float *ms);
+/* ---- (2c) batch tracks: every tag's reads in time order, built on the device -------------------------------------- */
+/* Behind the inventory of a pass: one rfid_tag_read per read the inventory counts (EPC window, crc_ok == 1, window
+ * index < n_windows_used), ONE array ordered by (stream, entry, seq) -- grouped by tag, each tag's reads in time order.
+ * The order is total and every place is computed, not raced for: the bytes of a pass are a function of its input.
+ * A trace whose inventory overflowed lists no reads, as it lists no entries.
+ * rfid_batch_plan_tracks reserves the workspace of the current plan (ceil(wmax / 2) reads per trace: EPC windows are
+ * every other window).  RFID_ERR_STATE without an inventory workspace; RFID_ERR_HIP when the allocation fails (the
+ * plan and the inventory workspace stay usable).  A new rfid_batch_plan and a new rfid_batch_plan_inventory drop it. */
+RFID_API int rfid_batch_plan_tracks(rfid_ctx *ctx);
+/* enqueues the tracks of the LAST pass behind its inventory (asynchronous, no host synchronisation).
+ * RFID_ERR_STATE: no tracks workspace, or no rfid_batch_inventory was enqueued since the last pass */
+RFID_API int rfid_batch_tracks(rfid_ctx *ctx);
+/* synchronises; *n = reads in all; offsets (nullable): n_entries + 1 values aligned with the packed entries of
+ * rfid_batch_get_inventory -- reads offsets[i] .. offsets[i + 1] belong to entry i, offsets[i + 1] - offsets[i] ==
+ * entries[i].reads.  RFID_ERR_CAPACITY: cap too small (nothing lost: *n says how many there are, call again; reads may
+ * be NULL with cap = 0), or a trace overflowed the inventory (rfid_last_error names the first such trace) */
+RFID_API int rfid_batch_get_tracks(rfid_ctx *ctx, rfid_tag_read *reads, int64_t cap, int64_t *n, int64_t *offsets);
+/* synchronises; device time of the last rfid_batch_tracks (HIP events), from its first launch to the end of its last */
+RFID_API int rfid_batch_tracks_ms(rfid_ctx *ctx, float *ms);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
