@@ -22,6 +22,7 @@
 #include "rfid_kernels.hpp"
 #include "rfid_inventory.hpp"
 #include "rfid_tracks.hpp"
+#include "rfid_quality.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
 // the launch list of the long-stream front end, on the stream named by the enclosing scope's `ls2_stream`
@@ -308,6 +309,18 @@ struct rfid_ctx {
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool enqueued = false;            // an rfid_batch_tracks is behind the events
   } trk;
+  bool trk_current = false;           // an rfid_batch_tracks was enqueued behind the inventory of the LAST pass
+  // ---- quality stage (rfid_batch_plan_quality): lives and dies with the tracks workspace ----
+  struct Quality {
+    void *blk = nullptr;              // one allocation, carved up
+    rfid_read_quality *d_table = nullptr;   // [B_plan][rows]
+    rfid_read_quality *d_packed = nullptr;  // [trk.cap]: aligned with the tracks
+    int *d_nrows = nullptr;           // [B_plan]: EPC windows before the cut-off
+    int rows = 0;                     // ceil(wmax / 2)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool enqueued = false;            // an rfid_batch_quality is behind the events
+    int n_streams = 0;                // traces it covered
+  } qual;
   bool stats_current = false;         // d_stats holds the statistics of the results in d_res (rfid_batch_stats ran behind the last decode)
   int n_chunks_last = 0;   // > 0 when the last pass used the overlapped path
   int fused_last = 0;      // 1 when the last rfid_batch_process pass used front_end_fused_kernel
@@ -427,7 +440,14 @@ void init_reader_state(rfid_ctx *c) {  // global_vars.cc:34-54
   c->rs.cur_slot_number = 1;
 }
 
+void free_quality(rfid_ctx *c) {
+  if (c->qual.blk) (void)hipFree(c->qual.blk);
+  c->qual.blk = nullptr; c->qual.rows = 0; c->qual.enqueued = false;
+}
+
 void free_tracks(rfid_ctx *c) {
+  free_quality(c);                     // (sized by this workspace, and reading it)
+  c->trk_current = false;
   if (c->trk.blk) (void)hipFree(c->trk.blk);
   c->trk.blk = nullptr; c->trk.cap = 0; c->trk.enqueued = false;
 }
@@ -947,6 +967,8 @@ int rfid_ctx_destroy(rfid_ctx *c) {
     if (c->inv.ev[i]) (void)hipEventDestroy(c->inv.ev[i]);
   for (int i = 0; i < 2; ++i)
     if (c->trk.ev[i]) (void)hipEventDestroy(c->trk.ev[i]);
+  for (int i = 0; i < 2; ++i)
+    if (c->qual.ev[i]) (void)hipEventDestroy(c->qual.ev[i]);
   if (c->stream2) {
     (void)hipStreamSynchronize(c->stream2);
     for (int i = 0; i <= rfid_ctx::MAX_CHUNKS; ++i)
@@ -1442,6 +1464,7 @@ int rfid_batch_inventory(rfid_ctx *c) {
   v.enqueued = true;
   v.n_streams = c->B;
   c->inv_current = true;
+  c->trk_current = false;              // (the tracks behind an earlier inventory are not this one's)
   return RFID_OK;
 }
 
@@ -1536,6 +1559,7 @@ int rfid_batch_tracks(rfid_ctx *c) {
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(t.ev[1], c->stream));
   t.enqueued = true;
+  c->trk_current = true;
   return RFID_OK;
 }
 
@@ -1567,6 +1591,122 @@ int rfid_batch_tracks_ms(rfid_ctx *c, float *ms) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipEventSynchronize(c->trk.ev[1]));
   HIPCHK(c, hipEventElapsedTime(ms, c->trk.ev[0], c->trk.ev[1]));
+  return RFID_OK;
+}
+
+// ---- quality stage: per-read SNR and decision margin, behind the tracks of a pass (csrc/rfid_quality.hpp) ----
+int rfid_batch_plan_quality(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  if (!c->B_plan || !c->inv.blk || !c->trk.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_quality: no plan with a tracks workspace (rfid_batch_plan_tracks)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  rfid_ctx::Quality &q = c->qual;
+  free_quality(c);
+  for (int i = 0; i < 2; ++i)
+    if (!q.ev[i]) HIPCHK(c, hipEventCreate(&q.ev[i]));
+  // EPC windows are every other window: ceil(wmax / 2) rows per trace, as many packed records as the tracks have reads
+  const int rows = (c->wmax + 1) / 2;
+  auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t sz_t = up256(sizeof(rfid_read_quality) * (size_t)rows * (size_t)c->B_plan), sz_p = up256(sizeof(rfid_read_quality) * (size_t)c->trk.cap),
+               sz_i = up256(sizeof(int) * (size_t)c->B_plan);
+  hipError_t e = hipMalloc(&q.blk, sz_t + sz_p + sz_i);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    q.blk = nullptr;
+    return fail(c, RFID_ERR_HIP, "rfid_batch_plan_quality: workspace allocation", e);
+  }
+  char *b = (char *)q.blk;
+  q.d_table = (rfid_read_quality *)b; b += sz_t; q.d_packed = (rfid_read_quality *)b; b += sz_p; q.d_nrows = (int *)b;
+  q.rows = rows;
+  return RFID_OK;
+}
+
+int rfid_batch_quality(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Tracks &t = c->trk;
+  rfid_ctx::Quality &q = c->qual;
+  if (!c->B || !c->inv.blk || !t.blk || !q.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_quality: no plan with a quality workspace (rfid_batch_plan_quality)");
+  if (!t.enqueued || !c->trk_current || !c->inv_current || !c->stats_current) return fail(c, RFID_ERR_STATE, "rfid_batch_quality: no rfid_batch_tracks behind the last pass");
+  HIPCHK(c, hipSetDevice(c->device));
+  // as rfid_batch_inventory: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
+  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
+  { int rj = join_tails(c); if (rj) return rj; }
+  const int n = c->inv.n_streams;     // the traces the inventory and the tracks covered
+  QualArgs a;
+  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->d_wtab; a.res = c->d_res; a.wcount = c->d_wcount; a.stats = c->d_stats;
+  a.wmax = c->wmax; a.n_streams = n; a.rows = q.rows; a.table = q.d_table; a.nrows = q.d_nrows;
+  QualGatherArgs g;
+  g.reads = t.d_reads; g.head = t.d_head; g.cap = t.cap; g.table = q.d_table; g.n_streams = n; g.rows = q.rows; g.out = q.d_packed;
+  HIPCHK(c, hipEventRecord(q.ev[0], c->stream));
+  // single-wave workgroups, each walking packs of eight rows (12.6 KB of LDS each)
+  const int64_t items = (int64_t)n * ((q.rows + QUAL_PACK - 1) / QUAL_PACK);
+  const int64_t most = (int64_t)c->n_cus * QUAL_WGS_PER_CU;
+  hipLaunchKernelGGL(quality_kernel, dim3((unsigned)(items < most ? (items > 0 ? items : 1) : most)), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  const int64_t words = t.cap * QUAL_WORDS, gmost = (int64_t)c->n_cus * 8;
+  int64_t gblocks = (words + QUAL_GATHER_THREADS - 1) / QUAL_GATHER_THREADS;
+  if (gblocks > gmost) gblocks = gmost;
+  if (gblocks < 1) gblocks = 1;
+  hipLaunchKernelGGL(quality_gather_kernel, dim3((unsigned)gblocks), dim3(QUAL_GATHER_THREADS), 0, c->stream, g);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(q.ev[1], c->stream));
+  // the long-stream front end hands this pass's matched-filter buffer to the pass after next, whose first launch runs on the
+  // second stream as soon as the buffer's event has come: the event is recorded again, behind the launches that read the buffer
+  if (c->y_recorded[c->y_idx]) HIPCHK(c, hipEventRecord(c->ev_y_free[c->y_idx], c->stream));
+  q.enqueued = true;
+  q.n_streams = n;
+  return RFID_OK;
+}
+
+int rfid_batch_get_quality(rfid_ctx *c, rfid_read_quality *out, int64_t cap, int64_t *n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
+  rfid_ctx::Inventory &v = c->inv;
+  rfid_ctx::Tracks &t = c->trk;
+  rfid_ctx::Quality &q = c->qual;
+  if (!v.blk || !t.blk || !q.blk || !q.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_quality: no rfid_batch_quality behind this plan");
+  HIPCHK(c, hipSetDevice(c->device));
+  int head[2] = {0, 0}, total = 0;
+  HIPCHK(c, hipMemcpyAsync(head, v.d_head, sizeof(head), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&total, t.d_head, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n = total;
+  if (head[1] != INV_EMPTY) {
+    snprintf(c->err, sizeof(c->err), "rfid_batch_get_quality: trace %d holds more than max_tags_per_trace = %d distinct frames", head[1], v.max_tags);
+    return RFID_ERR_CAPACITY;
+  }
+  if (total > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_quality: cap is smaller than the number of reads");
+  if (total > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, q.d_packed, sizeof(rfid_read_quality) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return RFID_OK;
+}
+
+int rfid_batch_get_window_quality(rfid_ctx *c, int stream, rfid_read_quality *out, int64_t cap, int64_t *n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
+  rfid_ctx::Quality &q = c->qual;
+  if (!q.blk || !q.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_quality: no rfid_batch_quality behind this plan");
+  if (stream < 0 || stream >= q.n_streams) return RFID_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  int nrows = 0;
+  HIPCHK(c, hipMemcpyAsync(&nrows, q.d_nrows + stream, sizeof(nrows), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n = nrows;
+  if (nrows > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_window_quality: cap is smaller than the number of EPC windows");
+  const int64_t take = (cap < q.rows) ? cap : q.rows;      // (the zeroed rows behind the cut-off too, as far as there is room)
+  if (take > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, q.d_table + (size_t)stream * (size_t)q.rows, sizeof(rfid_read_quality) * (size_t)take, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return RFID_OK;
+}
+
+int rfid_batch_quality_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  if (!c->qual.blk || !c->qual.enqueued) return RFID_ERR_STATE;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(c->qual.ev[1]));
+  HIPCHK(c, hipEventElapsedTime(ms, c->qual.ev[0], c->qual.ev[1]));
   return RFID_OK;
 }
 

@@ -1,0 +1,183 @@
+// rfid_quality.hpp -- the read-quality stage of the batched path: behind the tracks of a pass, one rfid_read_quality per EPC
+// window before the TERMINATED cut-off, CRC-verified or not -- how far the 128 decision values of tag_detection_EPC
+// (tag_decoder_impl.cc:171-190) stand above what lies in quadrature to them.  The tag modulates along h_est, so
+// r_j = Re((s_a - s_b) conj(h_est)) carries the signal and q_j = Im(...) noise and interference only: sum r^2 / sum q^2 tells
+// a weak tag from an empty or collided slot, min |r| says which bit was nearest to flipping.  No counterpart in the reference:
+// it is what a caller would otherwise work out on the host from every gated window of a pass (10 960 bytes each).
+//
+// The definition (include/rfid_mi355x.h, rfid_read_quality) is in binary32, one rounding per operation, the three sums in the
+// order of j: a record is a function of the input alone.  The kernel's shape:
+//   gather  a wave takes QUAL_PACK = 8 EPC windows of one trace at a time (a persistent grid over (trace, pack of rows)).  Only
+//           512 of a window's 1 370 samples are touched, 40 bytes apart: they are gathered straight from global memory, as the
+//           RN16 decoder does (the decoder streamed them through L2 a moment ago), two j per lane -- j = lane and lane + 64 --
+//           and the gathers of all eight windows are in flight together.  |r|, r^2 and q^2 are formed in registers.
+//   minimum a wave minimum of min(|r_lane|, |r_lane+64|), then the first lane that holds it by ballot: among j < 64 first,
+//           among j >= 64 only when none of those does.
+//   sums    the 3 x 128 terms of a window are parked in LDS (rows 129 floats apart: the walkers' rows start in different
+//           banks) and 24 lanes -- one per (window, sum) -- walk a row each, from 0.0f in the order of j: 128 dependent
+//           additions for eight windows, against the 20 x 256 of the decoder's half-period search for three.
+//   store   the eight 32-byte records are put together in LDS and leave as one 256-byte row of the table, one word per lane.
+// Rows behind a trace's cut-off are zeroed, so the table's bytes repeat from pass to pass.  Single-wave workgroups, nothing
+// shared between them, no atomics: nothing depends on the order in which they run.
+// quality_gather_kernel then copies the records of the CRC-verified reads into one array aligned with the tracks.
+// Only primitives both device environments offer.
+#pragma once
+#include "rfid_tracks.hpp"
+
+namespace rfidk {
+
+constexpr int QUAL_PACK = 8;              // EPC windows per wave and step
+constexpr int QUAL_WGS_PER_CU = 8;        // most single-wave workgroups of a launch, per compute unit
+constexpr int QUAL_TERM_STRIDE = 129;     // = 1 mod 32
+constexpr int QUAL_WORDS = (int)(sizeof(rfid_read_quality) / sizeof(int));
+static_assert(sizeof(rfid_read_quality) == 32 && QUAL_PACK * QUAL_WORDS == 64, "one word per lane");
+static_assert(QUAL_PACK * 3 <= 32, "one bank per walker");
+
+struct QualArgs {
+  const float2 *y;                  // the matched filter's output of the pass
+  int64_t y_stride;
+  const rfid_window *wtab;          // [n_streams][wmax]
+  const rfid_decode_result *res;    // [n_streams][wmax]
+  const int *wcount;                // [n_streams]
+  const rfid_stream_stats *stats;   // [n_streams]: n_windows_used of the same pass
+  int wmax, n_streams;
+  int rows;                         // ceil(wmax / 2): EPC windows have odd seq, the row of one is seq >> 1
+  rfid_read_quality *table;         // [n_streams][rows]
+  int *nrows;                       // [n_streams]: EPC windows before the cut-off (n_windows_used / 2)
+};
+
+struct QualWin {     // what a window's gathers need (the same in every lane)
+  const float2 *src;
+  float dcr, dci, h_re, h_im, T, fidx;
+  int crc_ok;
+};
+
+RFID_DEVICE int qual_clamp(int i) { return (i < 0) ? 0 : ((i > EPC_WIN - 1) ? (EPC_WIN - 1) : i); }
+
+RFID_KERNEL(64) void quality_kernel(QualArgs a) {
+  RFID_SHARED float term[QUAL_PACK * 3 * QUAL_TERM_STRIDE];
+  RFID_SHARED int rec[QUAL_PACK * QUAL_WORDS];
+  const int lane = wv::lane_id();
+  const int packs_per = (a.rows + QUAL_PACK - 1) / QUAL_PACK;
+  const int64_t n_items = (int64_t)a.n_streams * packs_per;
+  int *table_w = reinterpret_cast<int *>(a.table);
+  for (int64_t it = (int64_t)blockIdx.x; it < n_items; it += (int64_t)gridDim.x) {
+    const int s = (int)(it / packs_per);
+    const int r0 = (int)(it - (int64_t)s * packs_per) * QUAL_PACK;
+    int nw = a.wcount[s];
+    {
+      const int used = a.stats[s].n_windows_used;
+      if (used < nw) nw = used;
+      if (nw > a.wmax) nw = a.wmax;
+      if (nw < 0) nw = 0;
+    }
+    const int nrows = nw >> 1;             // seq = 2 row + 1 < nw
+    if (r0 == 0 && lane == 0) a.nrows[s] = nrows;
+    const int my_row = r0 + (lane >> 3);   // (the record this lane stores a word of)
+    int *out = table_w + ((int64_t)s * a.rows + my_row) * QUAL_WORDS + (lane & 7);
+    if (r0 >= nrows) {                     // behind the cut-off
+      if (my_row < a.rows) *out = 0;
+      continue;
+    }
+    // ---- the eight windows: record, result, the 4 x 8 gathers ----
+    QualWin w[QUAL_PACK];
+    float2 pa[QUAL_PACK], qa[QUAL_PACK], pb[QUAL_PACK], qb[QUAL_PACK];
+#pragma unroll
+    for (int u = 0; u < QUAL_PACK; ++u) {
+      const int row = (r0 + u < nrows) ? (r0 + u) : r0;      // (a row behind the cut-off: the pack's first, its terms unused)
+      const int64_t k = (int64_t)s * a.wmax + (2 * row + 1);
+      const rfid_window wd = a.wtab[k];
+      const int *p = reinterpret_cast<const int *>(a.res + k);
+      int t0, t1, t2, t3, t4, d0, d1, d2;
+      wv::load4_i32(p, t0, t1, t2, t3);                      // type, index, h_re, h_im
+      wv::load4_i32(p + 4, t4, d0, d1, d2);                  // T, bits[0..2]
+      w[u].crc_ok = p[10];
+      w[u].src = a.y + (int64_t)s * a.y_stride + wd.start;
+      w[u].dcr = wd.dc_re; w[u].dci = wd.dc_im;
+      w[u].h_re = wv::u2f((uint32_t)t2); w[u].h_im = wv::u2f((uint32_t)t3); w[u].T = wv::u2f((uint32_t)t4);
+      w[u].fidx = (float)t1;
+    }
+#pragma unroll
+    for (int u = 0; u < QUAL_PACK; ++u) {
+      // the decoder's own gather (tag_decoder_impl.cc:171-190), indices held inside the window (not reached: they end at 1356)
+      const float T = w[u].T, T2 = 2.0f * T, fidx = w[u].fidx;
+      const int j0 = lane, j1 = lane + 64;
+      pa[u] = w[u].src[qual_clamp(wv::f2i((float)j0 * T2 + fidx))];
+      qa[u] = w[u].src[qual_clamp(wv::f2i(((float)(j0 * 2) * T + T) + fidx))];
+      pb[u] = w[u].src[qual_clamp(wv::f2i((float)j1 * T2 + fidx))];
+      qb[u] = w[u].src[qual_clamp(wv::f2i(((float)(j1 * 2) * T + T) + fidx))];
+    }
+    // ---- terms, minimum ----
+#pragma unroll
+    for (int u = 0; u < QUAL_PACK; ++u) {
+      const float dcr = w[u].dcr, dci = w[u].dci, h_re = w[u].h_re, h_im = w[u].h_im, nhim = -h_im;
+      // gate output in[i] - dc_est per component, then the difference of the two half-bit samples
+      const float dx0 = (pa[u].x - dcr) - (qa[u].x - dcr), dy0 = (pa[u].y - dci) - (qa[u].y - dci);
+      const float dx1 = (pb[u].x - dcr) - (qb[u].x - dcr), dy1 = (pb[u].y - dci) - (qb[u].y - dci);
+      const float r0v = dx0 * h_re - dy0 * nhim, q0v = dy0 * h_re - dx0 * h_im;
+      const float r1v = dx1 * h_re - dy1 * nhim, q1v = dy1 * h_re - dx1 * h_im;
+      const float a0 = __builtin_fabsf(r0v), a1 = __builtin_fabsf(r1v);
+      float *t = term + (u * 3) * QUAL_TERM_STRIDE;
+      t[lane] = a0; t[lane + 64] = a1;
+      t[QUAL_TERM_STRIDE + lane] = r0v * r0v; t[QUAL_TERM_STRIDE + lane + 64] = r1v * r1v;
+      t[2 * QUAL_TERM_STRIDE + lane] = q0v * q0v; t[2 * QUAL_TERM_STRIDE + lane + 64] = q1v * q1v;
+      float mn = (a1 < a0) ? a1 : a0;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) {
+        const float o = wv::shfl_xor(mn, off);
+        mn = (o < mn) ? o : mn;
+      }
+      const uint64_t lo = wv::ballot(a0 == mn), hi = wv::ballot(a1 == mn);
+      const int bit = lo ? wv::ffs64(lo) : (64 + (wv::ffs64(hi) & 63));
+      if (lane == 0) {
+        const bool on = r0 + u < nrows;
+        int *r = rec + u * QUAL_WORDS;
+        r[0] = on ? s : 0; r[1] = on ? (2 * (r0 + u) + 1) : 0;
+        r[5] = on ? (int)wv::f2u(mn) : 0; r[6] = on ? bit : 0; r[7] = on ? (w[u].crc_ok & 1) : 0;
+      }
+    }
+    wv::wave_sync();
+    // ---- the in-order sums: lane 3 u + c walks sum c of window u ----
+    if (lane < QUAL_PACK * 3) {
+      const float *t = term + lane * QUAL_TERM_STRIDE;
+      float acc = 0.0f;
+#pragma unroll 16
+      for (int j = 0; j < 128; ++j) acc = acc + t[j];
+      const int u = lane / 3, c = lane - 3 * u;
+      rec[u * QUAL_WORDS + 2 + c] = (r0 + u < nrows) ? (int)wv::f2u(acc) : 0;
+    }
+    wv::wave_sync();
+    if (my_row < a.rows) *out = rec[lane];
+    wv::wave_sync();   // (the next pack overwrites both areas)
+  }
+}
+
+// ---- the records of the CRC-verified reads, aligned with the tracks: quality[i] belongs to reads[i] ---------------------
+struct QualGatherArgs {
+  const rfid_tag_read *reads;       // the tracks of the same pass
+  const int *head;                  // [0] reads in all
+  int64_t cap;
+  const rfid_read_quality *table;   // [n_streams][rows]
+  int n_streams, rows;
+  rfid_read_quality *out;           // [cap]
+};
+
+constexpr int QUAL_GATHER_THREADS = 256;
+
+RFID_KERNEL(QUAL_GATHER_THREADS) void quality_gather_kernel(QualGatherArgs a) {
+  int64_t total = a.head[0];
+  if (total > a.cap) total = a.cap;
+  const int *table_w = reinterpret_cast<const int *>(a.table);
+  int *out_w = reinterpret_cast<int *>(a.out);
+  const int64_t n = total * QUAL_WORDS, step = (int64_t)gridDim.x * QUAL_GATHER_THREADS;
+  for (int64_t t = (int64_t)blockIdx.x * QUAL_GATHER_THREADS + (int64_t)threadIdx.x; t < n; t += step) {   // a word per thread
+    const int64_t i = t / QUAL_WORDS;
+    const int word = (int)(t - i * QUAL_WORDS);
+    const int s = a.reads[i].stream, row = a.reads[i].seq >> 1;
+    int v = 0;
+    if (s >= 0 && s < a.n_streams && row >= 0 && row < a.rows) v = table_w[((int64_t)s * a.rows + row) * QUAL_WORDS + word];
+    out_w[t] = v;
+  }
+}
+
+}  // namespace rfidk

@@ -43,6 +43,8 @@ class BatchDecoder:
         self._trk_planned = False
         self.last_inventory = None    # (entries, per-trace counts) of the last decode(..., inventory=True)
         self.last_tracks = None       # (reads, offsets) of the last decode(..., tracks=True)
+        self._qual_planned = False
+        self.last_quality = None      # one record per read, aligned with last_tracks[0], of the last decode(..., quality=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -53,8 +55,9 @@ class BatchDecoder:
         if self._planned[0] < n_traces or self._planned[1] < max_len:
             self.ctx.batch_plan(max(n_traces, self._planned[0]), max(max_len, self._planned[1]))
             self._planned = (max(n_traces, self._planned[0]), max(max_len, self._planned[1]))
-            self._inv_tags = 0        # (a new plan drops the inventory workspace, and the tracks workspace with it)
+            self._inv_tags = 0        # (a new plan drops the inventory workspace, and the tracks and quality workspaces with it)
             self._trk_planned = False
+            self._qual_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -64,14 +67,17 @@ class BatchDecoder:
         return stride
 
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
-               inventory: bool = False, max_tags: int = 64, tracks: bool = False):
+               inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
         of every trace (up to max_tags per trace) are listed on the device behind the pass and kept as
         `self.last_inventory` = (entries, per-trace counts); the return value is the same.  tracks=True (implies
         inventory=True): every tag's reads in time order are listed behind the inventory and kept as `self.last_tracks` =
-        (reads, offsets), offsets aligned with the entries."""
+        (reads, offsets), offsets aligned with the entries.  quality=True (implies tracks=True): the SNR and decision
+        margin of every EPC window are worked out behind the tracks; `self.last_quality` keeps one record per read, aligned
+        with the reads (quality_fields() turns them into snr_db and margin); a trace's whole row, failed windows included:
+        `self.ctx.batch_window_quality(stream)`."""
         torch = self._torch
         n = len(traces)
         lens = np.array([len(t) for t in traces], dtype=np.int64)
@@ -89,6 +95,7 @@ class BatchDecoder:
             self._lens_dev = torch.from_numpy(lens).to(dev.device, non_blocking=True)
             torch.cuda.current_stream().synchronize()
         t1 = time.perf_counter()
+        tracks = tracks or quality
         inventory = inventory or tracks
         if inventory and self._inv_tags != int(max_tags):
             self.ctx.batch_plan_inventory(int(max_tags))
@@ -97,17 +104,25 @@ class BatchDecoder:
         if tracks and not self._trk_planned:
             self.ctx.batch_plan_tracks()
             self._trk_planned = True
+            self._qual_planned = False
+        if quality and not self._qual_planned:
+            self.ctx.batch_plan_quality()
+            self._qual_planned = True
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
         if inventory:
             self.ctx.batch_inventory_enqueue()
         if tracks:
             self.ctx.batch_tracks_enqueue()
+        if quality:
+            self.ctx.batch_quality_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
             self.last_inventory = self.ctx.batch_inventory_fetch()
         if tracks:
             self.last_tracks = self.ctx.batch_tracks_fetch()
+        if quality:
+            self.last_quality = self.ctx.batch_quality_fetch()
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -187,27 +202,62 @@ TRACKS_HEADER = "file,epc,pc,seq,t_s,h_re,h_im,mag_db,phase_rad,T"
 TRACKS_RATE = 400e3       # samples per second behind the decimation of a 2 Msps trace: what rfid_window::start counts
 
 
-def format_tracks(entries: np.ndarray, reads: np.ndarray, offsets: np.ndarray, names: Sequence[str]) -> str:
+TRACKS_QUALITY_HEADER = TRACKS_HEADER + ",snr_db,margin"
+
+
+def quality_fields(q: np.ndarray):
+    """rfid_read_quality records -> (snr_db, margin), float64 arrays: snr_db = 10 log10(sig_sq / quad_sq) (+inf when
+    quad_sq == 0 < sig_sq, nan when both are 0), margin = margin_min / (sig_abs / 128): the weakest of the 128 decisions
+    relative to the mean one."""
+    q = np.asarray(q)
+    sig, quad = q["sig_sq"].astype(np.float64), q["quad_sq"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        snr_db = 10.0 * np.log10(sig / quad)
+        margin = q["margin_min"].astype(np.float64) / (q["sig_abs"].astype(np.float64) / 128.0)
+    return snr_db, margin
+
+
+def format_quality(rows: np.ndarray) -> str:
+    """One line for one trace's EPC windows before the cut-off (Context.batch_window_quality): how many there are, how many
+    failed their CRC, the median snr_db of the reads and of the failed windows, the weakest margin among the reads."""
+    rows = np.asarray(rows)
+    ok = (rows["flags"] & 1) != 0
+    snr_db, margin = quality_fields(rows)
+    med = lambda v: "%.2f" % float(np.median(v)) if len(v) else "-"
+    return ("| EPC windows : %d  failed : %d  median SNR dB reads : %s  failed : %s  weakest margin of a read : %s\n" %
+            (len(rows), int((~ok).sum()), med(snr_db[ok]), med(snr_db[~ok]), ("%.3f" % float(margin[ok].min())) if ok.any() else "-"))
+
+
+def format_tracks(entries: np.ndarray, reads: np.ndarray, offsets: np.ndarray, names: Sequence[str],
+                  quality: Optional[np.ndarray] = None) -> str:
     """CSV text, one line per read in the order of `reads` (grouped by tag, time order inside a tag):
     file,epc,pc,seq,t_s,h_re,h_im,mag_db,phase_rad,T with t_s = start / 400e3.  entries / offsets: the packed inventory
     and the offsets aligned with it (Context.batch_inventory_fetch / batch_tracks_fetch); names[stream]: the trace's file.
-    Floats are printed with %.9g: binary32 values survive the round trip."""
-    lines = [TRACKS_HEADER]
+    Floats are printed with %.9g: binary32 values survive the round trip.  quality (optional; the records aligned with
+    `reads`, Context.batch_quality_fetch): two more columns, snr_db,margin (quality_fields)."""
+    lines = [TRACKS_HEADER if quality is None else TRACKS_QUALITY_HEADER]
+    if quality is not None:
+        assert len(quality) == len(reads)
+        snr_db, margin = quality_fields(quality)
     for i, e in enumerate(entries):
         pc, epc = frame_fields(e["frame"])
         name = names[int(e["stream"])]
-        for r in reads[int(offsets[i]):int(offsets[i + 1])]:
+        for k in range(int(offsets[i]), int(offsets[i + 1])):
+            r = reads[k]
             re, im = np.float64(r["h_re"]), np.float64(r["h_im"])
             mag = float(np.hypot(re, im))
             db = 20.0 * np.log10(mag) if mag > 0 else float("-inf")
-            lines.append("%s,%s,%04x,%d,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g" %
-                         (name, epc, pc, int(r["seq"]), int(r["start"]) / TRACKS_RATE, float(r["h_re"]), float(r["h_im"]), db,
-                          float(np.arctan2(im, re)), float(r["T"])))
+            line = ("%s,%s,%04x,%d,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g" %
+                    (name, epc, pc, int(r["seq"]), int(r["start"]) / TRACKS_RATE, float(r["h_re"]), float(r["h_im"]), db,
+                     float(np.arctan2(im, re)), float(r["T"])))
+            if quality is not None:
+                line += ",%.9g,%.9g" % (float(snr_db[k]), float(margin[k]))
+            lines.append(line)
     return "\n".join(lines) + "\n"
 
 
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -218,6 +268,9 @@ def main(argv=None) -> int:
     ap.add_argument("--max-tags", type=int, default=64, help="distinct EPCs per trace the inventory has room for (1..512)")
     ap.add_argument("--tracks", metavar="OUT.csv", default=None,
                     help="write every tag's reads in time order (t_s, h_est, T) to this CSV file; implies --inventory")
+    ap.add_argument("--quality", action="store_true",
+                    help="one line per file on the SNR and decision margin of its EPC windows (built on the device); with --tracks the "
+                         "CSV gains the columns snr_db,margin")
     args = ap.parse_args(argv)
     if args.tracks:
         args.inventory = True
@@ -225,10 +278,12 @@ def main(argv=None) -> int:
     try:
         timing = {}
         stats, _, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
-                                            tracks=bool(args.tracks))
-        for path, row in zip(args.files, stats):
+                                            tracks=bool(args.tracks), quality=args.quality)
+        for i, (path, row) in enumerate(zip(args.files, stats)):
             print(path)
             print(format_results(row), end="")
+            if args.quality:
+                print(format_quality(dec.ctx.batch_window_quality(i)), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
               (len(args.files), timing["raw_samples"] / 1e6, timing["total_s"], timing["h2d_s"], timing["gpu_s"]))
         if args.inventory:
@@ -244,7 +299,7 @@ def main(argv=None) -> int:
         if args.tracks:
             reads, offsets = dec.last_tracks
             with open(args.tracks, "w") as f:
-                f.write(format_tracks(dec.last_inventory[0], reads, offsets, args.files))
+                f.write(format_tracks(dec.last_inventory[0], reads, offsets, args.files, dec.last_quality if args.quality else None))
     finally:
         dec.close()
     return 0

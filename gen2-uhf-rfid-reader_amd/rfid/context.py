@@ -363,6 +363,51 @@ class Context:
         self._chk(self._lib.rfid_batch_tracks_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
+    def batch_plan_quality(self) -> None:
+        """Reserves the quality workspace of the current plan (behind batch_plan_tracks; a new plan, batch_plan_inventory or
+        batch_plan_tracks drops it)."""
+        self._chk(self._lib.rfid_batch_plan_quality(self._h))
+
+    def batch_quality_enqueue(self) -> None:
+        """Asynchronous: the read quality of the last pass, behind its tracks (rfid_batch_quality)."""
+        self._chk(self._lib.rfid_batch_quality(self._h))
+
+    def batch_quality_fetch(self) -> np.ndarray:
+        """-> capi.QUALITY_DTYPE records of the last batch_quality_enqueue (synchronises), one per CRC-verified read:
+        record i belongs to reads[i] of batch_tracks_fetch."""
+        n = C.c_int64(0)
+        q = np.zeros(0, dtype=capi.QUALITY_DTYPE)
+        st = self._lib.rfid_batch_get_quality(self._h, None, 0, C.byref(n))
+        if st == capi.ERR_CAPACITY and n.value > 0:      # (the size is known now; a trace that overflowed fails again below)
+            q = np.zeros(n.value, dtype=capi.QUALITY_DTYPE)
+            st = self._lib.rfid_batch_get_quality(self._h, q.ctypes.data, len(q), C.byref(n))
+        self._chk(st)
+        return q
+
+    def batch_quality(self) -> np.ndarray:
+        """SNR and decision margin of every read of the last pass, built on the device behind batch_tracks():
+        see batch_quality_fetch; rfid.batch.quality_fields turns the records into snr_db and margin."""
+        self.batch_quality_enqueue()
+        return self.batch_quality_fetch()
+
+    def batch_window_quality(self, stream: int, extra: int = 0) -> np.ndarray:
+        """Debug tap (synchronises): the records of EVERY EPC window of one trace before the cut-off, in seq order, failed
+        ones included (n_windows_used // 2 of them), of the last batch_quality_enqueue.  extra > 0: up to that many of the
+        table's rows behind them as well (zeroed by the stage)."""
+        n = C.c_int64(0)
+        st = self._lib.rfid_batch_get_window_quality(self._h, int(stream), None, 0, C.byref(n))
+        if st not in (capi.OK, capi.ERR_CAPACITY):
+            self._chk(st)
+        q = np.zeros(n.value + max(int(extra), 0), dtype=capi.QUALITY_DTYPE)
+        if len(q):
+            self._chk(self._lib.rfid_batch_get_window_quality(self._h, int(stream), q.ctypes.data, len(q), C.byref(n)))
+        return q
+
+    def batch_quality_ms(self) -> float:
+        ms = C.c_float(0.0)
+        self._chk(self._lib.rfid_batch_quality_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

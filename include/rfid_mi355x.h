@@ -148,6 +148,33 @@ typedef struct rfid_tag_read {       /* 32 bytes */
   int32_t index;                     /* rfid_decode_result::index (tag_sync's return value) */
 } rfid_tag_read;
 
+/* how good the decision of one EPC window was: what the quality stage (rfid_batch_quality) works out for EVERY EPC window
+ * before the TERMINATED cut-off, CRC-verified or not, from the 128 decision values of tag_detection_EPC
+ * (lib/tag_decoder_impl.cc:171-190) and their quadrature counterparts.  THE DEFINITION (the contract; binary32 throughout,
+ * every operation rounded by itself, no fused multiply-add):
+ *   from the window's own rfid_decode_result (h_re, h_im, T, index) and its gated samples
+ *   s[i] = y[start + i] - dc per component (y: the matched filter's output, start / dc: the window's rfid_window),
+ *   for j = 0 .. 127:
+ *     ia  = (int)((float)j * (2.0f * T) + (float)index)
+ *     ib  = (int)(((float)(j * 2) * T + T) + (float)index)
+ *     dx  = s[ia].x - s[ib].x,  dy = s[ia].y - s[ib].y
+ *     r_j = dx * h_re - dy * (-h_im)         the decoder's decision value, Re((s_a - s_b) conj(h_est))
+ *     q_j = dy * h_re - dx * h_im            the imaginary part of the same product: noise and interference only
+ *   the three sums are IN-ORDER sums (((0.0f + t_0) + t_1) + ...) + t_127: a record is a function of the input alone and
+ *   is compared by bit pattern.  (A window with a non-finite sample: unspecified, as its decoding is.)
+ * What a host makes of it (rfid.batch.quality_fields, in binary64): snr_db = 10 log10(sig_sq / quad_sq) -- CRC-verified
+ * reads lie some 6 dB per halving of the noise above the ~0 dB of an empty or collided slot -- and
+ * margin = margin_min / (sig_abs / 128), the weakest decision relative to the mean one. */
+typedef struct rfid_read_quality {   /* 32 bytes */
+  int32_t stream, seq;               /* the EPC window (rfid_window::stream / seq) */
+  float   sig_abs;                   /* sum_j |r_j|      j = 0..127, ascending, from 0.0f, binary32 */
+  float   sig_sq;                    /* sum_j r_j * r_j  same order */
+  float   quad_sq;                   /* sum_j q_j * q_j  same order */
+  float   margin_min;                /* min_j |r_j| */
+  int32_t margin_bit;                /* the first j that attains it (a = |r_0|; j = 1..127: if (|r_j| < a) take j) */
+  int32_t flags;                     /* bit 0: crc_ok of the window's result */
+} rfid_read_quality;
+
 /* timing of the last rfid_batch_* pass, from HIP events on the ctx stream */
 typedef struct rfid_batch_timing {
   float mf_ms, gate_ms, decode_ms, stats_ms; /* kernel time per pass (summed over the launches of a pass) */
@@ -488,6 +515,34 @@ RFID_API int rfid_batch_tracks(rfid_ctx *ctx);
 RFID_API int rfid_batch_get_tracks(rfid_ctx *ctx, rfid_tag_read *reads, int64_t cap, int64_t *n, int64_t *offsets);
 /* synchronises; device time of the last rfid_batch_tracks (HIP events), from its first launch to the end of its last */
 RFID_API int rfid_batch_tracks_ms(rfid_ctx *ctx, float *ms);
+/* ---- (2d) batch read quality: per-read SNR and decision margin, built on the device -------------------------------- */
+/* Behind the tracks of a pass: one rfid_read_quality (see its definition above) per EPC window with seq < n_windows_used,
+ * CRC-verified or not, in a device table [n_streams][ceil(wmax / 2)] (row = seq >> 1; the rows of a trace behind its
+ * cut-off are zeroed: the table's bytes repeat from pass to pass), and the records of the CRC-verified reads once more as
+ * ONE array aligned with the tracks: quality[i] belongs to reads[i] of rfid_batch_get_tracks.
+ * rfid_batch_plan_quality reserves both (2 x 32 bytes per possible EPC window).  RFID_ERR_STATE without a tracks
+ * workspace; RFID_ERR_HIP when the allocation fails (the plan, the inventory and the tracks workspace stay usable).  A
+ * new rfid_batch_plan, rfid_batch_plan_inventory or rfid_batch_plan_tracks drops it. */
+RFID_API int rfid_batch_plan_quality(rfid_ctx *ctx);
+/* enqueues the quality of the LAST pass behind its tracks (asynchronous, no host synchronisation).  RFID_ERR_STATE: no
+ * quality workspace, or no rfid_batch_tracks was enqueued since the last pass.
+ * It reads that pass's matched-filter output, window table, results and statistics on the context's main stream.  With two
+ * result sets alternating (RFID_OVERLAP=2) all four belong to the set and the next pass's front end, on the same stream,
+ * runs behind it.  The long-stream front end alternates the matched-filter output alone and starts a pass's first launch on
+ * the second stream as soon as its buffer is free: this call records that buffer's "free" event again behind its own
+ * launches, so the pass after next, which gets the buffer, waits for them. */
+RFID_API int rfid_batch_quality(rfid_ctx *ctx);
+/* synchronises; *n = reads in all, the number rfid_batch_get_tracks reports; q[i] belongs to its reads[i].
+ * RFID_ERR_CAPACITY as there: cap too small (nothing lost: *n says how many there are, call again; q may be NULL with
+ * cap = 0), or a trace overflowed the inventory (rfid_last_error names the first such trace) */
+RFID_API int rfid_batch_get_quality(rfid_ctx *ctx, rfid_read_quality *q, int64_t cap, int64_t *n);
+/* synchronises; debug tap (as rfid_batch_get_mf) and the way to look at failed slots: one trace's row of the table, every
+ * EPC window before the cut-off in seq order, failed ones included: *n = n_windows_used / 2 as the statistics count it.
+ * RFID_ERR_CAPACITY when cap < *n (nothing is copied; q may be NULL with cap = 0).  With cap > *n the table's rows behind
+ * *n are copied too, up to min(cap, ceil(wmax / 2)) records in all: they are zero. */
+RFID_API int rfid_batch_get_window_quality(rfid_ctx *ctx, int stream, rfid_read_quality *q, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_quality (HIP events), from its first launch to the end of its last */
+RFID_API int rfid_batch_quality_ms(rfid_ctx *ctx, float *ms);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
