@@ -63,6 +63,13 @@ DUMP_DTYPE = np.dtype([
 assert DUMP_DTYPE.itemsize == C.sizeof(DecodeDump), (DUMP_DTYPE.itemsize, C.sizeof(DecodeDump))
 
 
+class Decoder(C.Structure):
+    _fields_ = [("n_samples_TAG_BIT", C.c_float), ("T_global", C.c_float), ("h_est", Cf), ("char_bits", C.c_char * 128)]
+
+
+WINDOW_LEN = {DECODE_RN16: 250, DECODE_EPC: 1370}
+
+
 def build(force: bool = False) -> str:
     src = os.path.join(_HERE, "rfid_oracle.c")
     hdr = os.path.join(_HERE, "rfid_oracle.h")
@@ -117,6 +124,11 @@ def lib() -> C.CDLL:
         L.orc_check_crc.restype = C.c_int
         L.orc_crc16_bytes.argtypes = [C.c_char_p, C.c_int]
         L.orc_crc16_bytes.restype = C.c_uint
+        L.orc_decoder_init.argtypes = [C.POINTER(Decoder), C.c_int]
+        L.orc_decoder_work.argtypes = [C.POINTER(Decoder), C.POINTER(ReaderState), vp, C.c_int, vp, C.POINTER(C.c_int),
+                                       C.POINTER(DecodeDump)]
+        L.orc_decoder_work.restype = C.c_int
+        L.orc_reader_work.argtypes = [C.POINTER(ReaderState), C.c_int]
         _lib = L
     return _lib
 
@@ -177,6 +189,66 @@ def run_trace(raw: np.ndarray, cfg: Optional[Config] = None, chunk: int = 4096,
 def run_decimated(y: np.ndarray, cfg: Optional[Config] = None, chunk: int = 4096,
                   max_dumps: Optional[int] = None) -> Result:
     return _run(lib().orc_run_decimated, cfg or config(), y, chunk, max_dumps)
+
+
+class BlockSim:
+    """tag_decoder and reader stepped call by call on windows handed in as the gate would hand them out: DC-free samples,
+    their squared magnitudes in READER_STATE (gate_impl.cc:175-176,186-187), n_samples_to_ungate armed at a SEEK_*
+    (gate_impl.cc:112-123)."""
+
+    def __init__(self, cfg: Optional[Config] = None):
+        self.cfg = cfg or config()
+        self.dec = Decoder()
+        self.state = ReaderState()
+        lib().orc_decoder_init(C.byref(self.dec), 400000)
+        lib().orc_initialize_reader_state(C.byref(self.state), C.byref(self.cfg))
+
+    def reader_until_idle(self, n_in: int = 0) -> None:
+        rs = self.state
+        for _ in range(8):
+            before = rs.gen2_logic_status
+            if before == 3:           # IDLE
+                break
+            lib().orc_reader_work(C.byref(rs), int(n_in))
+            n_in = 0
+            if rs.gen2_logic_status == before:
+                break
+
+    def arm_gate(self) -> None:
+        rs = self.state
+        if rs.gate_status in (2, 3):  # SEEK_RN16 / SEEK_EPC -> CLOSED
+            rs.n_samples_to_ungate = WINDOW_LEN[DECODE_EPC if rs.gate_status == 3 else DECODE_RN16]
+            rs.gate_status = 1
+
+    def decoder_work(self, win: np.ndarray):
+        """-> (consumed, port-0 floats, dump record): one orc_decoder_work call on `win`"""
+        win = np.ascontiguousarray(win, dtype=np.complex64)
+        assert len(win) <= ORC_MAX_MAGN
+        rs = self.state
+        m2 = win.real * win.real + win.imag * win.imag      # std::norm, two products and one sum in binary32
+        assert m2.dtype == np.float32
+        C.memmove(C.addressof(rs) + ReaderState.magn_squared.offset, m2.ctypes.data, m2.nbytes)
+        rs.n_magn = len(m2)
+        out0 = np.zeros(16, dtype=np.float32)
+        dump = np.zeros(1, dtype=DUMP_DTYPE)
+        cons = C.c_int(0)
+        n = lib().orc_decoder_work(C.byref(self.dec), C.byref(rs), win.ctypes.data, len(win), out0.ctypes.data, C.byref(cons),
+                                   C.cast(dump.ctypes.data, C.POINTER(DecodeDump)))
+        return cons.value, out0[:n].copy(), dump[0]
+
+
+def decode_window(win: np.ndarray, type: int):
+    """One window through tag_decoder_impl::general_work on a fresh decoder and reader state.  win: complex64, already
+    DC-free, 250 (type 0, RN16) or 1370 (type 1, EPC) samples.  -> DUMP_DTYPE record: index, h_est, corr[15],
+    energy[20], T, n_bits, bits, crc_ok, tag_id (energy / T / crc_ok / tag_id are zero for an RN16 window, tag_id for a
+    frame whose CRC fails)."""
+    assert type in WINDOW_LEN and len(win) == WINDOW_LEN[type], (type, len(win))
+    sim = BlockSim()
+    sim.state.decoder_status = type
+    sim.state.n_samples_to_ungate = len(win)
+    cons, _, dump = sim.decoder_work(win)
+    assert cons == len(win) and dump["type"] == type and dump["n_bits"] == (128 if type else 16)
+    return dump
 
 
 class Stream:

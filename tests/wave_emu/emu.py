@@ -206,7 +206,41 @@ def chain_scan2(x, ca, cb):
     return oa, ob, bool(sc.value)
 
 
-def mf_stream(staging: np.ndarray, in_off: int, n_out: int) -> np.ndarray:
+DECODE_ALL, DECODE_EPC3, DECODE_RN16X4 = 0, 1, 2
+RES_FILL, SCORE_FILL, SUM_FILL = 0xA5, 0x5A, 0x3C     # the bytes decode_lists() prefills the result tables with
+
+
+def decode_lists(y: np.ndarray, epc, rn16, which: int = DECODE_ALL, n_wg: int = 1, wmax: int = 0, schedule: str = "seq", seed: int = 0):
+    """Caller-given window lists (capi.WINDOW_DTYPE records: start, dc, type; stream 0, seq = the result slot) through
+    decode_all_kernel, or decode_epc3_kernel / decode_rn16x4_kernel on their own, on n_wg one-wave workgroups.
+    -> dict(results, scores, sum, tickets): [wmax] tables prefilled with RES_FILL / SCORE_FILL / SUM_FILL bytes."""
+    y = np.ascontiguousarray(y, dtype=np.complex64)
+    epc = np.ascontiguousarray(epc, dtype=capi.WINDOW_DTYPE)
+    rn16 = np.ascontiguousarray(rn16, dtype=capi.WINDOW_DTYPE)
+    wmax = max(int(wmax), 1)
+    results = np.frombuffer(bytearray([RES_FILL]) * (wmax * capi.RESULT_DTYPE.itemsize), dtype=capi.RESULT_DTYPE)
+    scores = np.frombuffer(bytearray([SCORE_FILL]) * (wmax * capi.SCORES_DTYPE.itemsize), dtype=capi.SCORES_DTYPE)
+    sums = np.frombuffer(bytearray([SUM_FILL]) * (wmax * 4), dtype=np.int32)
+    tickets = np.array([0, 12345], dtype=np.int32)
+    L = lib()
+    L.emu_schedule(SCHEDULES[schedule], C.c_ulonglong(seed))
+    try:
+        rc = L.emu_decode_lists(C.c_void_p(y.ctypes.data), C.c_long(len(y)),
+                                C.c_void_p(epc.ctypes.data) if len(epc) else None, len(epc),
+                                C.c_void_p(rn16.ctypes.data) if len(rn16) else None, len(rn16), int(which), int(n_wg), wmax,
+                                C.c_void_p(results.ctypes.data), C.c_void_p(scores.ctypes.data), C.c_void_p(sums.ctypes.data),
+                                C.c_void_p(tickets.ctypes.data))
+    finally:
+        L.emu_schedule(0, C.c_ulonglong(0))
+    if rc == EMU_DEADLOCK:
+        _raise_deadlock(L, "decode_lists")
+    assert rc == 0, rc
+    return dict(results=results, scores=scores, sum=sums, tickets=tickets)
+
+
+def mf_stream(staging: np.ndarray, in_off: int, n_out: int, unaligned: bool = False) -> np.ndarray:
+    """mf_boxcar25_decim5_kernel in its streaming form: output k sums staging[in_off + 5 k + 0..24] (samples in front of the
+    staging buffer count as zeros)."""
     buf = np.zeros(len(staging) + 2, dtype=np.complex64)
     off = (16 - buf.ctypes.data % 16) % 16 // 8
     if unaligned:          # rows 8-byte aligned only: the kernels' float2 load path

@@ -655,6 +655,38 @@ int emu_decode_one(const float *win, int type, rfid_decode_result *res, rfid_sco
   return run.rc(0);
 }
 
+// caller-given window lists through the batched decoders: which 0 = decode_all_kernel (as rfid_batch_decode launches it), 1 =
+// decode_epc3_kernel alone, 2 = decode_rn16x4_kernel alone, on n_wg one-wave workgroups.  y: one row of n_y samples; the windows
+// give start, dc and type themselves (stream 0, seq < wmax: the slot of res / scores / sum, which the caller prefills -- the
+// slots of windows in no list must come back untouched).  A list of length 0 may be a null pointer.  tickets[2]: the launch's
+// ticket counter and the next launch's, as decode_all_kernel leaves them (given in: 0 and a non-zero value).
+int emu_decode_lists(const float *y, long n_y, const rfid_window *epc, int n_epc, const rfid_window *rn16, int n_rn16, int which,
+                     int n_wg, int wmax, rfid_decode_result *res, rfid_scores *scores, int *sum, int *tickets) {
+  EmuRun run;
+  if (n_wg < 1 || n_epc < 0 || n_rn16 < 0 || (n_epc && !epc) || (n_rn16 && !rn16)) return -1;
+  for (int k = 0; k < n_epc + n_rn16; ++k) {   // every window inside y and inside the result tables, and in the list of its type
+    const rfid_window &w = (k < n_epc) ? epc[k] : rn16[k - n_epc];
+    const int type = (k < n_epc) ? RFID_DECODE_EPC : RFID_DECODE_RN16;
+    if (w.type != type || w.stream != 0 || w.seq < 0 || w.seq >= wmax || w.start < 0 ||
+        (long)w.start + (type ? EPC_WIN : RN16_WIN) > n_y)
+      return -1;
+  }
+  DecodeListArgs da;
+  da.y = reinterpret_cast<const float2 *>(y); da.y_stride = n_y; da.cap = wmax; da.res = res; da.scores = scores; da.wmax = wmax;
+  da.sum = sum;
+  rfidh::t_candidates(da.t_cand, 400000);
+  DecodeAllArgs all;
+  all.epc = da; all.rn16 = da; all.ticket = &tickets[0]; all.ticket_next = &tickets[1];
+  all.epc.list = epc; all.epc.count = &n_epc;
+  all.rn16.list = rn16; all.rn16.count = &n_rn16;
+  const emu::Idx3 grid{(unsigned)n_wg, 1, 1}, block{64, 1, 1};
+  if (which == 0) emu::launch(grid, block, [&]() { decode_all_kernel(all); }, "decode_all_kernel");
+  else if (which == 1) emu::launch(grid, block, [&]() { decode_epc3_kernel(all.epc); }, "decode_epc3_kernel");
+  else if (which == 2) emu::launch(grid, block, [&]() { decode_rn16x4_kernel(all.rn16); }, "decode_rn16x4_kernel");
+  else return -1;
+  return run.rc(0);
+}
+
 // primitives self-test kernel
 int emu_selftest(const float *x, const float *num, const float *den, float carry, float *chain_out,
                  float *div_out, float *hyp_out, float *shr_out) {
