@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <new>
@@ -287,41 +288,41 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
+  // ---- the stages behind a pass: inventory, tracks, quality.  What the three share ----
+  struct Stage {
+    void *blk = nullptr;              // one allocation, carved up (stage_alloc)
+    hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
+    bool enqueued = false;            // the stage's launches are behind the events (survives a new pass: the stage's get
+                                      // function may still fetch the earlier output)
+  };
   // ---- inventory stage (rfid_batch_plan_inventory): lives and dies with the plan ----
-  struct Inventory {
-    void *blk = nullptr;              // one allocation, carved up
+  struct Inventory : Stage {
     int max_tags = 0, slots = 0;
     rfid_tag_entry *d_ent = nullptr, *d_packed = nullptr;   // [B_plan][max_tags] each
     int *d_counts = nullptr, *d_over = nullptr, *d_off = nullptr, *d_head = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool enqueued = false;            // an rfid_batch_inventory is behind the events
     int n_streams = 0;                // traces it covered
   } inv;
-  bool inv_current = false;           // an rfid_batch_inventory was enqueued behind the statistics of the LAST pass (Inventory::enqueued
-                                      // survives a new pass: rfid_batch_get_inventory may still fetch the earlier one)
   // ---- tracks stage (rfid_batch_plan_tracks): lives and dies with the inventory workspace ----
-  struct Tracks {
-    void *blk = nullptr;              // one allocation, carved up
+  struct Tracks : Stage {
     rfid_tag_read *d_reads = nullptr; // [cap]
     int64_t cap = 0;                  // B_plan x ceil(wmax / 2)
     int64_t *d_off = nullptr;         // [B_plan x max_tags + 1]
     int *d_base = nullptr, *d_head = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool enqueued = false;            // an rfid_batch_tracks is behind the events
   } trk;
-  bool trk_current = false;           // an rfid_batch_tracks was enqueued behind the inventory of the LAST pass
   // ---- quality stage (rfid_batch_plan_quality): lives and dies with the tracks workspace ----
-  struct Quality {
-    void *blk = nullptr;              // one allocation, carved up
+  struct Quality : Stage {
     rfid_read_quality *d_table = nullptr;   // [B_plan][rows]
     rfid_read_quality *d_packed = nullptr;  // [trk.cap]: aligned with the tracks
     int *d_nrows = nullptr;           // [B_plan]: EPC windows before the cut-off
     int rows = 0;                     // ceil(wmax / 2)
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    bool enqueued = false;            // an rfid_batch_quality is behind the events
     int n_streams = 0;                // traces it covered
   } qual;
-  bool stats_current = false;         // d_stats holds the statistics of the results in d_res (rfid_batch_stats ran behind the last decode)
+  // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
+  // (rfid_batch_stats ran behind the last decode), the inventory was enqueued behind those statistics, the tracks behind
+  // that inventory.  A stage is current only while every stage before it is: one ordered level, moved by mark_current and
+  // invalidate_from alone.
+  enum Current { CUR_NONE = 0, CUR_STATS, CUR_INVENTORY, CUR_TRACKS };
+  int current = CUR_NONE;
   int n_chunks_last = 0;   // > 0 when the last pass used the overlapped path
   int fused_last = 0;      // 1 when the last rfid_batch_process pass used front_end_fused_kernel
   float front_ms = 0.0f;
@@ -440,24 +441,105 @@ void init_reader_state(rfid_ctx *c) {  // global_vars.cc:34-54
   c->rs.cur_slot_number = 1;
 }
 
+// ---- which outputs belong to the last pass (rfid_ctx::current) ----
+// `stage` was enqueued behind the stage before it: current up to here, and whatever stood behind an earlier run is not
+void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
+// `stage` and everything behind it no longer belong to the last pass
+void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
+
+// ---- what the inventory, tracks and quality stages share on the host ----
+size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+void stage_free(rfid_ctx::Stage &st) {
+  if (st.blk) (void)hipFree(st.blk);
+  st.blk = nullptr; st.enqueued = false;
+}
+
+// One allocation for a stage's workspace, carved into 256-byte aligned pieces in the order given, and the stage's two
+// events when they do not exist yet.  `what`: the error a failed allocation leaves.
+struct StagePiece { void **p; size_t bytes; };
+int stage_alloc(rfid_ctx *c, rfid_ctx::Stage &st, const char *what, std::initializer_list<StagePiece> pieces) {
+  for (int i = 0; i < 2; ++i)
+    if (!st.ev[i]) HIPCHK(c, hipEventCreate(&st.ev[i]));
+  size_t total = 0;
+  for (const StagePiece &pc : pieces) total += up256(pc.bytes);
+  hipError_t e = hipMalloc(&st.blk, total);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    st.blk = nullptr;
+    return fail(c, RFID_ERR_HIP, what, e);
+  }
+  char *b = (char *)st.blk;
+  for (const StagePiece &pc : pieces) { *pc.p = b; b += up256(pc.bytes); }
+  return RFID_OK;
+}
+
+// the event in front of (0) or behind (1) a stage's launches
+int stage_record(rfid_ctx *c, rfid_ctx::Stage &st, int which) {
+  HIPCHK(c, hipEventRecord(st.ev[which], c->stream));
+  return RFID_OK;
+}
+
+int stage_ms(rfid_ctx *c, rfid_ctx::Stage &st, float *ms) {
+  if (!st.blk || !st.enqueued) return RFID_ERR_STATE;
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipEventSynchronize(st.ev[1]));
+  HIPCHK(c, hipEventElapsedTime(ms, st.ev[0], st.ev[1]));
+  return RFID_OK;
+}
+
+// What fetching a stage's output begins with.  Reads the inventory's head ([0] entries in all, [1] the first trace that
+// overflowed) and, with `d_reads_head`, the tracks' (reads in all), behind everything enqueued so far.  *n: the records the
+// caller's array has to hold -- reads with `d_reads_head`, entries without.  RFID_ERR_CAPACITY under `fn`'s name when a
+// trace overflowed the inventory, then when `cap` is smaller than *n.
+int stage_fetch_head(rfid_ctx *c, const char *fn, const int *d_reads_head, int64_t cap, int64_t *n, int *n_entries) {
+  int head[2] = {0, 0}, total = 0;
+  HIPCHK(c, hipMemcpyAsync(head, c->inv.d_head, sizeof(head), hipMemcpyDeviceToHost, c->stream));
+  if (d_reads_head) HIPCHK(c, hipMemcpyAsync(&total, d_reads_head, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n_entries = head[0];
+  *n = d_reads_head ? total : head[0];
+  if (head[1] != INV_EMPTY) {
+    snprintf(c->err, sizeof(c->err), "%s: trace %d holds more than max_tags_per_trace = %d distinct frames", fn, head[1], c->inv.max_tags);
+    return RFID_ERR_CAPACITY;
+  }
+  if (*n > cap) {
+    snprintf(c->err, sizeof(c->err), "%s: cap is smaller than the number of %s", fn, d_reads_head ? "reads" : "entries");
+    return RFID_ERR_CAPACITY;
+  }
+  return RFID_OK;
+}
+
+// ---- launch geometry of the kernels that take one workgroup per trace (statistics, inventory, tracks) ----
+// one wave per trace; sixteen when a trace can hold thousands of windows (few long traces)
+static_assert(STATS_MAX_WAVES == INV_MAX_WAVES, "one rule for the three kernels");
+bool wide_traces(const rfid_ctx *c) { return c->wmax > 2048; }
+dim3 trace_block(const rfid_ctx *c) { return dim3(wide_traces(c) ? 64 * INV_MAX_WAVES : 64); }
+// the one workgroup of an offsets scan over n traces (scan_share / scan_partials, csrc/rfid_inventory.hpp)
+dim3 scan_block(int n) { return dim3((unsigned)((n >= INV_SCAN_THREADS) ? INV_SCAN_THREADS : ((n + 63) & ~63))); }
+
 void free_quality(rfid_ctx *c) {
-  if (c->qual.blk) (void)hipFree(c->qual.blk);
-  c->qual.blk = nullptr; c->qual.rows = 0; c->qual.enqueued = false;
+  stage_free(c->qual);
+  c->qual.rows = 0;
 }
 
 void free_tracks(rfid_ctx *c) {
   free_quality(c);                     // (sized by this workspace, and reading it)
-  c->trk_current = false;
-  if (c->trk.blk) (void)hipFree(c->trk.blk);
-  c->trk.blk = nullptr; c->trk.cap = 0; c->trk.enqueued = false;
+  invalidate_from(c, rfid_ctx::CUR_TRACKS);
+  stage_free(c->trk);
+  c->trk.cap = 0;
+}
+
+void free_inventory(rfid_ctx *c) {
+  free_tracks(c);                      // (sized by this workspace, and reading it)
+  invalidate_from(c, rfid_ctx::CUR_INVENTORY);
+  stage_free(c->inv);
+  c->inv.max_tags = 0;
 }
 
 void free_plan(rfid_ctx *c) {
-  free_tracks(c);
-  c->inv_current = false;
-  if (c->inv.blk) (void)hipFree(c->inv.blk);
-  c->inv.blk = nullptr; c->inv.max_tags = 0; c->inv.enqueued = false;
-  c->stats_current = false;
+  free_inventory(c);
+  invalidate_from(c, rfid_ctx::CUR_STATS);
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
   if (c->alt_y_blk) (void)hipFree(c->alt_y_blk);
@@ -963,12 +1045,9 @@ int rfid_ctx_destroy(rfid_ctx *c) {
   if (c->ls2_host) (void)hipHostFree(c->ls2_host);
   for (int i = 0; i < 5; ++i)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-  for (int i = 0; i < 2; ++i)
-    if (c->inv.ev[i]) (void)hipEventDestroy(c->inv.ev[i]);
-  for (int i = 0; i < 2; ++i)
-    if (c->trk.ev[i]) (void)hipEventDestroy(c->trk.ev[i]);
-  for (int i = 0; i < 2; ++i)
-    if (c->qual.ev[i]) (void)hipEventDestroy(c->qual.ev[i]);
+  for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual})
+    for (int i = 0; i < 2; ++i)
+      if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
     (void)hipStreamSynchronize(c->stream2);
     for (int i = 0; i <= rfid_ctx::MAX_CHUNKS; ++i)
@@ -1181,7 +1260,6 @@ int rfid_batch_plan(rfid_ctx *c, int n_streams, int64_t max_raw) {
   // one allocation per result set, carved up (256-byte aligned pieces): a plan -- every rfid_stream_begin and
   // rfid_lookahead_enable makes one -- costs one hipMalloc, not nine
   hipError_t e = hipSuccess;
-  auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
   const size_t sz_y = up256(sizeof(float2) * (size_t)c->y_stride * n_streams), sz_g = up256(sizeof(GateState) * (size_t)n_streams),
                sz_w = up256(sizeof(rfid_window) * (size_t)c->flat_cap), sz_f = up256(sizeof(rfid_window) * 2 * (size_t)c->flat_cap),
                sz_c = up256(sizeof(int) * (size_t)n_streams), sz_fc = 256, sz_r = up256(sizeof(rfid_decode_result) * (size_t)c->flat_cap),
@@ -1205,7 +1283,7 @@ int rfid_batch_plan(rfid_ctx *c, int n_streams, int64_t max_raw) {
     return fail(c, RFID_ERR_HIP, "rfid_batch_plan: workspace allocation", e);
   }
   c->B = c->B_plan = n_streams;
-  if (c->wmax > 2048) {
+  if (wide_traces(c)) {
     // few, long traces: the statistics kernel is one workgroup per trace, and 48-byte results through one CU are its whole
     // time (0.36 ms for configs[2]'s 320 000 windows); the decoder leaves the word it needs of each (doing without is fine)
     if (hipMalloc((void **)&c->d_sum, sizeof(int) * ((size_t)c->flat_cap + 4)) != hipSuccess) { (void)hipGetLastError(); c->d_sum = nullptr; }
@@ -1327,8 +1405,7 @@ static int rfid_batch_gate_impl(rfid_ctx *c, const int *skip_if) {
   a.state = c->d_gstate; a.n_streams = c->B; a.wtab = c->d_wtab; a.wmax = c->wmax; a.wcount = c->d_wcount;
   a.flat = c->d_flat; a.flat_count = c->d_flat_count; a.flat_cap = c->flat_cap; a.mode = 0;
   a.gated = nullptr; a.gated_cap = 0; a.io = nullptr;
-  c->stats_current = false;
-  c->inv_current = false;
+  invalidate_from(c, rfid_ctx::CUR_STATS);
   if (!c->ev_valid[1]) { HIPCHK(c, hipEventRecord(c->ev[1], c->stream)); c->ev_valid[1] = true; }
   hipLaunchKernelGGL(gate_scan_kernel, dim3((unsigned)((c->B + GATE_STREAMS_PER_WG - 1) / GATE_STREAMS_PER_WG)), dim3(GATE_THREADS), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
@@ -1368,8 +1445,7 @@ int rfid_batch_decode(rfid_ctx *c, int want_scores) {
   d.ticket = c->d_ticket + (c->ticket_flip & 1);        // (both zero after rfid_ctx_create; every launch zeroes the other one)
   d.ticket_next = c->d_ticket + ((c->ticket_flip & 1) ^ 1);
   c->ticket_flip ^= 1;
-  c->stats_current = false;
-  c->inv_current = false;
+  invalidate_from(c, rfid_ctx::CUR_STATS);
   hipLaunchKernelGGL(decode_all_kernel, dim3((unsigned)grid), dim3(64), 0, ts, d);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[3], ts));
@@ -1390,13 +1466,11 @@ int rfid_batch_stats(rfid_ctx *c) {
   hipStream_t ts = c->tail_stream ? c->tail_stream : c->stream;
   if (!c->tail_stream) { int rj = join_tails(c); if (rj) return rj; }
   if (!c->ev_valid[3]) { HIPCHK(c, hipEventRecord(c->ev[3], ts)); c->ev_valid[3] = true; }
-  // one wave per trace; sixteen when a trace can hold thousands of windows (few long traces)
-  hipLaunchKernelGGL(stream_stats_kernel, dim3((unsigned)c->B), dim3(c->wmax > 2048 ? 64 * STATS_MAX_WAVES : 64), 0, ts, a);
+  hipLaunchKernelGGL(stream_stats_kernel, dim3((unsigned)c->B), trace_block(c), 0, ts, a);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev[4], ts));
   c->ev_valid[4] = true;
-  c->stats_current = true;
-  c->inv_current = false;
+  mark_current(c, rfid_ctx::CUR_STATS);
   return RFID_OK;
 }
 
@@ -1413,23 +1487,12 @@ int rfid_batch_plan_inventory(rfid_ctx *c, int max_tags) {
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   rfid_ctx::Inventory &v = c->inv;
-  free_tracks(c);                      // (sized by this workspace, and reading it)
-  c->inv_current = false;
-  if (v.blk) HIPCHK(c, hipFree(v.blk));
-  v.blk = nullptr; v.max_tags = 0; v.enqueued = false;
-  for (int i = 0; i < 2; ++i)
-    if (!v.ev[i]) HIPCHK(c, hipEventCreate(&v.ev[i]));
-  auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t sz_e = up256(sizeof(rfid_tag_entry) * (size_t)max_tags * (size_t)c->B_plan), sz_i = up256(sizeof(int) * (size_t)c->B_plan);
-  hipError_t e = hipMalloc(&v.blk, 2 * sz_e + 3 * sz_i + 256);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    v.blk = nullptr;
-    return fail(c, RFID_ERR_HIP, "rfid_batch_plan_inventory: workspace allocation", e);
-  }
-  char *b = (char *)v.blk;
-  v.d_ent = (rfid_tag_entry *)b; b += sz_e; v.d_packed = (rfid_tag_entry *)b; b += sz_e;
-  v.d_counts = (int *)b; b += sz_i; v.d_over = (int *)b; b += sz_i; v.d_off = (int *)b; b += sz_i; v.d_head = (int *)b;
+  free_inventory(c);
+  const size_t sz_e = sizeof(rfid_tag_entry) * (size_t)max_tags * (size_t)c->B_plan, sz_i = sizeof(int) * (size_t)c->B_plan;
+  const int r = stage_alloc(c, v, "rfid_batch_plan_inventory: workspace allocation",
+                            {{(void **)&v.d_ent, sz_e}, {(void **)&v.d_packed, sz_e}, {(void **)&v.d_counts, sz_i}, {(void **)&v.d_over, sz_i},
+                             {(void **)&v.d_off, sz_i}, {(void **)&v.d_head, 2 * sizeof(int)}});
+  if (r) return r;
   v.max_tags = max_tags; v.slots = slots;
   return RFID_OK;
 }
@@ -1438,7 +1501,7 @@ int rfid_batch_inventory(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
   rfid_ctx::Inventory &v = c->inv;
   if (!c->B || !v.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_inventory: no plan with an inventory workspace (rfid_batch_plan_inventory)");
-  if (!c->stats_current) return fail(c, RFID_ERR_STATE, "rfid_batch_inventory: no pass with statistics yet");
+  if (c->current < rfid_ctx::CUR_STATS) return fail(c, RFID_ERR_STATE, "rfid_batch_inventory: no pass with statistics yet");
   HIPCHK(c, hipSetDevice(c->device));
   // the result set and the statistics c->d_* name are the last pass's; with two sets in flight its decoder and statistics
   // ran on the second stream: the main stream waits for them, and everything later on it waits for this
@@ -1449,22 +1512,19 @@ int rfid_batch_inventory(rfid_ctx *c) {
   InvPackArgs p;
   p.in = v.d_ent; p.counts = v.d_counts; p.overflow = v.d_over; p.n_streams = c->B; p.max_tags = v.max_tags;
   p.offsets = v.d_off; p.head = v.d_head; p.packed = v.d_packed;
-  HIPCHK(c, hipEventRecord(v.ev[0], c->stream));
-  // one wave per trace; sixteen when a trace can hold thousands of windows (as the statistics kernel)
-  const dim3 block(c->wmax > 2048 ? 64 * INV_MAX_WAVES : 64);
+  { int r = stage_record(c, v, 0); if (r) return r; }
+  const dim3 block = trace_block(c);
   if (v.slots <= 128) hipLaunchKernelGGL(inventory_kernel<128>, dim3((unsigned)c->B), block, 0, c->stream, a);
   else hipLaunchKernelGGL(inventory_kernel<1024>, dim3((unsigned)c->B), block, 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
-  const int scan_threads = (c->B >= INV_SCAN_THREADS) ? INV_SCAN_THREADS : ((c->B + 63) & ~63);
-  hipLaunchKernelGGL(inventory_offsets_kernel, dim3(1), dim3((unsigned)scan_threads), 0, c->stream, p);
+  hipLaunchKernelGGL(inventory_offsets_kernel, dim3(1), scan_block(c->B), 0, c->stream, p);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(inventory_pack_kernel, dim3((unsigned)c->B), dim3(64), 0, c->stream, p);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(v.ev[1], c->stream));
+  { int r = stage_record(c, v, 1); if (r) return r; }
   v.enqueued = true;
   v.n_streams = c->B;
-  c->inv_current = true;
-  c->trk_current = false;              // (the tracks behind an earlier inventory are not this one's)
+  mark_current(c, rfid_ctx::CUR_INVENTORY);     // (the tracks behind an earlier inventory are not this one's)
   return RFID_OK;
 }
 
@@ -1473,18 +1533,11 @@ int rfid_batch_get_inventory(rfid_ctx *c, rfid_tag_entry *entries, int64_t cap, 
   rfid_ctx::Inventory &v = c->inv;
   if (!v.blk || !v.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_inventory: no rfid_batch_inventory behind this plan");
   HIPCHK(c, hipSetDevice(c->device));
-  int head[2] = {0, 0};
-  HIPCHK(c, hipMemcpyAsync(head, v.d_head, sizeof(head), hipMemcpyDeviceToHost, c->stream));
   if (counts) HIPCHK(c, hipMemcpyAsync(counts, v.d_counts, sizeof(int) * (size_t)v.n_streams, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *n = head[0];
-  if (head[1] != INV_EMPTY) {
-    snprintf(c->err, sizeof(c->err), "rfid_batch_get_inventory: trace %d holds more than max_tags_per_trace = %d distinct frames", head[1], v.max_tags);
-    return RFID_ERR_CAPACITY;
-  }
-  if (head[0] > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_inventory: cap is smaller than the number of entries");
-  if (head[0] > 0) {
-    HIPCHK(c, hipMemcpyAsync(entries, v.d_packed, sizeof(rfid_tag_entry) * (size_t)head[0], hipMemcpyDeviceToHost, c->stream));
+  int n_entries = 0;
+  { int r = stage_fetch_head(c, "rfid_batch_get_inventory", nullptr, cap, n, &n_entries); if (r) return r; }
+  if (n_entries > 0) {
+    HIPCHK(c, hipMemcpyAsync(entries, v.d_packed, sizeof(rfid_tag_entry) * (size_t)n_entries, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return RFID_OK;
@@ -1492,11 +1545,7 @@ int rfid_batch_get_inventory(rfid_ctx *c, rfid_tag_entry *entries, int64_t cap, 
 
 int rfid_batch_inventory_ms(rfid_ctx *c, float *ms) {
   if (!c || !ms) return RFID_ERR_INVALID;
-  if (!c->inv.blk || !c->inv.enqueued) return RFID_ERR_STATE;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->inv.ev[1]));
-  HIPCHK(c, hipEventElapsedTime(ms, c->inv.ev[0], c->inv.ev[1]));
-  return RFID_OK;
+  return stage_ms(c, c->inv, ms);
 }
 
 // ---- tracks stage: every tag's reads in time order, behind the inventory of a pass (csrc/rfid_tracks.hpp) ----
@@ -1507,21 +1556,13 @@ int rfid_batch_plan_tracks(rfid_ctx *c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   rfid_ctx::Tracks &t = c->trk;
   free_tracks(c);
-  for (int i = 0; i < 2; ++i)
-    if (!t.ev[i]) HIPCHK(c, hipEventCreate(&t.ev[i]));
   // EPC windows are every other window: at most ceil(wmax / 2) reads per trace
   const int64_t cap = (int64_t)((c->wmax + 1) / 2) * c->B_plan;      // (< 2^31: wmax x B_plan is, rfid_batch_plan)
-  auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t sz_r = up256(sizeof(rfid_tag_read) * (size_t)cap), sz_o = up256(sizeof(int64_t) * ((size_t)c->inv.max_tags * (size_t)c->B_plan + 1)),
-               sz_i = up256(sizeof(int) * (size_t)c->B_plan);
-  hipError_t e = hipMalloc(&t.blk, sz_r + sz_o + sz_i + 256);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    t.blk = nullptr;
-    return fail(c, RFID_ERR_HIP, "rfid_batch_plan_tracks: workspace allocation", e);
-  }
-  char *b = (char *)t.blk;
-  t.d_reads = (rfid_tag_read *)b; b += sz_r; t.d_off = (int64_t *)b; b += sz_o; t.d_base = (int *)b; b += sz_i; t.d_head = (int *)b;
+  const int r = stage_alloc(c, t, "rfid_batch_plan_tracks: workspace allocation",
+                            {{(void **)&t.d_reads, sizeof(rfid_tag_read) * (size_t)cap},
+                             {(void **)&t.d_off, sizeof(int64_t) * ((size_t)c->inv.max_tags * (size_t)c->B_plan + 1)},
+                             {(void **)&t.d_base, sizeof(int) * (size_t)c->B_plan}, {(void **)&t.d_head, sizeof(int)}});
+  if (r) return r;
   t.cap = cap;
   return RFID_OK;
 }
@@ -1531,7 +1572,7 @@ int rfid_batch_tracks(rfid_ctx *c) {
   rfid_ctx::Inventory &v = c->inv;
   rfid_ctx::Tracks &t = c->trk;
   if (!c->B || !v.blk || !t.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_tracks: no plan with a tracks workspace (rfid_batch_plan_tracks)");
-  if (!v.enqueued || !c->inv_current || !c->stats_current) return fail(c, RFID_ERR_STATE, "rfid_batch_tracks: no rfid_batch_inventory behind the last pass");
+  if (!v.enqueued || c->current < rfid_ctx::CUR_INVENTORY) return fail(c, RFID_ERR_STATE, "rfid_batch_tracks: no rfid_batch_inventory behind the last pass");
   HIPCHK(c, hipSetDevice(c->device));
   // as rfid_batch_inventory: c->d_* name the last pass's result set; its tails ran on the second stream when two sets alternate
   { int rj = join_tails(c); if (rj) return rj; }
@@ -1543,23 +1584,21 @@ int rfid_batch_tracks(rfid_ctx *c) {
   a.res = c->d_res; a.wtab = c->d_wtab; a.wcount = c->d_wcount; a.stats = c->d_stats; a.wmax = c->wmax; a.n_streams = n;
   a.ent = v.d_ent; a.counts = v.d_counts; a.ent_off = v.d_off; a.max_tags = v.max_tags; a.slots = v.slots;
   a.base = t.d_base; a.out = t.d_reads; a.cap = t.cap; a.offsets = t.d_off;
-  HIPCHK(c, hipEventRecord(t.ev[0], c->stream));
-  const int scan_threads = (n >= INV_SCAN_THREADS) ? INV_SCAN_THREADS : ((n + 63) & ~63);
-  hipLaunchKernelGGL(tracks_offsets_kernel, dim3(1), dim3((unsigned)scan_threads), 0, c->stream, p);
+  { int r = stage_record(c, t, 0); if (r) return r; }
+  hipLaunchKernelGGL(tracks_offsets_kernel, dim3(1), scan_block(n), 0, c->stream, p);
   HIPCHK(c, hipGetLastError());
-  // one wave per trace; sixteen when a trace can hold thousands of windows (as the inventory kernel).  The small
-  // instantiation: a table of up to 128 slots and up to 64 entries per trace
+  // the small instantiation: a table of up to 128 slots and up to 64 entries per trace
   const bool small = v.slots <= 128 && v.max_tags <= 64;
-  const bool wide = c->wmax > 2048;
-  const dim3 grid((unsigned)n);
-  if (small && !wide) hipLaunchKernelGGL((tracks_kernel<128, 64, 1>), grid, dim3(64), 0, c->stream, a);
-  else if (!wide) hipLaunchKernelGGL((tracks_kernel<1024, 512, 1>), grid, dim3(64), 0, c->stream, a);
-  else if (small) hipLaunchKernelGGL((tracks_kernel<128, 64, INV_MAX_WAVES>), grid, dim3(64 * INV_MAX_WAVES), 0, c->stream, a);
-  else hipLaunchKernelGGL((tracks_kernel<1024, 512, INV_MAX_WAVES>), grid, dim3(64 * INV_MAX_WAVES), 0, c->stream, a);
+  const bool wide = wide_traces(c);
+  const dim3 grid((unsigned)n), block = trace_block(c);
+  if (small && !wide) hipLaunchKernelGGL((tracks_kernel<128, 64, 1>), grid, block, 0, c->stream, a);
+  else if (!wide) hipLaunchKernelGGL((tracks_kernel<1024, 512, 1>), grid, block, 0, c->stream, a);
+  else if (small) hipLaunchKernelGGL((tracks_kernel<128, 64, INV_MAX_WAVES>), grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((tracks_kernel<1024, 512, INV_MAX_WAVES>), grid, block, 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(t.ev[1], c->stream));
+  { int r = stage_record(c, t, 1); if (r) return r; }
   t.enqueued = true;
-  c->trk_current = true;
+  mark_current(c, rfid_ctx::CUR_TRACKS);
   return RFID_OK;
 }
 
@@ -1569,29 +1608,17 @@ int rfid_batch_get_tracks(rfid_ctx *c, rfid_tag_read *reads, int64_t cap, int64_
   rfid_ctx::Tracks &t = c->trk;
   if (!v.blk || !t.blk || !t.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_tracks: no rfid_batch_tracks behind this plan");
   HIPCHK(c, hipSetDevice(c->device));
-  int head[2] = {0, 0}, total = 0;
-  HIPCHK(c, hipMemcpyAsync(head, v.d_head, sizeof(head), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&total, t.d_head, sizeof(total), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *n = total;
-  if (head[1] != INV_EMPTY) {
-    snprintf(c->err, sizeof(c->err), "rfid_batch_get_tracks: trace %d holds more than max_tags_per_trace = %d distinct frames", head[1], v.max_tags);
-    return RFID_ERR_CAPACITY;
-  }
-  if (total > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_tracks: cap is smaller than the number of reads");
-  if (total > 0) HIPCHK(c, hipMemcpyAsync(reads, t.d_reads, sizeof(rfid_tag_read) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
-  if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, t.d_off, sizeof(int64_t) * ((size_t)head[0] + 1), hipMemcpyDeviceToHost, c->stream));
+  int n_entries = 0;
+  { int r = stage_fetch_head(c, "rfid_batch_get_tracks", t.d_head, cap, n, &n_entries); if (r) return r; }
+  if (*n > 0) HIPCHK(c, hipMemcpyAsync(reads, t.d_reads, sizeof(rfid_tag_read) * (size_t)*n, hipMemcpyDeviceToHost, c->stream));
+  if (offsets) HIPCHK(c, hipMemcpyAsync(offsets, t.d_off, sizeof(int64_t) * ((size_t)n_entries + 1), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
 }
 
 int rfid_batch_tracks_ms(rfid_ctx *c, float *ms) {
   if (!c || !ms) return RFID_ERR_INVALID;
-  if (!c->trk.blk || !c->trk.enqueued) return RFID_ERR_STATE;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->trk.ev[1]));
-  HIPCHK(c, hipEventElapsedTime(ms, c->trk.ev[0], c->trk.ev[1]));
-  return RFID_OK;
+  return stage_ms(c, c->trk, ms);
 }
 
 // ---- quality stage: per-read SNR and decision margin, behind the tracks of a pass (csrc/rfid_quality.hpp) ----
@@ -1602,21 +1629,13 @@ int rfid_batch_plan_quality(rfid_ctx *c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   rfid_ctx::Quality &q = c->qual;
   free_quality(c);
-  for (int i = 0; i < 2; ++i)
-    if (!q.ev[i]) HIPCHK(c, hipEventCreate(&q.ev[i]));
   // EPC windows are every other window: ceil(wmax / 2) rows per trace, as many packed records as the tracks have reads
   const int rows = (c->wmax + 1) / 2;
-  auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t sz_t = up256(sizeof(rfid_read_quality) * (size_t)rows * (size_t)c->B_plan), sz_p = up256(sizeof(rfid_read_quality) * (size_t)c->trk.cap),
-               sz_i = up256(sizeof(int) * (size_t)c->B_plan);
-  hipError_t e = hipMalloc(&q.blk, sz_t + sz_p + sz_i);
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
-    q.blk = nullptr;
-    return fail(c, RFID_ERR_HIP, "rfid_batch_plan_quality: workspace allocation", e);
-  }
-  char *b = (char *)q.blk;
-  q.d_table = (rfid_read_quality *)b; b += sz_t; q.d_packed = (rfid_read_quality *)b; b += sz_p; q.d_nrows = (int *)b;
+  const int r = stage_alloc(c, q, "rfid_batch_plan_quality: workspace allocation",
+                            {{(void **)&q.d_table, sizeof(rfid_read_quality) * (size_t)rows * (size_t)c->B_plan},
+                             {(void **)&q.d_packed, sizeof(rfid_read_quality) * (size_t)c->trk.cap},
+                             {(void **)&q.d_nrows, sizeof(int) * (size_t)c->B_plan}});
+  if (r) return r;
   q.rows = rows;
   return RFID_OK;
 }
@@ -1626,7 +1645,7 @@ int rfid_batch_quality(rfid_ctx *c) {
   rfid_ctx::Tracks &t = c->trk;
   rfid_ctx::Quality &q = c->qual;
   if (!c->B || !c->inv.blk || !t.blk || !q.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_quality: no plan with a quality workspace (rfid_batch_plan_quality)");
-  if (!t.enqueued || !c->trk_current || !c->inv_current || !c->stats_current) return fail(c, RFID_ERR_STATE, "rfid_batch_quality: no rfid_batch_tracks behind the last pass");
+  if (!t.enqueued || c->current < rfid_ctx::CUR_TRACKS) return fail(c, RFID_ERR_STATE, "rfid_batch_quality: no rfid_batch_tracks behind the last pass");
   HIPCHK(c, hipSetDevice(c->device));
   // as rfid_batch_inventory: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
   // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
@@ -1637,7 +1656,7 @@ int rfid_batch_quality(rfid_ctx *c) {
   a.wmax = c->wmax; a.n_streams = n; a.rows = q.rows; a.table = q.d_table; a.nrows = q.d_nrows;
   QualGatherArgs g;
   g.reads = t.d_reads; g.head = t.d_head; g.cap = t.cap; g.table = q.d_table; g.n_streams = n; g.rows = q.rows; g.out = q.d_packed;
-  HIPCHK(c, hipEventRecord(q.ev[0], c->stream));
+  { int r = stage_record(c, q, 0); if (r) return r; }
   // single-wave workgroups, each walking packs of eight rows (12.6 KB of LDS each)
   const int64_t items = (int64_t)n * ((q.rows + QUAL_PACK - 1) / QUAL_PACK);
   const int64_t most = (int64_t)c->n_cus * QUAL_WGS_PER_CU;
@@ -1649,7 +1668,7 @@ int rfid_batch_quality(rfid_ctx *c) {
   if (gblocks < 1) gblocks = 1;
   hipLaunchKernelGGL(quality_gather_kernel, dim3((unsigned)gblocks), dim3(QUAL_GATHER_THREADS), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(q.ev[1], c->stream));
+  { int r = stage_record(c, q, 1); if (r) return r; }
   // the long-stream front end hands this pass's matched-filter buffer to the pass after next, whose first launch runs on the
   // second stream as soon as the buffer's event has come: the event is recorded again, behind the launches that read the buffer
   if (c->y_recorded[c->y_idx]) HIPCHK(c, hipEventRecord(c->ev_y_free[c->y_idx], c->stream));
@@ -1665,18 +1684,10 @@ int rfid_batch_get_quality(rfid_ctx *c, rfid_read_quality *out, int64_t cap, int
   rfid_ctx::Quality &q = c->qual;
   if (!v.blk || !t.blk || !q.blk || !q.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_quality: no rfid_batch_quality behind this plan");
   HIPCHK(c, hipSetDevice(c->device));
-  int head[2] = {0, 0}, total = 0;
-  HIPCHK(c, hipMemcpyAsync(head, v.d_head, sizeof(head), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&total, t.d_head, sizeof(total), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *n = total;
-  if (head[1] != INV_EMPTY) {
-    snprintf(c->err, sizeof(c->err), "rfid_batch_get_quality: trace %d holds more than max_tags_per_trace = %d distinct frames", head[1], v.max_tags);
-    return RFID_ERR_CAPACITY;
-  }
-  if (total > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_quality: cap is smaller than the number of reads");
-  if (total > 0) {
-    HIPCHK(c, hipMemcpyAsync(out, q.d_packed, sizeof(rfid_read_quality) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+  int n_entries = 0;
+  { int r = stage_fetch_head(c, "rfid_batch_get_quality", t.d_head, cap, n, &n_entries); if (r) return r; }
+  if (*n > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, q.d_packed, sizeof(rfid_read_quality) * (size_t)*n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return RFID_OK;
@@ -1703,11 +1714,7 @@ int rfid_batch_get_window_quality(rfid_ctx *c, int stream, rfid_read_quality *ou
 
 int rfid_batch_quality_ms(rfid_ctx *c, float *ms) {
   if (!c || !ms) return RFID_ERR_INVALID;
-  if (!c->qual.blk || !c->qual.enqueued) return RFID_ERR_STATE;
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipEventSynchronize(c->qual.ev[1]));
-  HIPCHK(c, hipEventElapsedTime(ms, c->qual.ev[0], c->qual.ev[1]));
-  return RFID_OK;
+  return stage_ms(c, c->qual, ms);
 }
 
 // mf -> gate -> decode -> stats.  The matched filter (HBM-bound) and the gate scan (bound by the

@@ -26,6 +26,11 @@
 // rule: one that claims, one in which every read finds its frame.
 // Counts, last read and the largest |h|^2 are accumulated by the reads that resolve in a round and thrown away if the
 // round turns out not to be the last; the strongest read's seq needs the maximum first and takes one more walk.
+//
+// Also here, because the tracks and the quality stage (rfid_tracks.hpp, rfid_quality.hpp, which include this file) decide
+// the same things: stage_windows (which windows of a trace count in a pass), stage_fetch (how a result record is read and
+// which records are reads), inv_hash / inv_walk (how a frame is looked up in the table) and scan_share / scan_partials
+// (the one-workgroup offsets scan).  How a table is BUILT is not shared: reads claim slots here, entries in the tracks.
 #pragma once
 #include "rfid_kernels.hpp"
 
@@ -47,15 +52,26 @@ constexpr int INV_EMPTY = 0x7fffffff;
 constexpr int INV_MAX_WAVES = 16;
 constexpr int INV_UNROLL = 4;       // 64-window batches of loads in flight per wave
 
-struct InvRead {
+// the windows of trace s that count in this pass: those the gate opened, before the TERMINATED cut-off (shared by the
+// inventory, tracks and quality kernels)
+RFID_DEVICE int stage_windows(const int *wcount, const rfid_stream_stats *stats, int wmax, int s) {
+  int nw = wcount[s];
+  const int used = stats[s].n_windows_used;
+  if (used < nw) nw = used;
+  if (nw > wmax) nw = wmax;
+  return (nw < 0) ? 0 : nw;
+}
+
+// one result record as the stages read it (shared by the inventory and the tracks kernels)
+struct StageRead {
   uint32_t f[4];
-  int norm;      // int pattern of h_re*h_re + h_im*h_im (non-negative: ordered like the float)
-  bool on;       // an EPC window with a verified CRC
+  int h_re, h_im, T, index;   // (bit patterns)
+  bool on;                    // an EPC window with a verified CRC
 };
 
-RFID_DEVICE InvRead inv_fetch(const rfid_decode_result *rs, int k, int k_end) {
-  InvRead q;
-  q.f[0] = q.f[1] = q.f[2] = q.f[3] = 0u; q.norm = 0; q.on = false;
+RFID_DEVICE StageRead stage_fetch(const rfid_decode_result *rs, int k, int k_end) {
+  StageRead q;
+  q.f[0] = q.f[1] = q.f[2] = q.f[3] = 0u; q.h_re = q.h_im = q.T = q.index = 0; q.on = false;
   if (k < k_end) {
     // the whole 48-byte record in three 16-byte loads, none of them waiting for another (rows are 16-byte aligned)
     static_assert(sizeof(rfid_decode_result) == 48, "rfid_decode_result is read as 12 words");
@@ -67,12 +83,17 @@ RFID_DEVICE InvRead inv_fetch(const rfid_decode_result *rs, int k, int k_end) {
     if (w[0] == RFID_DECODE_EPC && w[10] == 1) {
       q.on = true;
       q.f[0] = (uint32_t)w[5]; q.f[1] = (uint32_t)w[6]; q.f[2] = (uint32_t)w[7]; q.f[3] = (uint32_t)w[8];
-      const float re = wv::u2f((uint32_t)w[2]), im = wv::u2f((uint32_t)w[3]);
-      const float n = re * re + im * im;            // (binary32, two products and one sum: -ffp-contract=off)
-      q.norm = (int)(wv::f2u(n) & 0x7fffffffu);
+      q.index = w[1]; q.h_re = w[2]; q.h_im = w[3]; q.T = w[4];
     }
   }
   return q;
+}
+
+// int pattern of h_re*h_re + h_im*h_im (non-negative: ordered like the float)
+RFID_DEVICE int inv_norm(const StageRead &q) {
+  const float re = wv::u2f((uint32_t)q.h_re), im = wv::u2f((uint32_t)q.h_im);
+  const float n = re * re + im * im;              // (binary32, two products and one sum: -ffp-contract=off)
+  return (int)(wv::f2u(n) & 0x7fffffffu);
 }
 
 RFID_DEVICE void inv_hash(const uint32_t (&f)[4], int mask, int &h0, int &step) {
@@ -84,15 +105,14 @@ RFID_DEVICE void inv_hash(const uint32_t (&f)[4], int mask, int &h0, int &step) 
 
 // the slot among probes 0..last whose settled owner holds this frame: its index, -1 when an empty slot comes first
 // (`empty_slot` names it), -2 when every probe is owned by another frame
-template <int SLOTS>
-RFID_DEVICE int inv_walk(const InvRead &q, const int *settled, const uint32_t *key, int mask, int last, int &empty_slot) {
+RFID_DEVICE int inv_walk(const uint32_t (&f)[4], const int *settled, const uint32_t *key, int mask, int last, int &empty_slot) {
   int h0, step;
-  inv_hash(q.f, mask, h0, step);
+  inv_hash(f, mask, h0, step);
   for (int i = 0; i <= last; ++i) {
     const int slot = (h0 + i * step) & mask;
     if (settled[slot] == INV_EMPTY) { empty_slot = slot; return -1; }
     const uint32_t *kk = key + 4 * slot;
-    if (kk[0] == q.f[0] && kk[1] == q.f[1] && kk[2] == q.f[2] && kk[3] == q.f[3]) return slot;
+    if (kk[0] == f[0] && kk[1] == f[1] && kk[2] == f[2] && kk[3] == f[3]) return slot;
   }
   return -2;
 }
@@ -119,30 +139,25 @@ RFID_KERNEL(64 * INV_MAX_WAVES) void inventory_kernel(InvArgs a) {
   }
   if (tid == 0) { sh_again = 0; sh_n = 0; }
   wv::block_sync();
-  int nw = a.wcount[s];
-  {
-    const int used = a.stats[s].n_windows_used;
-    if (used < nw) nw = used;
-    if (nw > a.wmax) nw = a.wmax;
-  }
+  const int nw = stage_windows(a.wcount, a.stats, a.wmax, s);
   const rfid_decode_result *rs = a.res + (int64_t)s * a.wmax;
   bool full = false;     // more distinct frames than slots
   for (int r = 0;; ++r) {
     const int deepest = (r < S) ? r : (S - 1);
     for (int base = 0; base < nw; base += nthr * INV_UNROLL) {
-      InvRead q[INV_UNROLL];
+      StageRead q[INV_UNROLL];
 #pragma unroll
-      for (int u = 0; u < INV_UNROLL; ++u) q[u] = inv_fetch(rs, base + u * nthr + tid, nw);
+      for (int u = 0; u < INV_UNROLL; ++u) q[u] = stage_fetch(rs, base + u * nthr + tid, nw);
 #pragma unroll
       for (int u = 0; u < INV_UNROLL; ++u) {
         if (!q[u].on) continue;
         const int k = base + u * nthr + tid;
         int empty_slot = 0;
-        const int slot = inv_walk<SLOTS>(q[u], settled, key, mask, deepest, empty_slot);
+        const int slot = inv_walk(q[u].f, settled, key, mask, deepest, empty_slot);
         if (slot >= 0) {
           wv::atomic_add(&cnt[slot], 1);
           wv::atomic_max(&last[slot], k);
-          wv::atomic_max(&bestn[slot], q[u].norm);
+          wv::atomic_max(&bestn[slot], inv_norm(q[u]));
         } else {
           if (slot == -1) wv::atomic_min(&owner[empty_slot], k);
           sh_again = 1;     // (every writer stores the same value)
@@ -177,15 +192,15 @@ RFID_KERNEL(64 * INV_MAX_WAVES) void inventory_kernel(InvArgs a) {
   }
   // the strongest read of every frame: the earliest among those that hold the maximum
   for (int base = 0; base < nw; base += nthr * INV_UNROLL) {
-    InvRead q[INV_UNROLL];
+    StageRead q[INV_UNROLL];
 #pragma unroll
-    for (int u = 0; u < INV_UNROLL; ++u) q[u] = inv_fetch(rs, base + u * nthr + tid, nw);
+    for (int u = 0; u < INV_UNROLL; ++u) q[u] = stage_fetch(rs, base + u * nthr + tid, nw);
 #pragma unroll
     for (int u = 0; u < INV_UNROLL; ++u) {
       if (!q[u].on) continue;
       int empty_slot = 0;
-      const int slot = inv_walk<SLOTS>(q[u], settled, key, mask, S - 1, empty_slot);
-      if (slot >= 0 && q[u].norm == bestn[slot]) wv::atomic_min(&bests[slot], base + u * nthr + tid);
+      const int slot = inv_walk(q[u].f, settled, key, mask, S - 1, empty_slot);
+      if (slot >= 0 && inv_norm(q[u]) == bestn[slot]) wv::atomic_min(&bests[slot], base + u * nthr + tid);
     }
   }
   wv::block_sync();
@@ -219,31 +234,51 @@ struct InvPackArgs {
   rfid_tag_entry *packed;       // [sum of counts]
 };
 
+// The one-workgroup offsets scan over per-trace amounts (inventory_offsets_kernel, tracks_offsets_kernel): every thread
+// sums the amounts of a contiguous share of the traces, thread 0 scans the partial sums serially (INV_SCAN_THREADS at
+// most), every thread then walks its share again from the base it is handed.
 constexpr int INV_SCAN_THREADS = 1024;
+
+struct ScanShare { int b0, b1; };     // this thread's traces: [b0, b1)
+RFID_DEVICE ScanShare scan_share(int n_streams, int tid, int nthr) {
+  const int per = (n_streams + nthr - 1) / nthr;
+  ScanShare sh;
+  sh.b0 = tid * per;
+  sh.b1 = (sh.b0 + per < n_streams) ? (sh.b0 + per) : n_streams;
+  return sh;
+}
+
+// `sum`: what this thread's share holds.  -> what the shares of the threads before it hold; `total` (thread 0 only):
+// what all hold.  Two workgroup barriers: what the threads wrote to LDS before the call is visible behind it.
+RFID_DEVICE int scan_partials(int *part, int tid, int nthr, int sum, int &total) {
+  part[tid] = sum;
+  wv::block_sync();
+  if (tid == 0) {
+    int run = 0;
+    for (int t = 0; t < nthr; ++t) { const int v = part[t]; part[t] = run; run += v; }
+    total = run;
+  }
+  wv::block_sync();
+  return part[tid];
+}
+
 RFID_KERNEL(INV_SCAN_THREADS) void inventory_offsets_kernel(InvPackArgs a) {
   RFID_SHARED int part[INV_SCAN_THREADS];
   RFID_SHARED int sh_over;
   const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
   if (tid == 0) sh_over = INV_EMPTY;
   wv::block_sync();
-  const int per = (a.n_streams + nthr - 1) / nthr;
-  const int b0 = tid * per, b1 = (b0 + per < a.n_streams) ? (b0 + per) : a.n_streams;
+  const ScanShare sh = scan_share(a.n_streams, tid, nthr);
   int sum = 0, over = INV_EMPTY;
-  for (int b = b0; b < b1; ++b) {
+  for (int b = sh.b0; b < sh.b1; ++b) {
     sum += a.counts[b];
     if (a.overflow[b] && b < over) over = b;
   }
-  part[tid] = sum;
   if (over != INV_EMPTY) wv::atomic_min(&sh_over, over);
-  wv::block_sync();
-  if (tid == 0) {
-    int run = 0;
-    for (int t = 0; t < nthr; ++t) { const int v = part[t]; part[t] = run; run += v; }
-    a.head[0] = run; a.head[1] = sh_over;
-  }
-  wv::block_sync();
-  int run = part[tid];
-  for (int b = b0; b < b1; ++b) { a.offsets[b] = run; run += a.counts[b]; }
+  int total = 0;
+  int run = scan_partials(part, tid, nthr, sum, total);
+  if (tid == 0) { a.head[0] = total; a.head[1] = sh_over; }
+  for (int b = sh.b0; b < sh.b1; ++b) { a.offsets[b] = run; run += a.counts[b]; }
 }
 
 RFID_KERNEL(64) void inventory_pack_kernel(InvPackArgs a) {

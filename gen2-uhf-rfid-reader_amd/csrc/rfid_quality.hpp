@@ -17,8 +17,9 @@
 //           banks) and 24 lanes -- one per (window, sum) -- walk a row each, from 0.0f in the order of j: 128 dependent
 //           additions for eight windows, against the 20 x 256 of the decoder's half-period search for three.
 //   store   the eight 32-byte records are put together in LDS and leave as one 256-byte row of the table, one word per lane.
-// Rows behind a trace's cut-off are zeroed, so the table's bytes repeat from pass to pass.  Single-wave workgroups, nothing
-// shared between them, no atomics: nothing depends on the order in which they run.
+// The cut-off is the inventory's and the tracks' (stage_windows).  Rows behind a trace's cut-off are zeroed, so the table's
+// bytes repeat from pass to pass.  Single-wave workgroups, nothing shared between them, no atomics: nothing depends on the
+// order in which they run.
 // quality_gather_kernel then copies the records of the CRC-verified reads into one array aligned with the tracks.
 // Only primitives both device environments offer.
 #pragma once
@@ -64,13 +65,7 @@ RFID_KERNEL(64) void quality_kernel(QualArgs a) {
   for (int64_t it = (int64_t)blockIdx.x; it < n_items; it += (int64_t)gridDim.x) {
     const int s = (int)(it / packs_per);
     const int r0 = (int)(it - (int64_t)s * packs_per) * QUAL_PACK;
-    int nw = a.wcount[s];
-    {
-      const int used = a.stats[s].n_windows_used;
-      if (used < nw) nw = used;
-      if (nw > a.wmax) nw = a.wmax;
-      if (nw < 0) nw = 0;
-    }
+    const int nw = stage_windows(a.wcount, a.stats, a.wmax, s);
     const int nrows = nw >> 1;             // seq = 2 row + 1 < nw
     if (r0 == 0 && lane == 0) a.nrows[s] = nrows;
     const int my_row = r0 + (lane >> 3);   // (the record this lane stores a word of)

@@ -6,8 +6,9 @@
 // A read's place is  base(stream) + reads of the trace's earlier entries + earlier reads of the same frame  -- a
 // function of the input alone.  A stable counting scatter finds it in linear time, one workgroup per trace:
 //   table   the trace's entries (<= 512 distinct frames, listed by the inventory in the order of their first reads)
-//           are put into a hash table in LDS, the ENTRY INDEX as the owner of a slot.  Probe sequence and hash are the
-//           inventory's (inv_hash); so is the round scheme that needs no compare-and-swap: in a round every entry not
+//           are put into a hash table in LDS, the ENTRY INDEX as the owner of a slot.  Probe sequence, hash and the
+//           walk that finds a frame are the inventory's (inv_hash, inv_walk); the round scheme is of its kind and needs no
+//           compare-and-swap either: in a round every entry not
 //           yet placed walks its probes over settled[] (the owners as they stood when the round began) to the first
 //           empty slot and asks for it with atomic_min; behind a barrier the winner settles with its key, the others
 //           move one probe on.  The lowest index among those that ask always wins: at most as many rounds as entries,
@@ -19,13 +20,14 @@
 //   pass 2  every wave walks its range in batches of 64 windows, in order.  Inside a batch the lanes that hold the same
 //           entry are found with ballot; a lane's rank is the number of lower lanes among them, the lowest of them
 //           moves the cursor on by their number (an LDS atomic whose old value readlane hands to the others).
+// Which windows count (stage_windows) and how a result record is read (stage_fetch) are the inventory's too.
 // Only primitives both device environments offer, workgroup barriers only, nothing shared between workgroups.
 #pragma once
 #include "rfid_inventory.hpp"
 
 namespace rfidk {
 
-// ---- bases: the reads of the traces before each trace (one workgroup; inventory_offsets_kernel is the model) --------
+// ---- bases: the reads of the traces before each trace (one workgroup; scan_share / scan_partials as inventory_offsets_kernel) --------
 struct TrkScanArgs {
   const rfid_tag_entry *ent;    // [n_streams][max_tags]: the inventory's rows
   const int *counts;            // [n_streams]: entries per trace (0 when the trace overflowed)
@@ -39,25 +41,20 @@ struct TrkScanArgs {
 RFID_KERNEL(INV_SCAN_THREADS) void tracks_offsets_kernel(TrkScanArgs a) {
   RFID_SHARED int part[INV_SCAN_THREADS];
   const int tid = (int)threadIdx.x, nthr = (int)blockDim.x;
-  const int per = (a.n_streams + nthr - 1) / nthr;
-  const int b0 = tid * per, b1 = (b0 + per < a.n_streams) ? (b0 + per) : a.n_streams;
+  const ScanShare sh = scan_share(a.n_streams, tid, nthr);
   int sum = 0;
-  for (int b = b0; b < b1; ++b) {
+  for (int b = sh.b0; b < sh.b1; ++b) {
     const rfid_tag_entry *e = a.ent + (int64_t)b * a.max_tags;
     const int n = a.counts[b];
     for (int i = 0; i < n; ++i) sum += e[i].reads;
   }
-  part[tid] = sum;
-  wv::block_sync();
+  int total = 0;
+  int run = scan_partials(part, tid, nthr, sum, total);
   if (tid == 0) {
-    int run = 0;
-    for (int t = 0; t < nthr; ++t) { const int v = part[t]; part[t] = run; run += v; }
-    a.head[0] = run;
-    a.offsets[a.inv_head[0]] = run;
+    a.head[0] = total;
+    a.offsets[a.inv_head[0]] = total;
   }
-  wv::block_sync();
-  int run = part[tid];
-  for (int b = b0; b < b1; ++b) {
+  for (int b = sh.b0; b < sh.b1; ++b) {
     a.base[b] = run;
     const rfid_tag_entry *e = a.ent + (int64_t)b * a.max_tags;
     const int n = a.counts[b];
@@ -83,43 +80,12 @@ struct TrkArgs {
   int64_t *offsets;                 // [entries in all + 1], aligned with the packed entries
 };
 
-struct TrkRead {
-  uint32_t f[4];
-  int h_re, h_im, T, index;   // (bit patterns)
-  bool on;                    // an EPC window with a verified CRC
-};
-
-RFID_DEVICE TrkRead trk_fetch(const rfid_decode_result *rs, int k, int k_end) {
-  TrkRead q;
-  q.f[0] = q.f[1] = q.f[2] = q.f[3] = 0u; q.h_re = q.h_im = q.T = q.index = 0; q.on = false;
-  if (k < k_end) {
-    // as inv_fetch: the 48-byte record in three 16-byte loads, none of them waiting for another
-    const int *p = reinterpret_cast<const int *>(rs + k);
-    int w[12];
-    wv::load4_i32(p, w[0], w[1], w[2], w[3]);        // type, index, h_re, h_im
-    wv::load4_i32(p + 4, w[4], w[5], w[6], w[7]);    // T, bits[0..2]
-    wv::load4_i32(p + 8, w[8], w[9], w[10], w[11]);  // bits[3], n_bits, crc_ok, tag_id
-    if (w[0] == RFID_DECODE_EPC && w[10] == 1) {
-      q.on = true;
-      q.f[0] = (uint32_t)w[5]; q.f[1] = (uint32_t)w[6]; q.f[2] = (uint32_t)w[7]; q.f[3] = (uint32_t)w[8];
-      q.index = w[1]; q.h_re = w[2]; q.h_im = w[3]; q.T = w[4];
-    }
-  }
-  return q;
-}
-
-// the entry that holds this frame, -1 when none does (not reached behind an inventory of the same results)
+// the entry that holds this frame: all S probes of inv_walk, then the slot's owner.  -1 when none does (not reached
+// behind an inventory of the same results)
 RFID_DEVICE int trk_find(const uint32_t (&f)[4], const int *settled, const uint32_t *key, int S) {
-  int h0, step;
-  inv_hash(f, S - 1, h0, step);
-  for (int i = 0; i < S; ++i) {
-    const int slot = (h0 + i * step) & (S - 1);
-    const int o = settled[slot];
-    if (o == INV_EMPTY) return -1;
-    const uint32_t *kk = key + 4 * slot;
-    if (kk[0] == f[0] && kk[1] == f[1] && kk[2] == f[2] && kk[3] == f[3]) return o;
-  }
-  return -1;
+  int empty_slot = 0;
+  const int slot = inv_walk(f, settled, key, S - 1, S - 1, empty_slot);
+  return (slot >= 0) ? settled[slot] : -1;
 }
 
 // One workgroup per trace: WAVES = 1, or 16 when a trace can hold thousands of windows (the host picks, as for
@@ -182,12 +148,7 @@ RFID_KERNEL(64 * WAVES) void tracks_kernel(TrkArgs a) {
     if (tid == 0) sh_again = 0;
     wv::block_sync();
   }
-  int nw = a.wcount[s];
-  {
-    const int used = a.stats[s].n_windows_used;
-    if (used < nw) nw = used;
-    if (nw > a.wmax) nw = a.wmax;
-  }
+  const int nw = stage_windows(a.wcount, a.stats, a.wmax, s);
   const rfid_decode_result *rs = a.res + (int64_t)s * a.wmax;
   const rfid_window *wt = a.wtab + (int64_t)s * a.wmax;
   // this wave's windows: a contiguous range, a multiple of 64 long
@@ -197,9 +158,9 @@ RFID_KERNEL(64 * WAVES) void tracks_kernel(TrkArgs a) {
   // ---- pass 1 ----
   if (WAVES > 1) {
     for (int base = k0; base < k1; base += 64 * INV_UNROLL) {
-      TrkRead q[INV_UNROLL];
+      StageRead q[INV_UNROLL];
 #pragma unroll
-      for (int u = 0; u < INV_UNROLL; ++u) q[u] = trk_fetch(rs, base + u * 64 + lane, k1);
+      for (int u = 0; u < INV_UNROLL; ++u) q[u] = stage_fetch(rs, base + u * 64 + lane, k1);
 #pragma unroll
       for (int u = 0; u < INV_UNROLL; ++u) {
         if (!q[u].on) continue;
@@ -236,9 +197,9 @@ RFID_KERNEL(64 * WAVES) void tracks_kernel(TrkArgs a) {
   wv::block_sync();
   // ---- pass 2 ----
   for (int base = k0; base < k1; base += 64 * INV_UNROLL) {
-    TrkRead q[INV_UNROLL];
+    StageRead q[INV_UNROLL];
 #pragma unroll
-    for (int u = 0; u < INV_UNROLL; ++u) q[u] = trk_fetch(rs, base + u * 64 + lane, k1);
+    for (int u = 0; u < INV_UNROLL; ++u) q[u] = stage_fetch(rs, base + u * 64 + lane, k1);
 #pragma unroll
     for (int u = 0; u < INV_UNROLL; ++u) {
       const int k = base + u * 64 + lane;

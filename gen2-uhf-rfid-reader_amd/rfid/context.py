@@ -292,6 +292,24 @@ class Context:
                                                        s.ctypes.data if s is not None else None, k, C.byref(n)))
         return w, r, s
 
+    def _sized_fetch(self, get, dtype, head=(), tail=(), extra: int = 0) -> np.ndarray:
+        """The two calls every stage's fetch makes: `get` without an array tells the size (RFID_ERR_CAPACITY where there is
+        something to fetch), then an array of that size plus `extra` records is filled.  head / tail: get's arguments before
+        and behind (array, cap, n)."""
+        n = C.c_int64(0)
+        out = np.zeros(0, dtype=dtype)
+        st = get(self._h, *head, None, 0, C.byref(n), *tail)
+        if st in (capi.OK, capi.ERR_CAPACITY) and n.value + extra > 0:   # (the size is known now; a trace that overflowed fails again below)
+            out = np.zeros(n.value + extra, dtype=dtype)
+            st = get(self._h, *head, out.ctypes.data, len(out), C.byref(n), *tail)
+        self._chk(st)
+        return out
+
+    def _stage_ms(self, get_ms) -> float:
+        ms = C.c_float(0.0)
+        self._chk(get_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
     def batch_plan_inventory(self, max_tags: int) -> None:
         """Reserves the inventory workspace of the current plan: up to max_tags distinct EPC frames per trace."""
         self._chk(self._lib.rfid_batch_plan_inventory(self._h, int(max_tags)))
@@ -302,14 +320,8 @@ class Context:
 
     def batch_inventory_fetch(self):
         """-> (entries, per-trace counts) of the last batch_inventory_enqueue (synchronises)."""
-        n = C.c_int64(0)
         counts = np.zeros(max(self._active, 1), dtype=np.int32)
-        ent = np.zeros(0, dtype=capi.TAG_ENTRY_DTYPE)
-        st = self._lib.rfid_batch_get_inventory(self._h, None, 0, C.byref(n), counts.ctypes.data)
-        if st == capi.ERR_CAPACITY and n.value > 0:      # (the size is known now; a trace that overflowed fails again below)
-            ent = np.zeros(n.value, dtype=capi.TAG_ENTRY_DTYPE)
-            st = self._lib.rfid_batch_get_inventory(self._h, ent.ctypes.data, len(ent), C.byref(n), counts.ctypes.data)
-        self._chk(st)
+        ent = self._sized_fetch(self._lib.rfid_batch_get_inventory, capi.TAG_ENTRY_DTYPE, tail=(counts.ctypes.data,))
         return ent, counts[: self._active]
 
     def batch_inventory(self):
@@ -319,9 +331,7 @@ class Context:
         return self.batch_inventory_fetch()
 
     def batch_inventory_ms(self) -> float:
-        ms = C.c_float(0.0)
-        self._chk(self._lib.rfid_batch_inventory_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._stage_ms(self._lib.rfid_batch_inventory_ms)
 
     def batch_plan_tracks(self) -> None:
         """Reserves the tracks workspace of the current plan (behind batch_plan_inventory; a new plan or a new
@@ -336,20 +346,12 @@ class Context:
         """-> (reads, offsets) of the last batch_tracks_enqueue (synchronises): capi.TAG_READ_DTYPE ordered by
         (stream, entry, seq); int64 offsets aligned with the entries of batch_inventory_fetch -- reads
         offsets[i]:offsets[i + 1] are entry i's."""
-        n = C.c_int64(0)
-        reads = np.zeros(0, dtype=capi.TAG_READ_DTYPE)
-        st = self._lib.rfid_batch_get_tracks(self._h, None, 0, C.byref(n), None)
-        if st == capi.ERR_CAPACITY and n.value > 0:      # (the size is known now; a trace that overflowed fails again below)
-            reads = np.zeros(n.value, dtype=capi.TAG_READ_DTYPE)
-        if st in (capi.OK, capi.ERR_CAPACITY):
-            ne = C.c_int64(0)
-            si = self._lib.rfid_batch_get_inventory(self._h, None, 0, C.byref(ne), None)
-            if si not in (capi.OK, capi.ERR_CAPACITY):
-                self._chk(si)
-            offsets = np.zeros(ne.value + 1, dtype=np.int64)
-            st = self._lib.rfid_batch_get_tracks(self._h, reads.ctypes.data if len(reads) else None, len(reads), C.byref(n),
-                                                 offsets.ctypes.data)
-        self._chk(st)
+        ne = C.c_int64(0)      # the entries the offsets are aligned with
+        si = self._lib.rfid_batch_get_inventory(self._h, None, 0, C.byref(ne), None)
+        if si not in (capi.OK, capi.ERR_CAPACITY, capi.ERR_STATE):     # (no inventory: no tracks either, said below)
+            self._chk(si)
+        offsets = np.zeros(ne.value + 1, dtype=np.int64)
+        reads = self._sized_fetch(self._lib.rfid_batch_get_tracks, capi.TAG_READ_DTYPE, tail=(offsets.ctypes.data,))
         return reads, offsets
 
     def batch_tracks(self):
@@ -359,9 +361,7 @@ class Context:
         return self.batch_tracks_fetch()
 
     def batch_tracks_ms(self) -> float:
-        ms = C.c_float(0.0)
-        self._chk(self._lib.rfid_batch_tracks_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._stage_ms(self._lib.rfid_batch_tracks_ms)
 
     def batch_plan_quality(self) -> None:
         """Reserves the quality workspace of the current plan (behind batch_plan_tracks; a new plan, batch_plan_inventory or
@@ -375,14 +375,7 @@ class Context:
     def batch_quality_fetch(self) -> np.ndarray:
         """-> capi.QUALITY_DTYPE records of the last batch_quality_enqueue (synchronises), one per CRC-verified read:
         record i belongs to reads[i] of batch_tracks_fetch."""
-        n = C.c_int64(0)
-        q = np.zeros(0, dtype=capi.QUALITY_DTYPE)
-        st = self._lib.rfid_batch_get_quality(self._h, None, 0, C.byref(n))
-        if st == capi.ERR_CAPACITY and n.value > 0:      # (the size is known now; a trace that overflowed fails again below)
-            q = np.zeros(n.value, dtype=capi.QUALITY_DTYPE)
-            st = self._lib.rfid_batch_get_quality(self._h, q.ctypes.data, len(q), C.byref(n))
-        self._chk(st)
-        return q
+        return self._sized_fetch(self._lib.rfid_batch_get_quality, capi.QUALITY_DTYPE)
 
     def batch_quality(self) -> np.ndarray:
         """SNR and decision margin of every read of the last pass, built on the device behind batch_tracks():
@@ -394,19 +387,11 @@ class Context:
         """Debug tap (synchronises): the records of EVERY EPC window of one trace before the cut-off, in seq order, failed
         ones included (n_windows_used // 2 of them), of the last batch_quality_enqueue.  extra > 0: up to that many of the
         table's rows behind them as well (zeroed by the stage)."""
-        n = C.c_int64(0)
-        st = self._lib.rfid_batch_get_window_quality(self._h, int(stream), None, 0, C.byref(n))
-        if st not in (capi.OK, capi.ERR_CAPACITY):
-            self._chk(st)
-        q = np.zeros(n.value + max(int(extra), 0), dtype=capi.QUALITY_DTYPE)
-        if len(q):
-            self._chk(self._lib.rfid_batch_get_window_quality(self._h, int(stream), q.ctypes.data, len(q), C.byref(n)))
-        return q
+        return self._sized_fetch(self._lib.rfid_batch_get_window_quality, capi.QUALITY_DTYPE, head=(int(stream),),
+                                 extra=max(int(extra), 0))
 
     def batch_quality_ms(self) -> float:
-        ms = C.c_float(0.0)
-        self._chk(self._lib.rfid_batch_quality_ms(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._stage_ms(self._lib.rfid_batch_quality_ms)
 
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1

@@ -5,31 +5,17 @@ RN16 and EPC windows alternate as the reader state demands; the oracle's decoder
 results, scores, port-0 bits and the reader state compared after every call.  tests/test_gpu_decoder_windows.py runs the
 same driver against the real library."""
 import ctypes as C
-import os
-import sys
 
 import pytest
 
 import decoder_windows as dw
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "fake_hip"))
+import emu_lib
 
 
 @pytest.fixture(scope="module", autouse=True)
 def emulated_library():
-    """librfid_capi_emu.so in place of librfid_mi355x.so -- for this module's tests, in this process, and put back afterwards"""
-    import build_capi_emu as fake_build
-    from rfid import _capi
-    lib = C.CDLL(fake_build.build())
-    for name, (res, args) in _capi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    saved = _capi._lib
-    _capi._lib = lib
-    yield lib
-    _capi._lib = saved
+    with emu_lib.emulated_library() as lib:
+        yield lib
 
 
 def test_decoder_work_on_every_crafted_window(oracle_mod):

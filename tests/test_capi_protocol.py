@@ -8,7 +8,6 @@ The cases are the GPU suite's own protocol tests (tests/test_gpu_*.py: the ones 
 with traces of a few inventory rounds; each compares with the oracle exactly as it does on the device.  A second set runs with
 FAKE_HIP_LAG > 0: work enqueued on a stream becomes runnable only some runtime calls later, so that the host meets passes that are
 still "running" -- the orderings a real device produces."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -16,8 +15,9 @@ import sys
 import numpy as np
 import pytest
 
+import emu_lib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "fake_hip"))
 
 
 class SmallSynth:
@@ -38,19 +38,8 @@ class SmallSynth:
 
 @pytest.fixture(scope="module", autouse=True)
 def emulated_library():
-    """librfid_capi_emu.so in place of librfid_mi355x.so -- for this module's tests, in this process, and put back afterwards"""
-    import build_capi_emu as fake_build
-    import rfid
-    from rfid import _capi
-    lib = C.CDLL(fake_build.build())
-    for name, (res, args) in _capi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    saved = _capi._lib
-    _capi._lib = lib
-    yield lib
-    _capi._lib = saved
+    with emu_lib.emulated_library() as lib:
+        yield lib
 
 
 def _small(synth_mod, cap=4):

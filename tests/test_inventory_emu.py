@@ -7,16 +7,13 @@ The traces: rfid.synth.make_trace draws a random 88-bit head per tag, so tag_ids
 which two share the byte tag_reads[] is keyed by.  Seeds 104 (4 rounds) and 112 (3 rounds), FIXED_Q = 2: the oracle alone reads all
 three frames in each, the two 0x27 frames apart, every frame at least twice (asserted below before anything is compared)."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import inventory_ref as ref
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "fake_hip"))
+import emu_lib
+from emu_lib import oracle_runs as _oracle, run_pass as _pass
 
 TAGS = (0x27, 0x27, 0x31)
 SEEDS = ((104, 4), (112, 3))       # (seed, inventory rounds) per trace
@@ -24,19 +21,8 @@ SEEDS = ((104, 4), (112, 3))       # (seed, inventory rounds) per trace
 
 @pytest.fixture(scope="module", autouse=True)
 def emulated_library():
-    """librfid_capi_emu.so in place of librfid_mi355x.so -- for this module's tests, in this process, and put back afterwards"""
-    import build_capi_emu as fake_build
-    import rfid
-    from rfid import _capi
-    lib = C.CDLL(fake_build.build())
-    for name, (res, args) in _capi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    saved = _capi._lib
-    _capi._lib = lib
-    yield lib
-    _capi._lib = saved
+    with emu_lib.emulated_library() as lib:
+        yield lib
 
 
 def _batch(synth_mod, **kw):
@@ -52,10 +38,6 @@ def _batch(synth_mod, **kw):
     return host, lens, L, stride
 
 
-def _oracle(oracle_mod, host, lens, **cfg):
-    return [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=2, **cfg)) for b in range(len(lens))]
-
-
 @pytest.fixture(scope="module")
 def batch(oracle_mod, synth_mod):
     host, lens, L, stride = _batch(synth_mod)
@@ -67,10 +49,6 @@ def batch(oracle_mod, synth_mod):
         assert len(e) == 3 and (e["tag_id"] == 0x27).sum() == 2 and (e["reads"] >= 2).all(), (b, e)
         assert len({bytes(f) for f in e["frame"]}) == 3
     return host, lens, L, stride, refs, want, want_counts
-
-
-def _pass(ctx, host, lens, L, stride):
-    ctx.batch_process_ptr(host.ctypes.data, stride, L, lens.ctypes.data)
 
 
 @pytest.mark.parametrize("mode", [0, 2], ids=["fused-front-end", "long-stream"])

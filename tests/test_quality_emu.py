@@ -7,17 +7,14 @@ from the library's own windows or results, and every comparison is exact: by bit
 The traces are those of tests/test_inventory_emu.py: seeds 104 (4 rounds) and 112 (3 rounds), FIXED_Q = 2, tags (0x27, 0x27, 0x31),
 sigma = 0.02: a third of the slots are empty or collided, and the reference ACKs every one of them."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import quality_ref as ref
 import tracks_ref as tref
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "fake_hip"))
+import emu_lib
+from emu_lib import pack as _pack, run_pass as _pass
 
 TAGS = (0x27, 0x27, 0x31)
 SEEDS = ((104, 4), (112, 3))       # (seed, inventory rounds) per trace
@@ -25,30 +22,8 @@ SEEDS = ((104, 4), (112, 3))       # (seed, inventory rounds) per trace
 
 @pytest.fixture(scope="module", autouse=True)
 def emulated_library():
-    """librfid_capi_emu.so in place of librfid_mi355x.so -- for this module's tests, in this process, and put back afterwards"""
-    import build_capi_emu as fake_build
-    import rfid
-    from rfid import _capi
-    lib = C.CDLL(fake_build.build())
-    for name, (res, args) in _capi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    saved = _capi._lib
-    _capi._lib = lib
-    yield lib
-    _capi._lib = saved
-
-
-def _pack(ts, shorten=777):
-    L = max(map(len, ts))
-    stride = (L + 1) & ~1
-    host = np.zeros((len(ts), stride), dtype=np.complex64)
-    lens = np.array([len(t) for t in ts], dtype=np.int64)
-    lens[0] -= shorten            # (ragged also where the longest trace is concerned)
-    for i, t in enumerate(ts):
-        host[i, : len(t)] = t
-    return host, lens, L, stride
+    with emu_lib.emulated_library() as lib:
+        yield lib
 
 
 def _oracle(oracle_mod, host, lens, **cfg):
@@ -73,10 +48,6 @@ def batch(oracle_mod, synth_mod):
         assert snr[ok].min() - snr[~ok].max() > 6.0, (b, snr[ok].min(), snr[~ok].max())
     assert len(packed) == sum(o.state.n_epc_correct for o in refs)
     return host, lens, L, stride, refs, ys, (packed, rows)
-
-
-def _pass(ctx, host, lens, L, stride):
-    ctx.batch_process_ptr(host.ctypes.data, stride, L, lens.ctypes.data)
 
 
 def _plan(ctx, n, L, max_tags=8):

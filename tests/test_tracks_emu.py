@@ -8,17 +8,14 @@ sigma = 0.02.  By the oracle alone the three frames' reads fall at seq [3,15,21,
 [3,13,21] [7,9] (seed 112): the tags interleave in time, so the grouped order differs from the window order, and one tag has four
 reads (asserted below before anything is compared)."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
 import inventory_ref as iref
 import tracks_ref as ref
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "fake_hip"))
+import emu_lib
+from emu_lib import pack as _pack, oracle_runs as _oracle, run_pass as _pass
 
 TAGS = (0x27, 0x27, 0x31)
 SEEDS = ((104, 4), (112, 3))       # (seed, inventory rounds) per trace
@@ -28,38 +25,12 @@ SEQS_CUT = ([3, 5, 7, 11, 13], [1, 3, 7, 9, 13])      # max_num_queries = 7: wha
 
 @pytest.fixture(scope="module", autouse=True)
 def emulated_library():
-    """librfid_capi_emu.so in place of librfid_mi355x.so -- for this module's tests, in this process, and put back afterwards"""
-    import build_capi_emu as fake_build
-    import rfid
-    from rfid import _capi
-    lib = C.CDLL(fake_build.build())
-    for name, (res, args) in _capi.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    saved = _capi._lib
-    _capi._lib = lib
-    yield lib
-    _capi._lib = saved
-
-
-def _pack(ts, shorten=777):
-    L = max(map(len, ts))
-    stride = (L + 1) & ~1
-    host = np.zeros((len(ts), stride), dtype=np.complex64)
-    lens = np.array([len(t) for t in ts], dtype=np.int64)
-    lens[0] -= shorten            # (ragged also where the longest trace is concerned)
-    for i, t in enumerate(ts):
-        host[i, : len(t)] = t
-    return host, lens, L, stride
+    with emu_lib.emulated_library() as lib:
+        yield lib
 
 
 def _traces(synth_mod):
     return [synth_mod.make_trace(n_rounds=n, fixed_q=2, tag_ids=TAGS, seed=seed, sigma=0.02, t1_jitter_raw=3).samples for seed, n in SEEDS]
-
-
-def _oracle(oracle_mod, host, lens, **cfg):
-    return [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=2, **cfg)) for b in range(len(lens))]
 
 
 def _seqs_by_entry(reads, off):
@@ -80,10 +51,6 @@ def batch(oracle_mod, synth_mod):
         assert (np.diff(np.sort(r["seq"])) > 0).all()
     assert len(reads) == sum(o.state.n_epc_correct for o in refs)
     return host, lens, L, stride, refs, (ent, counts, reads, off)
-
-
-def _pass(ctx, host, lens, L, stride):
-    ctx.batch_process_ptr(host.ctypes.data, stride, L, lens.ctypes.data)
 
 
 def _check(ctx, want, what=""):
