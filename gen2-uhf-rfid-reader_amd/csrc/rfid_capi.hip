@@ -67,6 +67,7 @@ struct RfidKnobs {
   int la_profile = 0;      // RFID_LA_PROFILE        1: where the look-ahead's host time went, on stderr when the context is destroyed
   // ---- test hooks ----
   int front_unfused = 0;   // RFID_FRONT_UNFUSED     1: many traces through the stage kernels instead of front_end_fused_kernel
+  int front_single_step = 0;  // RFID_FRONT_SINGLE_STEP 1: front_end_fused_kernel runs its one-step-at-a-time body (gate_scan_body<true>) instead of the pair body
   int front_chunks = 1;    // RFID_FRONT_CHUNKS      2..16: the time-chunked stage kernels on two streams (round 1's overlap)
   int fsm_lanes_min = -1;  // RFID_LS2_FSM_LANES_MIN from how many possible units on the state machine runs one lane per unit (-1: 8192)
   int dc_rounds = -1;      // RFID_LS2_DC_ROUNDS     0..64: dc_est rounds a long-stream pass enqueues behind the first (-1: by the pass's size -- 0 / 3 / 10; what they leave, the finishing walk takes)
@@ -358,6 +359,7 @@ const KnobEntry g_knob_table[] = {
   {"ls_debug", "RFID_LS_DEBUG", &RfidKnobs::ls_debug, 0, 1},
   {"la_profile", "RFID_LA_PROFILE", &RfidKnobs::la_profile, 0, 1},
   {"front_unfused", "RFID_FRONT_UNFUSED", &RfidKnobs::front_unfused, 0, 1},
+  {"front_single_step", "RFID_FRONT_SINGLE_STEP", &RfidKnobs::front_single_step, 0, 1},
   {"front_chunks", "RFID_FRONT_CHUNKS", &RfidKnobs::front_chunks, 1, rfid_ctx::MAX_CHUNKS},
   {"fsm_lanes_min", "RFID_LS2_FSM_LANES_MIN", &RfidKnobs::fsm_lanes_min, -1, 1 << 30},
   {"dc_rounds", "RFID_LS2_DC_ROUNDS", &RfidKnobs::dc_rounds, -1, 64},
@@ -1290,9 +1292,10 @@ int rfid_batch_plan(rfid_ctx *c, int n_streams, int64_t max_raw) {
   }
   {
     // the second result set (see rfid_ctx::ResultSet): opt-in (RFID_OVERLAP=2) and only where it is small beside what is
-    // free.  Measured on configs[1] (profiles/r04/overlap.txt): the decoder's waves beside the next front end take their
-    // instruction slots from it -- -1.5 % per pass on one box, +3 % on another (a decoder wave that gets to a CU first keeps
-    // the front end's workgroup out until it is through) -- not a default.
+    // free.  Measured on configs[1] (profiles/r04/overlap.txt): -1.5 % per pass on one box, +3 % on another -- not a default.
+    // The fused front end's 4 waves x 128 VGPRs fill every SIMD's register file for the whole launch, so no 232-VGPR decoder
+    // wave is ever co-resident with it: the only effect is a decoder wave that reaches a CU first and keeps the front end's
+    // workgroup out until it is through, and what overlap=2 measures beyond that is noise.
     const size_t need = sizeof(float2) * (size_t)c->y_stride * n_streams + (sizeof(rfid_window) * 3 + sizeof(rfid_decode_result)) * (size_t)c->flat_cap +
                         sizeof(rfid_stream_stats) * (size_t)n_streams;
     size_t free_b = 0, total_b = 0;
@@ -1857,6 +1860,7 @@ int rfid_batch_process(rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64
     g.flat = c->d_flat; g.flat_count = c->d_flat_count; g.flat_cap = c->flat_cap; g.mode = 0;
     g.raw = (const float2 *)d_raw; g.raw_stride = raw_stride; g.n_raw = n_raw;
     g.raw_vec_ok = ((raw_stride & 1) == 0 && (((uintptr_t)d_raw) & 15) == 0) ? 1 : 0;
+    g.single_step = c->knobs.front_single_step;
     hipLaunchKernelGGL(front_end_fused_kernel, dim3((unsigned)((c->B + GATE_STREAMS_PER_WG - 1) / GATE_STREAMS_PER_WG)),
                        dim3(GATE_THREADS), 0, c->stream, g);
     HIPCHK(c, hipGetLastError());

@@ -283,6 +283,9 @@ struct GateArgs {
   // optional: the launch does nothing when *skip_if != 0 (the sequential scan enqueued behind the long-stream front end
   // as its fallback: it only runs when that front end gave up)
   const int *skip_if;
+  // front_end_fused_kernel only: 0 -- the batch body that works on pairs of steps (gate_pairs_body), 1 -- gate_scan_body<true>,
+  // one step at a time (kept for comparison in one binary)
+  int single_step;
 };
 
 // x / C for the gate's two constant divisors (100: gate_impl.cc:131, 48: :141) in three instructions
@@ -836,16 +839,11 @@ RFID_DEVICE void gate_dc_step(GateBackRegs &g, uint64_t closedmask, uint64_t ope
   g.dci_c = wv::readlane(dci, 63);
 }
 
-RFID_DEVICE void gate_back(const GateArgs &a, GateBackRegs &g, const GateSlot *slot, int pos, int n_total, int row, int lane,
-                           float2 *lds_dc, float2 *lds_tmp, bool &stop) {
-  int word, w1 = 0;
-  uint64_t closedmask, openmask;
-  const int spec_bad_v = wv::lds_peek(&slot->spec_bad);   // (rides on the descriptor's round trip)
-  wv::lds_load_rec(&slot->b_word, word, closedmask);
+// (the step's descriptor is in registers: read by gate_back, or for two steps at once by gate_back_pair)
+RFID_DEVICE void gate_back_desc(const GateArgs &a, GateBackRegs &g, const GateSlot *slot, int word, uint64_t closedmask,
+                                uint64_t openmask, int spec_bad_v, int pos, int n_total, int row, int lane,
+                                float2 *lds_dc, float2 *lds_tmp, bool &stop) {
   const int flags = word & 7, nvalid = (word >> 8) & 0xff, open = (word >> 16) & 0x1ff;   // lane | type << 8
-  // (batch mode only needs to know WHETHER samples lie inside a window: gate_dc_incr's test for a wholly closed step)
-  if (a.mode != 0) wv::lds_load_rec(reinterpret_cast<const int *>(&slot->b_openmask), w1, openmask);
-  else openmask = (flags & 4) ? 1ull : 0ull;
   const bool spec_ok = wv::uniform(spec_bad_v) == 0;
   float dcr, dci;
   const bool lanes_wanted = (open & 0xff) != 0xff || a.mode == 1;   // dc_est at a gate opening / under the gated samples
@@ -886,6 +884,17 @@ RFID_DEVICE void gate_back(const GateArgs &a, GateBackRegs &g, const GateSlot *s
     }
   }
   stop = (flags & 2) != 0;
+}
+RFID_DEVICE void gate_back(const GateArgs &a, GateBackRegs &g, const GateSlot *slot, int pos, int n_total, int row, int lane,
+                           float2 *lds_dc, float2 *lds_tmp, bool &stop) {
+  int word, w1 = 0;
+  uint64_t closedmask, openmask;
+  const int spec_bad_v = wv::lds_peek(&slot->spec_bad);   // (rides on the descriptor's round trip)
+  wv::lds_load_rec(&slot->b_word, word, closedmask);
+  // (batch mode only needs to know WHETHER samples lie inside a window: gate_dc_incr's test for a wholly closed step)
+  if (a.mode != 0) wv::lds_load_rec(reinterpret_cast<const int *>(&slot->b_openmask), w1, openmask);
+  else openmask = (word & 4) ? 1ull : 0ull;
+  gate_back_desc(a, g, slot, word, closedmask, openmask, spec_bad_v, pos, n_total, row, lane, lds_dc, lds_tmp, stop);
 }
 
 // Workgroup = 16 waves = 4 traces.  Wave w serves trace w % 4 in role w / 4: 0 consumer (avg_ampl, state machine),
@@ -990,9 +999,118 @@ RFID_DEVICE float2 gate_fir_step(const GateRawRegs &r, float4 *tile4, int lane, 
   return wv::lds_sum25_in_order(&tile[DECIM * lane]);   // single ds_read_b64s, never ds_read2_b64 (half the LDS rate)
 }
 
+// (one LDS block per kernel, whichever body it runs)
+RFID_DEVICE GateShared *gate_shared() {
+  RFID_SHARED GateShared sh_all[GATE_STREAMS_PER_WG];
+  return sh_all;
+}
+
+// ---- what the two bodies of the scan (gate_scan_body, gate_pairs_body) do alike ---------------------------------
+struct GateExtent { int n_total, n, nsteps; };   // valid samples of the whole trace, of this launch's chunk; its steps
+RFID_DEVICE GateExtent gate_extent(const GateArgs &a, int strm) {
+  int64_t n64 = a.n_dec;
+  if (a.lens) {
+    int64_t r = a.lens[strm];
+    if (r < 0) r = 0;
+    n64 = r / DECIM;
+    if (n64 > a.n_dec) n64 = a.n_dec;
+  }
+  GateExtent e;
+  e.n_total = wv::uniform((int)n64);
+  int64_t nl = n64 - a.pos0;
+  if (nl > a.chunk_len) nl = a.chunk_len;
+  if (nl < 0) nl = 0;
+  e.n = wv::uniform((int)nl);
+  e.nsteps = (e.n + 63) >> 6;
+  return e;
+}
+// filter wave, fused front end: the steps [k0, nsteps) behind the main groups (fewer than a group, the partial step included):
+// load, then filter
+RFID_DEVICE void gate_filter_tail(GateShared &sh, const float2 *xs, int64_t hi_idx, int64_t rbase, bool vec, float2 *yw, int k0,
+                                  int nsteps, int n, bool at_start, int &back_seen, float2 &prev_yv, int lane) {
+  for (int k = k0; k < nsteps; ++k) {
+    while (k - back_seen >= GATE_SLOTS) { back_seen = wv::lds_load(&sh.back_seq); if (k - back_seen >= GATE_SLOTS) wv::backoff(); }
+    GateRawRegs r;
+    gate_load_raw(r, xs, hi_idx, rbase + (int64_t)k * 64 * DECIM, lane, vec);
+    float2 yv = gate_fir_step(r, sh.rawtile, lane, k == 0 && at_start);
+    if (64 * k + lane < n) yw[64 * k + lane] = yv;
+    else yv = make_float2(0.0f, 0.0f);
+    sh.slots[k % GATE_SLOTS].yv[lane] = yv;
+    gate_spec_dc(sh.slots[k % GATE_SLOTS], yv, prev_yv, lane);
+    wv::lds_store(&sh.fir_seq, k + 1, lane);
+  }
+}
+// back wave: its state in, its state out (with the trace's window count and the decoder's lists in batch mode)
+RFID_DEVICE void gate_back_begin(GateBackRegs &g, const GateState *st, float2 *lds_dc, int64_t pos0, int strm, int lane) {
+  if (lane < DC_LEN) lds_dc[lane] = make_float2(st->dcr_re[lane], st->dcr_im[lane]);
+  g.dcr_c = wv::uniform(st->dc_re); g.dci_c = wv::uniform(st->dc_im);
+  g.dc_index = wv::uniform(st->dc_index);
+  g.run_closed = 0; g.ring_stale = 0;
+  g.prev_yv = make_float2(0.0f, 0.0f);
+  g.win_seq = wv::uniform(st->win_seq);
+  g.n_complete = 0; g.written = 0;
+  g.pos0 = (int)pos0; g.strm = strm;
+  wv::wave_sync();
+}
+RFID_DEVICE void gate_back_end(const GateArgs &a, GateBackRegs &g, GateState *st, float2 *lds_dc, int row, int64_t pos0, int lane) {
+  if (g.ring_stale) {
+    // materialise the dc ring: the last 48 closed samples (lanes 16..63 of the last closed step), oldest at dc_index
+    if (lane >= 64 - DC_LEN) {
+      int di = g.dc_index + (lane - (64 - DC_LEN));
+      if (di >= DC_LEN) di -= DC_LEN;
+      lds_dc[di] = g.prev_yv;
+    }
+    wv::wave_sync();
+  }
+  if (lane < DC_LEN) { st->dcr_re[lane] = lds_dc[lane].x; st->dcr_im[lane] = lds_dc[lane].y; }
+  if (lane == 0) {
+    st->dc_re = g.dcr_c; st->dc_im = g.dci_c; st->win_seq = g.win_seq; st->dc_index = g.dc_index;
+    if (a.mode != 0) a.io[1] = g.written;
+  }
+  if (a.mode == 0) {
+    const int before = (pos0 > 0) ? wv::uniform(a.wcount[row]) : 0;   // windows recorded by earlier chunks
+    int tot = before + g.n_complete;
+    tot = (tot < a.wmax) ? tot : a.wmax;
+    if (lane == 0) a.wcount[row] = tot;
+    gate_flat_lists(a, row, before, tot - before, lane);
+  }
+}
+// consumer wave: its state in, its state out
+RFID_DEVICE void gate_fsm_begin(GateRegs &g, const GateState *st, int n) {
+  g.avg_c = wv::uniform(st->avg_ampl);
+  g.f_n = wv::uniform(st->n_samples); g.f_state = wv::uniform(st->signal_state);
+  g.f_pulses = wv::uniform(st->num_pulses); g.f_open = wv::uniform(st->gate_open);
+  g.f_ung = wv::uniform(st->n_to_ungate); g.f_type = wv::uniform(st->wtype);
+  if (g.f_ung == 0) g.f_ung = g.f_type ? EPC_WIN : RN16_WIN;  // fresh state: first window is an RN16
+  g.consumed = n; g.stop = false;
+}
+template <bool FUSED>
+RFID_DEVICE void gate_fsm_end(const GateArgs &a, const GateRegs &g, GateState *st, GateShared &sh, const float2 *ys, int win_index0, int lane) {
+  // wait for the filter wave (fused front end: its y stores being visible)
+  while (wv::lds_load(&sh.prod_done) == 0) wv::backoff();
+  // amplitude ring: the last min(100, consumed) samples of this call overwrite their slots
+  // (the producer wave read st->win before it produced step 0, i.e. long before this point --
+  // except for an empty call, which writes nothing here)
+  {
+    const int c = g.consumed;
+    const int first = (c > WIN_LEN) ? (c - WIN_LEN) : 0;
+    for (int i = first + lane; i < c; i += 64) {
+      const float2 v = FUSED ? wv::load_coherent(&ys[i]) : ys[i];
+      st->win[(win_index0 + i) % WIN_LEN] = wv::hypot_f(v.x, v.y);
+    }
+  }
+  if (lane == 0) {
+    st->avg_ampl = g.avg_c;
+    st->n_samples = g.f_n; st->signal_state = g.f_state; st->num_pulses = g.f_pulses;
+    st->gate_open = g.f_open; st->n_to_ungate = g.f_ung; st->wtype = g.f_type;
+    st->win_index = (win_index0 + g.consumed) % WIN_LEN;
+    if (a.mode != 0) a.io[0] = g.consumed;
+  }
+}
+
 template <bool FUSED>
 RFID_DEVICE void gate_scan_body(const GateArgs &a) {
-  RFID_SHARED GateShared sh_all[GATE_STREAMS_PER_WG];
+  GateShared *sh_all = gate_shared();
   const int lane = wv::lane_id();
   const int wave = wv::uniform((int)(threadIdx.x >> 6));
   const int role = wave / GATE_STREAMS_PER_WG;           // 0 consumer, 1 filter, 2 back, 3 producer
@@ -1006,22 +1124,11 @@ RFID_DEVICE void gate_scan_body(const GateArgs &a) {
   if (s >= a.n_streams) return;
   if (a.skip_if && wv::uniform(*a.skip_if) != 0) return;
   const int strm = s, row = s;
-  const int64_t pos0 = a.pos0, chunk_len = a.chunk_len;
+  const int64_t pos0 = a.pos0;
   GateState *st = a.state + row;
   const float2 *ys = a.y + (int64_t)strm * a.y_stride + pos0;
-  int64_t n64 = a.n_dec;
-  if (a.lens) {
-    int64_t r = a.lens[strm];
-    if (r < 0) r = 0;
-    n64 = r / DECIM;
-    if (n64 > a.n_dec) n64 = a.n_dec;
-  }
-  const int n_total = wv::uniform((int)n64);          // valid samples of the whole trace
-  int64_t nl = n64 - pos0;                            // ... of this launch's chunk
-  if (nl > chunk_len) nl = chunk_len;
-  if (nl < 0) nl = 0;
-  const int n = wv::uniform((int)nl);
-  const int nsteps = (n + 63) >> 6;
+  const GateExtent ex = gate_extent(a, strm);
+  const int n_total = ex.n_total, n = ex.n, nsteps = ex.nsteps;
   const int win_index0 = wv::uniform(st->win_index);
 
   if (role == 1) {
@@ -1080,18 +1187,7 @@ RFID_DEVICE void gate_scan_body(const GateArgs &a) {
         for (; grp < g_fast; ++grp) group(grp, GateTrue());
         for (; grp < ngroups; ++grp) group(grp, GateFalse());
       }
-      // the last few steps (fewer than a group, the partial step included): load, then filter
-      for (int k = ngroups * GATE_RAW_DEPTH; k < nsteps; ++k) {
-        while (k - back_seen >= GATE_SLOTS) { back_seen = wv::lds_load(&sh.back_seq); if (k - back_seen >= GATE_SLOTS) wv::backoff(); }
-        GateRawRegs r;
-        gate_load_raw(r, xs, hi_idx, rbase + (int64_t)k * 64 * DECIM, lane, vec);
-        float2 yv = gate_fir_step(r, sh.rawtile, lane, k == 0 && at_start);
-        if (64 * k + lane < n) yw[64 * k + lane] = yv;
-        else yv = make_float2(0.0f, 0.0f);
-        sh.slots[k % GATE_SLOTS].yv[lane] = yv;
-        gate_spec_dc(sh.slots[k % GATE_SLOTS], yv, prev_yv, lane);
-        wv::lds_store(&sh.fir_seq, k + 1, lane);
-      }
+      gate_filter_tail(sh, xs, hi_idx, rbase, vec, yw, ngroups * GATE_RAW_DEPTH, nsteps, n, at_start, back_seen, prev_yv, lane);
       wv::global_release();                       // the consumer's write-back re-reads y
     } else {
       float2 cur[GATE_PREFETCH], nxt[GATE_PREFETCH];
@@ -1151,16 +1247,8 @@ RFID_DEVICE void gate_scan_body(const GateArgs &a) {
   } else if (role == 2) {
     // ================= back wave: dc_est, window records, gated output; frees the slots ===========================
     float2 *lds_dc = sh.dc, *lds_tmp = sh.tmp;
-    if (lane < DC_LEN) lds_dc[lane] = make_float2(st->dcr_re[lane], st->dcr_im[lane]);
     GateBackRegs g;
-    g.dcr_c = wv::uniform(st->dc_re); g.dci_c = wv::uniform(st->dc_im);
-    g.dc_index = wv::uniform(st->dc_index);
-    g.run_closed = 0; g.ring_stale = 0;
-    g.prev_yv = make_float2(0.0f, 0.0f);
-    g.win_seq = wv::uniform(st->win_seq);
-    g.n_complete = 0; g.written = 0;
-    g.pos0 = (int)pos0; g.strm = strm;
-    wv::wave_sync();
+    gate_back_begin(g, st, lds_dc, pos0, strm, lane);
     bool stop = false;
     int fsm_seen = 0;    // sh.fsm_seq as last read (it only grows)
     for (int k = 0; k < nsteps && !stop; ++k) {
@@ -1179,37 +1267,12 @@ RFID_DEVICE void gate_scan_body(const GateArgs &a) {
       gate_back(a, g, &sh.slots[k % GATE_SLOTS], 64 * k, n_total, row, lane, lds_dc, lds_tmp, stop);
       wv::lds_store(&sh.back_seq, k + 1, lane);   // slot k free again
     }
-    if (g.ring_stale) {
-      // materialise the dc ring: the last 48 closed samples (lanes 16..63 of the last closed step), oldest at dc_index
-      if (lane >= 64 - DC_LEN) {
-        int di = g.dc_index + (lane - (64 - DC_LEN));
-        if (di >= DC_LEN) di -= DC_LEN;
-        lds_dc[di] = g.prev_yv;
-      }
-      wv::wave_sync();
-    }
-    if (lane < DC_LEN) { st->dcr_re[lane] = lds_dc[lane].x; st->dcr_im[lane] = lds_dc[lane].y; }
-    if (lane == 0) {
-      st->dc_re = g.dcr_c; st->dc_im = g.dci_c; st->win_seq = g.win_seq; st->dc_index = g.dc_index;
-      if (a.mode != 0) a.io[1] = g.written;
-    }
-    if (a.mode == 0) {
-      const int before = (pos0 > 0) ? wv::uniform(a.wcount[row]) : 0;   // windows recorded by earlier chunks
-      int tot = before + g.n_complete;
-      tot = (tot < a.wmax) ? tot : a.wmax;
-      if (lane == 0) a.wcount[row] = tot;
-      gate_flat_lists(a, row, before, tot - before, lane);
-    }
+    gate_back_end(a, g, st, lds_dc, row, pos0, lane);
   } else {
     // ================= consumer: the edge / pulse / window state machine ============================================
     wv::set_priority_high();
     GateRegs g;
-    g.avg_c = wv::uniform(st->avg_ampl);
-    g.f_n = wv::uniform(st->n_samples); g.f_state = wv::uniform(st->signal_state);
-    g.f_pulses = wv::uniform(st->num_pulses); g.f_open = wv::uniform(st->gate_open);
-    g.f_ung = wv::uniform(st->n_to_ungate); g.f_type = wv::uniform(st->wtype);
-    if (g.f_ung == 0) g.f_ung = g.f_type ? EPC_WIN : RN16_WIN;  // fresh state: first window is an RN16
-    g.consumed = n; g.stop = false;
+    gate_fsm_begin(g, st, n);
     GateNext nx;
     nx.step = -1; nx.sq = 0; nx.amp = nx.d = 0.0f;
     for (int k = 0; k < nsteps && !g.stop; ++k) {
@@ -1221,34 +1284,348 @@ RFID_DEVICE void gate_scan_body(const GateArgs &a) {
     wv::lds_store(&sh.fsm_done, 1, lane);
     if (g.stop) wv::lds_store(&sh.stop, 1, lane);
 
-    // ---- write state back ----------------------------------------------------------------
-    // wait for the filter wave (fused front end: its y stores being visible)
-    while (wv::lds_load(&sh.prod_done) == 0) wv::backoff();
-    // amplitude ring: the last min(100, consumed) samples of this call overwrite their slots
-    // (the producer wave read st->win before it produced step 0, i.e. long before this point --
-    // except for an empty call, which writes nothing here)
+    gate_fsm_end<FUSED>(a, g, st, sh, ys, win_index0, lane);
+  }
+}
+
+// =========================================================================================
+// 2a'. The fused front end on PAIRS of steps (front_end_fused_kernel, batch mode; GateArgs::single_step == 0).
+//     A pair is two ordinary consecutive slots (2p, 2p + 1), both full steps, handled in one loop trip by every role: one
+//     wait, one sequence-word store (+2), and two independent dependence chains to interleave.  What is left over -- an odd
+//     full step, the partial last step -- goes through the single-step helpers above.
+// =========================================================================================
+// chain_add_scan for two consecutive steps from ONE carry: while all 128 partial sums stay in the carry's binade the second
+// step's sums are the first step's integer total plus a prefix sum of their own, and the parity chain of the rounding ties
+// runs on across the boundary (the carry-in of the second step is the parity after the first).
+struct ScanHalf {
+  float frac;
+  bool tie;
+  int R;
+  uint64_t badmask_t, tiemask;
+};
+RFID_DEVICE void scan_half_round(float x, float scale, uint32_t sign, ScanHalf &h) {
+  const float t = sign ? -(x * scale) : (x * scale);
+  const float r = wv::rint_f(t);
+  h.frac = t - r;
+  const bool bad_t = !(__builtin_fabsf(t) < 4194304.0f);
+  const bool half = __builtin_fabsf(h.frac) == 0.5f;
+  h.tie = !bad_t && half;
+  h.R = wv::f2i(bad_t ? 0.0f : r);
+  h.badmask_t = wv::ballot(bad_t);
+  h.tiemask = wv::ballot(half) & ~h.badmask_t;
+}
+// the ties of one step (see chain_add_scan); cin = parity of the sum before its first sample -> parity after its last
+RFID_DEVICE uint32_t scan_half_ties(ScanHalf &h, uint32_t cin, int lane) {
+  const int I = h.R - ((h.frac < 0.0f) ? 1 : 0);
+  const uint64_t rodd = wv::ballot((h.R & 1) != 0) & ~h.tiemask;
+  const uint64_t iodd = wv::ballot((I & 1) != 0) & h.tiemask;
+  const uint64_t Q = prefix_xor64(rodd);
+  const uint64_t gen = h.tiemask & Q, X = gen | ~h.tiemask;
+  const uint64_t sum = X + gen + (uint64_t)(cin & 1u);
+  const uint64_t W = X ^ gen ^ sum;
+  const uint64_t par = (Q << 1) ^ W;                              // bit k = parity of the sum before sample k
+  const uint64_t up = (par ^ iodd) & h.tiemask;
+  h.R = h.tie ? (I + (int)((up >> lane) & 1ull)) : h.R;
+  // a tie leaves an even sum, any other sample toggles the parity by R & 1
+  return (h.tiemask >> 63) ? 0u : (uint32_t)(((par ^ rodd) >> 63) & 1ull);
+}
+RFID_DEVICE bool chain_add_scan_pair(float carry, float x0, float x1, int lane, float &out0, float &out1) {
+  const uint32_t cb = wv::f2u(carry);
+  const uint32_t e_b = (cb >> 23) & 0xffu;
+  const uint32_t sign = cb & 0x80000000u;
+  const float scale = wv::u2f(((277u - e_b) & 0xffu) << 23);
+  ScanHalf h0, h1;
+  scan_half_round(x0, scale, sign, h0);
+  scan_half_round(x1, scale, sign, h1);
+  if ((h0.tiemask | h1.tiemask) != 0ull) {
+    uint32_t par = cb & 1u;
+    if (h0.tiemask != 0ull) par = scan_half_ties(h0, par, lane);
+    else par ^= (uint32_t)wv::popc64(wv::ballot((h0.R & 1) != 0)) & 1u;   // (no tie in the first step: every sample toggles)
+    if (h1.tiemask != 0ull) scan_half_ties(h1, par, lane);
+  }
+  const int s0 = wv::scan_add(h0.R), s1 = wv::scan_add(h1.R);
+  const uint32_t base = cb & 0x7fffffffu;
+  const uint32_t mag0 = base + (uint32_t)s0;
+  const uint32_t mag1 = base + (uint32_t)wv::readlane(s0, 63) + (uint32_t)s1;
+  const uint64_t badmask_s = wv::ballot((((mag0 ^ cb) | (mag1 ^ cb)) & 0x7f800000u) != 0u) |
+                             wv::ballot((mag0 & 0x007fffffu) == 0u) | wv::ballot((mag1 & 0x007fffffu) == 0u);
+  const bool bad_c = e_b < 23u || e_b > 254u;
+  out0 = wv::u2f(mag0 | sign);
+  out1 = wv::u2f(mag1 | sign);
+  return (h0.badmask_t | h1.badmask_t | badmask_s) == 0ull && !bad_c;
+}
+
+// gate_produce for two full steps: the two |x| chains are independent of each other, the amplitude ring goes in step
+// order (the second step's x[i-100] of lanes >= 36 are the first step's new amplitudes)
+RFID_DEVICE void gate_produce_pair(GateSlot &s0, GateSlot &s1, float2 yv0, float2 yv1, int lane, float *lds_win, int &win_index) {
+  const float amp0 = wv::hypot_f(yv0.x, yv0.y);
+  const float amp1 = wv::hypot_f(yv1.x, yv1.y);
+  int wi0 = win_index + lane;
+  if (wi0 >= WIN_LEN) wi0 -= WIN_LEN;
+  int wi1 = wi0 + 64;
+  if (wi1 >= WIN_LEN) wi1 -= WIN_LEN;
+  const float old0 = lds_win[wi0];
+  wv::wave_sync();
+  lds_win[wi0] = amp0;
+  wv::wave_sync();
+  const float old1 = lds_win[wi1];
+  wv::wave_sync();
+  lds_win[wi1] = amp1;
+  wv::wave_sync();
+  static_assert(WIN_LEN == 100, "128 mod WIN_LEN");
+  win_index += 128 - WIN_LEN;
+  if (win_index >= WIN_LEN) win_index -= WIN_LEN;
+  const float nd0 = amp0 - old0, nd1 = amp1 - old1;
+  float d0, d1;
+  if (__builtin_expect((div_const_bad(nd0) | div_const_bad(nd1)) == 0ull, 1)) {
+    d0 = div_const_fast<WIN_LEN>(nd0); d1 = div_const_fast<WIN_LEN>(nd1);
+  } else {
+    d0 = wv::fdiv(nd0, (float)WIN_LEN); d1 = wv::fdiv(nd1, (float)WIN_LEN);
+  }
+  s0.amp[lane] = amp0; s0.d[lane] = d0;
+  s1.amp[lane] = amp1; s1.d[lane] = d1;
+}
+
+// the next pair's slots, fetched one pair early by the consumer.  Plain LDS reads, unlike gate_consume's wv::lds_prefetch: the
+// values are loop-carried in two register sets (this pair's are still in use when the next pair's are asked for), and with
+// reads the compiler does not know to be in flight a register copy between the two sets may be placed ahead of the wait.
+// Here the compiler places the waits itself; the fences only keep the order sequence word -> slots.
+struct GateNextPair {
+  int step;           // the first step of the pair these values belong to (-1: none)
+  int sq;             // the sequence word as read just before the slots: the pair is valid iff sq > step + 1
+  float amp0, d0, amp1, d1;
+};
+RFID_DEVICE void gate_fetch_pair(GateNextPair &nx, const int *seq, const GateSlot *s0, const GateSlot *s1, int k, int lane) {
+  wv::compiler_fence();
+  nx.sq = wv::lds_peek(seq);
+  wv::compiler_fence();
+  nx.amp0 = s0->amp[lane]; nx.d0 = s0->d[lane];
+  nx.amp1 = s1->amp[lane]; nx.d1 = s1->d[lane];
+  wv::compiler_fence();
+  nx.step = k;
+}
+RFID_DEVICE void gate_consume_pair(GateRegs &g, GateSlot *s0, GateSlot *s1, const GateSlot *n0, const GateSlot *n1,
+                                   GateNextPair &nx, const int *seq, int k, int lane) {
+  if (!(nx.step == k && wv::uniform(nx.sq) > k + 1)) {
+    // (rare) wait for the producer, then fetch the pair
+    while (wv::lds_load(seq) <= k + 1) wv::backoff();
+    gate_fetch_pair(nx, seq, s0, s1, k, lane);
+  }
+  const float f_amp0 = nx.amp0, f_d0 = nx.d0, f_amp1 = nx.amp1, f_d1 = nx.d1;
+  // avg_ampl after every sample of both steps: one integer scan from the one carry, else step by step as gate_consume does
+  float avg0, avg1;
+  if (__builtin_expect(!chain_add_scan_pair(g.avg_c, f_d0, f_d1, lane, avg0, avg1), 0)) {
+    avg0 = chain_add_auto(g.avg_c, f_d0, lane);
+    avg1 = chain_add_auto(wv::readlane(avg0, 63), f_d1, lane);
+  }
+  g.avg_c = wv::readlane(avg1, 63);
+  const float th0 = avg0 * THRESH_FRACTION, th1 = avg1 * THRESH_FRACTION;
+  const uint64_t below0 = wv::ballot(f_amp0 < th0), below1 = wv::ballot(f_amp1 < th1);
+  // the next pair: the producer is normally more than a pair ahead, and the reads complete behind the state machine below
+  // (the sequence word tells the next call whether they count)
+  gate_fetch_pair(nx, seq, n0, n1, k + 2, lane);
+  uint64_t closed0, open0, closed1, open1;
+  int ol0 = 0xff, ot0 = 0, ol1 = 0xff, ot1 = 0;
+  // one test for both steps: gate_fsm_step's two plain kinds of step, twice in a row
+  //   (A) f_ung - f_n > 128: the second step sees f_n + 64 and still more than 64 to go;
+  //   (B) no sample of either step below the threshold and no opening due within 128 samples: the first step leaves
+  //       POS_EDGE, the pulse count and (saturating) f_n + 64 behind, on which the second step's test holds as well.
+  const bool plain_open = g.f_open && (g.f_ung - g.f_n > 128);
+  const bool plain_closed = !g.f_open && (g.f_state == 1) && ((below0 | below1) == 0) &&
+                            !((g.f_pulses > NUM_PULSES_CMD) && (T1_SAMPLES - g.f_n < 128));
+  if (__builtin_expect(plain_open || plain_closed, 1)) {
+    g.f_n += 128;
+    closed0 = closed1 = plain_closed ? ~0ull : 0ull;
+    open0 = open1 = plain_closed ? 0ull : ~0ull;
+    if (!g.f_open && g.f_n > GATE_N_SAT) g.f_n = GATE_N_SAT;
+  } else {
+    const uint64_t above0 = wv::ballot(f_amp0 > th0), above1 = wv::ballot(f_amp1 > th1);
+    int nv = 64;
+    gate_fsm_step(0, g, below0, above0, 64 * k, nv, closed0, open0, ol0, ot0);
+    nv = 64;
+    gate_fsm_step(0, g, below1, above1, 64 * k + 64, nv, closed1, open1, ol1, ot1);
+  }
+  wv::lds_store_rec(&s0->b_word, ((closed0 != 0) ? 1 : 0) | ((open0 != 0) ? 4 : 0) | (64 << 8) | (ol0 << 16) | (ot0 << 24), closed0, lane);
+  wv::lds_store_rec(&s1->b_word, ((closed1 != 0) ? 1 : 0) | ((open1 != 0) ? 4 : 0) | (64 << 8) | (ol1 << 16) | (ot1 << 24), closed1, lane);
+}
+
+// gate_back for two steps: both descriptors in one LDS round trip; two steps inside a window cost nothing else
+RFID_DEVICE void gate_back_pair(const GateArgs &a, GateBackRegs &g, const GateSlot *s0, const GateSlot *s1, int pos, int n_total,
+                                int row, int lane, float2 *lds_dc, float2 *lds_tmp) {
+  int word0, word1;
+  uint64_t closed0, closed1;
+  const int sb0 = wv::lds_peek(&s0->spec_bad), sb1 = wv::lds_peek(&s1->spec_bad);
+  wv::lds_load_rec(&s0->b_word, word0, closed0);
+  wv::lds_load_rec(&s1->b_word, word1, closed1);
+  if (((word0 | word1) & 1) == 0) {
+    // both steps lie entirely inside a window (a step with an opening has closed samples): dc_est, the ring and its index do not move
+    g.run_closed = 0;
+    return;
+  }
+  bool stop;
+  gate_back_desc(a, g, s0, word0, closed0, (word0 & 4) ? 1ull : 0ull, sb0, pos, n_total, row, lane, lds_dc, lds_tmp, stop);
+  gate_back_desc(a, g, s1, word1, closed1, (word1 & 4) ? 1ull : 0ull, sb1, pos + 64, n_total, row, lane, lds_dc, lds_tmp, stop);
+}
+
+// The ring protocol of the pair body.  Four sequence words per trace count STEPS: fir_seq >= prod_seq >= fsm_seq >= back_seq,
+// and fir_seq - back_seq <= GATE_SLOTS (the filter wave takes a slot only when the back wave is through with the step that
+// used it).  Every role walks the same list of steps: pairs (2p, 2p + 1) while 2p + 1 < nfull (full steps), then single steps
+// up to nsteps.  A role works on a pair when its upstream word is >= 2p + 2 and then advances its own word by 2 in one
+// store; the filter wave takes a pair when back_seq >= 2p + 2 - GATE_SLOTS, i.e. when BOTH slots are free -- GATE_SLOTS is
+// even, so the two slots of a pair never straddle the wrap.  (The filter wave's own grouping differs: whole groups of
+// GATE_RAW_DEPTH = 6 steps as three pairs, the rest of its steps one by one -- downstream a pair then simply becomes ready
+// in two stores.)  Why nobody waits for ever: batch mode never stops a scan, so every role goes through all nsteps steps
+// and "upstream has finished" can only be observed once the word has its final value nsteps -- a role never waits for a
+// step >= nsteps.  A role downstream of the filter waits for steps the filter wave hands over without anyone's help unless
+// the ring is full; the filter wave at step k waits for step k + 1 - GATE_SLOTS (pair) or k - GATE_SLOTS (single) to leave
+// the back wave, a step that it has itself handed over complete -- together with its pair partner, which is older than k
+// as well -- so the three waves downstream can finish it without any newer step.
+RFID_DEVICE void gate_pairs_body(const GateArgs &a) {
+  GateShared *sh_all = gate_shared();
+  const int lane = wv::lane_id();
+  const int wave = wv::uniform((int)(threadIdx.x >> 6));
+  const int role = wave / GATE_STREAMS_PER_WG;           // 0 consumer, 1 filter, 2 back, 3 producer
+  const int sl = wave % GATE_STREAMS_PER_WG;
+  const int s = (int)blockIdx.x * GATE_STREAMS_PER_WG + sl;
+  GateShared &sh = sh_all[sl];
+  if (lane == 0 && role == 0) {
+    sh.fir_seq = 0; sh.prod_seq = 0; sh.fsm_seq = 0; sh.back_seq = 0; sh.stop = 0; sh.fsm_done = 0; sh.prod_done = 0;
+  }
+  wv::block_sync();   // once, before any hand-off
+  if (s >= a.n_streams) return;
+  if (a.skip_if && wv::uniform(*a.skip_if) != 0) return;
+  const int strm = s, row = s;
+  const int64_t pos0 = a.pos0;
+  GateState *st = a.state + row;
+  const float2 *ys = a.y + (int64_t)strm * a.y_stride + pos0;
+  const GateExtent ex = gate_extent(a, strm);
+  const int n_total = ex.n_total, n = ex.n, nsteps = ex.nsteps;
+  const int nfull = n >> 6;                // steps with all 64 samples
+  const int npaired = nfull & ~1;          // steps [0, npaired) go in pairs
+  const int win_index0 = wv::uniform(st->win_index);
+
+  if (role == 1) {
+    // ================= filter wave (see gate_scan_body): one slot-free test and one fir_seq store per pair ==========
+    float2 prev_yv = make_float2(0.0f, 0.0f);
+    const float2 *xs = a.raw + (int64_t)strm * a.raw_stride;
+    const bool vec = a.raw_vec_ok != 0;
+    const int64_t hi_idx = vec ? ((a.raw_stride - 2) & ~(int64_t)1) : (a.raw_stride - 2);
+    float2 *yw = a.y_w + (int64_t)strm * a.y_stride + pos0;
+    const int64_t rbase = pos0 * DECIM - (NTAPS - 1);
+    static_assert(GATE_RAW_DEPTH % 2 == 0 && GATE_SLOTS % 2 == 0, "a group is whole pairs, a pair does not straddle the ring's wrap");
+    const int ngroups = nfull / GATE_RAW_DEPTH;
+    const bool at_start = pos0 == 0;
+    int back_seen = 0;
+    if (ngroups > 0) {
+      GateRawRegs buf[GATE_RAW_DEPTH];
+#pragma unroll
+      for (int u = 0; u < GATE_RAW_DEPTH; ++u) {
+        gate_load_raw(buf[u], xs, hi_idx, rbase + (int64_t)u * 64 * DECIM, lane, vec);
+        wv::compiler_fence();
+      }
+      int g_fast = 0;
+      if (vec) {
+        const int64_t j_max = (hi_idx - 2 * (GATE_RAW4 - 1) - rbase) / (64 * DECIM);
+        int64_t gf = (j_max + 1) / GATE_RAW_DEPTH - 1;
+        gf = (gf < 0) ? 0 : gf;
+        g_fast = (gf > ngroups) ? ngroups : (int)gf;
+      }
+      auto group = [&](int grp, auto interior) {
+#pragma unroll
+        for (int u = 0; u < GATE_RAW_DEPTH; ++u) {
+          const int k = grp * GATE_RAW_DEPTH + u;
+          if ((u & 1) == 0)   // both slots of the pair (k, k + 1)
+            while (k + 1 - back_seen >= GATE_SLOTS) { back_seen = wv::lds_load(&sh.back_seq); if (k + 1 - back_seen >= GATE_SLOTS) wv::backoff(); }
+          const float2 yv = gate_fir_step(buf[u], sh.rawtile, lane, u == 0 && grp == 0 && at_start);
+          gate_load_raw<decltype(interior)::value>(buf[u], xs, hi_idx, rbase + (int64_t)(k + GATE_RAW_DEPTH) * 64 * DECIM, lane, vec);
+          yw[64 * k + lane] = yv;
+          sh.slots[k % GATE_SLOTS].yv[lane] = yv;
+          gate_spec_dc(sh.slots[k % GATE_SLOTS], yv, prev_yv, lane);
+          if ((u & 1) == 1) wv::lds_store(&sh.fir_seq, k + 1, lane);   // after both slots' data (in-order LDS queue)
+        }
+      };
+      int grp = 0;
+      for (; grp < g_fast; ++grp) group(grp, GateTrue());
+      for (; grp < ngroups; ++grp) group(grp, GateFalse());
+    }
+    gate_filter_tail(sh, xs, hi_idx, rbase, vec, yw, ngroups * GATE_RAW_DEPTH, nsteps, n, at_start, back_seen, prev_yv, lane);
+    wv::global_release();                       // the consumer's write-back re-reads y
+    wv::lds_store(&sh.prod_done, 1, lane);
+  } else if (role == 3) {
+    // ================= producer wave ================================================================================
+    for (int j = lane; j < WIN_LEN; j += 64) sh.win[j] = st->win[j];
+    int win_index = win_index0;
+    wv::wave_sync();
+    int fir_seen = 0;
+    int k = 0;
+    for (; k < npaired; k += 2) {
+      while (fir_seen <= k + 1) { fir_seen = wv::lds_load(&sh.fir_seq); if (fir_seen <= k + 1) wv::backoff(); }
+      GateSlot &s0 = sh.slots[k % GATE_SLOTS], &s1 = sh.slots[k % GATE_SLOTS + 1];
+      gate_produce_pair(s0, s1, s0.yv[lane], s1.yv[lane], lane, sh.win, win_index);
+      wv::lds_store(&sh.prod_seq, k + 2, lane);
+    }
+    for (; k < nsteps; ++k) {
+      while (fir_seen <= k) { fir_seen = wv::lds_load(&sh.fir_seq); if (fir_seen <= k) wv::backoff(); }
+      GateSlot &slot = sh.slots[k % GATE_SLOTS];
+      gate_produce(slot, slot.yv[lane], 64 * k, n, lane, sh.win, win_index);
+      wv::lds_store(&sh.prod_seq, k + 1, lane);
+    }
+  } else if (role == 2) {
+    // ================= back wave ====================================================================================
+    float2 *lds_dc = sh.dc, *lds_tmp = sh.tmp;
+    GateBackRegs g;
+    gate_back_begin(g, st, lds_dc, pos0, strm, lane);
+    int fsm_seen = 0;
+    int k = 0;
+    for (; k < npaired; k += 2) {
+      while (fsm_seen <= k + 1) { fsm_seen = wv::lds_load(&sh.fsm_seq); if (fsm_seen <= k + 1) wv::backoff(); }
+      gate_back_pair(a, g, &sh.slots[k % GATE_SLOTS], &sh.slots[k % GATE_SLOTS + 1], 64 * k, n_total, row, lane, lds_dc, lds_tmp);
+      wv::lds_store(&sh.back_seq, k + 2, lane);   // both slots free again
+    }
+    for (; k < nsteps; ++k) {
+      while (fsm_seen <= k) { fsm_seen = wv::lds_load(&sh.fsm_seq); if (fsm_seen <= k) wv::backoff(); }
+      bool stop;
+      gate_back(a, g, &sh.slots[k % GATE_SLOTS], 64 * k, n_total, row, lane, lds_dc, lds_tmp, stop);
+      wv::lds_store(&sh.back_seq, k + 1, lane);
+    }
+    gate_back_end(a, g, st, lds_dc, row, pos0, lane);
+  } else {
+    // ================= consumer =====================================================================================
+    wv::set_priority_high();
+    GateRegs g;
+    gate_fsm_begin(g, st, n);
+    int k = 0;
     {
-      const int c = g.consumed;
-      const int first = (c > WIN_LEN) ? (c - WIN_LEN) : 0;
-      for (int i = first + lane; i < c; i += 64) {
-        const float2 v = FUSED ? wv::load_coherent(&ys[i]) : ys[i];
-        st->win[(win_index0 + i) % WIN_LEN] = wv::hypot_f(v.x, v.y);
+      GateNextPair nx;
+      nx.step = -1; nx.sq = 0; nx.amp0 = nx.d0 = nx.amp1 = nx.d1 = 0.0f;
+      for (; k < npaired; k += 2) {
+        GateSlot *s0 = &sh.slots[k % GATE_SLOTS], *n0 = &sh.slots[(k + 2) % GATE_SLOTS];
+        gate_consume_pair(g, s0, s0 + 1, n0, n0 + 1, nx, &sh.prod_seq, k, lane);
+        wv::lds_store(&sh.fsm_seq, k + 2, lane);   // both steps handed to the back wave
       }
     }
-    if (lane == 0) {
-      st->avg_ampl = g.avg_c;
-      st->n_samples = g.f_n; st->signal_state = g.f_state; st->num_pulses = g.f_pulses;
-      st->gate_open = g.f_open; st->n_to_ungate = g.f_ung; st->wtype = g.f_type;
-      st->win_index = (win_index0 + g.consumed) % WIN_LEN;
-      if (a.mode != 0) a.io[0] = g.consumed;
+    GateNext nx;
+    nx.step = -1; nx.sq = 0; nx.amp = nx.d = 0.0f;
+    for (; k < nsteps; ++k) {
+      gate_consume(a, g, &sh.slots[k % GATE_SLOTS], &sh.slots[(k + 1) % GATE_SLOTS], nx, &sh.prod_seq, k, 64 * k, n, lane);
+      wv::lds_store(&sh.fsm_seq, k + 1, lane);
+      wv::lds_prefetch_wait<2>(nx.sq, nx.amp, nx.d);
     }
+    wv::lds_store(&sh.fsm_done, 1, lane);
+    gate_fsm_end<true>(a, g, st, sh, ys, win_index0, lane);
   }
 }
 
 RFID_KERNEL_OCC(GATE_THREADS, GATE_WAVES_PER_SIMD) void gate_scan_kernel(GateArgs a) { gate_scan_body<false>(a); }
 // fused front end: matched filter (in the filter waves) + gate scan in one launch; reads the raw
-// 2 Msps samples once, writes y for the decoder
-RFID_KERNEL_OCC(GATE_THREADS, GATE_WAVES_PER_SIMD) void front_end_fused_kernel(GateArgs a) { gate_scan_body<true>(a); }
+// 2 Msps samples once, writes y for the decoder.  Two bodies, chosen by GateArgs::single_step (0, the default: pairs of steps).
+// Register budget: the two bodies together sit exactly at 128 VGPRs (4 waves per SIMD) with 12 SGPRs spilled to lanes of
+// one VGPR, all of them in gate_scan_body<true>'s code, and no scratch.  Anything that lengthens a live range in either
+// body tips the kernel into scratch: check `make resource-usage` after every change to either of them.
+RFID_KERNEL_OCC(GATE_THREADS, GATE_WAVES_PER_SIMD) void front_end_fused_kernel(GateArgs a) {
+  if (a.single_step == 0 && a.mode == 0) gate_pairs_body(a);
+  else gate_scan_body<true>(a);
+}
 
 // =========================================================================================
 // 2b. Long-stream front end (rfid_ls2.hpp): where ONE long trace (or a few) can be cut along time.  Pieces are cut
