@@ -24,6 +24,7 @@
 #include "rfid_inventory.hpp"
 #include "rfid_tracks.hpp"
 #include "rfid_quality.hpp"
+#include "rfid_repair.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
 // the launch list of the long-stream front end, on the stream named by the enclosing scope's `ls2_stream`
@@ -318,6 +319,17 @@ struct rfid_ctx {
     int rows = 0;                     // ceil(wmax / 2)
     int n_streams = 0;                // traces it covered
   } qual;
+  // ---- repair stage (rfid_batch_plan_repair): lives and dies with the inventory workspace; a side branch behind the inventory ----
+  struct Repair : Stage {
+    rfid_repair *d_table = nullptr;   // [B_plan][rows]
+    rfid_repair *d_packed = nullptr;  // [B_plan x rows]: the repaired rows, ordered by (stream, seq)
+    int *d_nrows = nullptr;           // [B_plan]: EPC windows before the cut-off
+    int *d_counts = nullptr, *d_off = nullptr;   // [B_plan][blocks]: repaired rows of a block of REP_ROWS rows / of the blocks before it
+    int *d_head = nullptr;            // [0] repaired rows in all
+    int rows = 0, blocks = 0;         // ceil(wmax / 2), ceil(rows / REP_ROWS)
+    int n_streams = 0;                // traces it covered
+  } rep;
+  DevBuf rep_one;                     // rfid_repair_window: the window, its result, the record
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
   // (rfid_batch_stats ran behind the last decode), the inventory was enqueued behind those statistics, the tracks behind
   // that inventory.  A stage is current only while every stage before it is: one ordered level, moved by mark_current and
@@ -532,8 +544,14 @@ void free_tracks(rfid_ctx *c) {
   c->trk.cap = 0;
 }
 
+void free_repair(rfid_ctx *c) {
+  stage_free(c->rep);
+  c->rep.rows = 0; c->rep.blocks = 0;
+}
+
 void free_inventory(rfid_ctx *c) {
   free_tracks(c);                      // (sized by this workspace, and reading it)
+  free_repair(c);                      // (reading it)
   invalidate_from(c, rfid_ctx::CUR_INVENTORY);
   stage_free(c->inv);
   c->inv.max_tags = 0;
@@ -1041,13 +1059,13 @@ int rfid_ctx_destroy(rfid_ctx *c) {
   la_free(c);
   sio_free(c);
   free_plan(c);
-  void *ptrs[] = {c->d_small, c->s_in.p, c->s_out.p, c->synth_tab.p, c->ls2_ws.p, c->ls2_ws_alt.p};
+  void *ptrs[] = {c->d_small, c->s_in.p, c->s_out.p, c->synth_tab.p, c->ls2_ws.p, c->ls2_ws_alt.p, c->rep_one.p};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->ls2_host) (void)hipHostFree(c->ls2_host);
   for (int i = 0; i < 5; ++i)
     if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-  for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual})
+  for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
@@ -1718,6 +1736,121 @@ int rfid_batch_get_window_quality(rfid_ctx *c, int stream, rfid_read_quality *ou
 int rfid_batch_quality_ms(rfid_ctx *c, float *ms) {
   if (!c || !ms) return RFID_ERR_INVALID;
   return stage_ms(c, c->qual, ms);
+}
+
+// ---- repair stage: CRC-failed EPC frames recovered from their weakest decisions, behind the inventory of a pass (csrc/rfid_repair.hpp) ----
+int rfid_batch_plan_repair(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  if (!c->B_plan || !c->inv.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_repair: no plan with an inventory workspace (rfid_batch_plan_inventory)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  rfid_ctx::Repair &p = c->rep;
+  free_repair(c);
+  // EPC windows are every other window: ceil(wmax / 2) rows per trace, at most as many repaired ones
+  const int rows = (c->wmax + 1) / 2, blocks = (rows + REP_ROWS - 1) / REP_ROWS;
+  const size_t sz_t = sizeof(rfid_repair) * (size_t)rows * (size_t)c->B_plan, sz_b = sizeof(int) * (size_t)blocks * (size_t)c->B_plan;
+  const int r = stage_alloc(c, p, "rfid_batch_plan_repair: workspace allocation",
+                            {{(void **)&p.d_table, sz_t}, {(void **)&p.d_packed, sz_t}, {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan},
+                             {(void **)&p.d_counts, sz_b}, {(void **)&p.d_off, sz_b}, {(void **)&p.d_head, sizeof(int)}});
+  if (r) return r;
+  p.rows = rows; p.blocks = blocks;
+  return RFID_OK;
+}
+
+int rfid_batch_repair(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Inventory &v = c->inv;
+  rfid_ctx::Repair &p = c->rep;
+  if (!c->B || !v.blk || !p.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_repair: no plan with a repair workspace (rfid_batch_plan_repair)");
+  if (!v.enqueued || c->current < rfid_ctx::CUR_INVENTORY) return fail(c, RFID_ERR_STATE, "rfid_batch_repair: no rfid_batch_inventory behind the last pass");
+  HIPCHK(c, hipSetDevice(c->device));
+  // as rfid_batch_quality: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
+  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
+  { int rj = join_tails(c); if (rj) return rj; }
+  const int n = v.n_streams;          // the traces the inventory covered
+  RepArgs a;
+  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->d_wtab; a.res = c->d_res; a.wcount = c->d_wcount; a.stats = c->d_stats;
+  a.wmax = c->wmax; a.n_streams = n; a.rows = p.rows; a.blocks = p.blocks;
+  a.ent = v.d_ent; a.ent_counts = v.d_counts; a.ent_over = v.d_over; a.max_tags = v.max_tags;
+  a.table = p.d_table; a.nrows = p.d_nrows; a.counts = p.d_counts;
+  RepPackArgs g;
+  g.table = p.d_table; g.counts = p.d_counts; g.n_streams = n; g.rows = p.rows; g.blocks = p.blocks;
+  g.offsets = p.d_off; g.head = p.d_head; g.packed = p.d_packed; g.cap = (int64_t)p.rows * c->B_plan;
+  { int r = stage_record(c, p, 0); if (r) return r; }
+  // single-wave workgroups, each walking blocks of 64 rows (no LDS)
+  const int64_t items = (int64_t)n * p.blocks, most = (int64_t)c->n_cus * REP_WGS_PER_CU;
+  const dim3 grid((unsigned)(items < most ? (items > 0 ? items : 1) : most));
+  hipLaunchKernelGGL(repair_kernel, grid, dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(repair_offsets_kernel, dim3(1), scan_block((int)items), 0, c->stream, g);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(repair_pack_kernel, grid, dim3(64), 0, c->stream, g);
+  HIPCHK(c, hipGetLastError());
+  { int r = stage_record(c, p, 1); if (r) return r; }
+  // (as rfid_batch_quality: the pass after next gets this pass's matched-filter buffer and waits for the launches that read it)
+  if (c->y_recorded[c->y_idx]) HIPCHK(c, hipEventRecord(c->ev_y_free[c->y_idx], c->stream));
+  p.enqueued = true;
+  p.n_streams = n;
+  return RFID_OK;
+}
+
+int rfid_batch_get_repairs(rfid_ctx *c, rfid_repair *out, int64_t cap, int64_t *n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
+  rfid_ctx::Repair &p = c->rep;
+  if (!p.blk || !p.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_repairs: no rfid_batch_repair behind this plan");
+  HIPCHK(c, hipSetDevice(c->device));
+  int total = 0;
+  HIPCHK(c, hipMemcpyAsync(&total, p.d_head, sizeof(total), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n = total;
+  if (total > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_repairs: cap is smaller than the number of repaired windows");
+  if (total > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, p.d_packed, sizeof(rfid_repair) * (size_t)total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return RFID_OK;
+}
+
+int rfid_batch_get_window_repairs(rfid_ctx *c, int stream, rfid_repair *out, int64_t cap, int64_t *n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
+  rfid_ctx::Repair &p = c->rep;
+  if (!p.blk || !p.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_repairs: no rfid_batch_repair behind this plan");
+  if (stream < 0 || stream >= p.n_streams) return RFID_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  int nrows = 0;
+  HIPCHK(c, hipMemcpyAsync(&nrows, p.d_nrows + stream, sizeof(nrows), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n = nrows;
+  if (nrows > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_window_repairs: cap is smaller than the number of EPC windows");
+  const int64_t take = (cap < p.rows) ? cap : p.rows;      // (the zeroed rows behind the cut-off too, as far as there is room)
+  if (take > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, p.d_table + (size_t)stream * (size_t)p.rows, sizeof(rfid_repair) * (size_t)take, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return RFID_OK;
+}
+
+int rfid_batch_repair_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  return stage_ms(c, c->rep, ms);
+}
+
+// the per-call form: one window in host memory through the batch kernel's device function (one launch, synchronising)
+int rfid_repair_window(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_result *res, rfid_repair *out) {
+  if (!c || !gated || !res || !out) return RFID_ERR_INVALID;
+  if (res->type != RFID_DECODE_EPC) return fail(c, RFID_ERR_INVALID, "rfid_repair_window: not the result of an EPC window");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_w = up256(sizeof(float2) * (size_t)EPC_WIN), sz_r = up256(sizeof(rfid_decode_result));
+  { int r = grow(c, c->rep_one, sz_w + sz_r + sizeof(rfid_repair)); if (r) return r; }
+  char *b = (char *)c->rep_one.p;
+  HIPCHK(c, hipMemcpyAsync(b, gated, sizeof(float2) * (size_t)EPC_WIN, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(repair_one_kernel, dim3(1), dim3(64), 0, c->stream, (const float2 *)b, (const rfid_decode_result *)(b + sz_w),
+                     (rfid_repair *)(b + sz_w + sz_r));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
 }
 
 // mf -> gate -> decode -> stats.  The matched filter (HBM-bound) and the gate scan (bound by the

@@ -82,6 +82,10 @@ assert STREAM_WINDOW_DTYPE.itemsize == 24 and TAG_ENTRY_DTYPE.itemsize == 48
 QUALITY_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("sig_abs", "<f4"), ("sig_sq", "<f4"), ("quad_sq", "<f4"),
                           ("margin_min", "<f4"), ("margin_bit", "<i4"), ("flags", "<i4")])
 assert TAG_READ_DTYPE.itemsize == 32 and QUALITY_DTYPE.itemsize == 32
+REPAIR_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("flags", "<i4"), ("n_flips", "<i4"),
+                         ("flips", "<i4"), ("cost", "<f4"), ("entry", "<i4"), ("frame", "<u4", (4,))])
+REPAIR_CANDIDATES, REPAIR_MAX_FLIPS = 8, 3
+assert REPAIR_DTYPE.itemsize == 48
 assert WINDOW_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 48
 assert SCORES_DTYPE.itemsize == 144 and STATS_DTYPE.itemsize == 1056
 
@@ -151,6 +155,12 @@ SIGNATURES = {
     "rfid_batch_get_quality": (_i, [_vp, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_get_window_quality": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_quality_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_batch_plan_repair": (_i, [_vp]),
+    "rfid_batch_repair": (_i, [_vp]),
+    "rfid_batch_get_repairs": (_i, [_vp, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_get_window_repairs": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_repair_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_repair_window": (_i, [_vp, _vp, _vp, _vp]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

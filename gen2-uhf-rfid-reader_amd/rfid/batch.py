@@ -45,6 +45,8 @@ class BatchDecoder:
         self.last_tracks = None       # (reads, offsets) of the last decode(..., tracks=True)
         self._qual_planned = False
         self.last_quality = None      # one record per read, aligned with last_tracks[0], of the last decode(..., quality=True)
+        self._rep_planned = False
+        self.last_repairs = None      # the repaired windows, ordered by (stream, seq), of the last decode(..., repair=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -58,6 +60,7 @@ class BatchDecoder:
             self._inv_tags = 0        # (a new plan drops the inventory workspace, and the tracks and quality workspaces with it)
             self._trk_planned = False
             self._qual_planned = False
+            self._rep_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -67,7 +70,8 @@ class BatchDecoder:
         return stride
 
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
-               inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False):
+               inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False,
+               repair: bool = False):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
@@ -77,7 +81,10 @@ class BatchDecoder:
         (reads, offsets), offsets aligned with the entries.  quality=True (implies tracks=True): the SNR and decision
         margin of every EPC window are worked out behind the tracks; `self.last_quality` keeps one record per read, aligned
         with the reads (quality_fields() turns them into snr_db and margin); a trace's whole row, failed windows included:
-        `self.ctx.batch_window_quality(stream)`."""
+        `self.ctx.batch_window_quality(stream)`.  repair=True (implies inventory=True): the CRC-failed EPC windows that
+        reversing one to three of their eight weakest decisions makes pass are searched behind the inventory;
+        `self.last_repairs` keeps their records (capi.REPAIR_DTYPE, ordered by (stream, seq)); a repair is not a read and
+        changes nothing else; a trace's whole row: `self.ctx.batch_window_repairs(stream)`."""
         torch = self._torch
         n = len(traces)
         lens = np.array([len(t) for t in traces], dtype=np.int64)
@@ -96,11 +103,15 @@ class BatchDecoder:
             torch.cuda.current_stream().synchronize()
         t1 = time.perf_counter()
         tracks = tracks or quality
-        inventory = inventory or tracks
+        inventory = inventory or tracks or repair
         if inventory and self._inv_tags != int(max_tags):
             self.ctx.batch_plan_inventory(int(max_tags))
             self._inv_tags = int(max_tags)
             self._trk_planned = False
+            self._rep_planned = False
+        if repair and not self._rep_planned:
+            self.ctx.batch_plan_repair()
+            self._rep_planned = True
         if tracks and not self._trk_planned:
             self.ctx.batch_plan_tracks()
             self._trk_planned = True
@@ -115,6 +126,8 @@ class BatchDecoder:
             self.ctx.batch_tracks_enqueue()
         if quality:
             self.ctx.batch_quality_enqueue()
+        if repair:
+            self.ctx.batch_repair_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
@@ -123,6 +136,8 @@ class BatchDecoder:
             self.last_tracks = self.ctx.batch_tracks_fetch()
         if quality:
             self.last_quality = self.ctx.batch_quality_fetch()
+        if repair:
+            self.last_repairs = self.ctx.batch_repair_fetch()
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -256,8 +271,41 @@ def format_tracks(entries: np.ndarray, reads: np.ndarray, offsets: np.ndarray, n
     return "\n".join(lines) + "\n"
 
 
+REPAIRS_HEADER = "file,epc,pc,seq,t_s,n_flips,flips,cost,known"
+
+
+def repair_flips(rec) -> List[int]:
+    """rfid_repair::flips -> the indices of the reversed decisions, ascending"""
+    w = int(rec["flips"]) & 0xFFFFFFFF
+    return [(w >> (8 * k)) & 0xFF for k in range(int(rec["n_flips"]))]
+
+
+def format_repair_summary(rows: np.ndarray) -> str:
+    """One line for one trace's EPC windows before the cut-off (Context.batch_window_repairs): how many failed their CRC, how
+    many of those were repaired, and how many of the repaired frames are a tag's of that trace's inventory."""
+    rows = np.asarray(rows)
+    failed = (rows["flags"] & 1) == 0
+    fixed = rows["n_flips"] > 0
+    return ("| failed EPC windows : %d  repaired : %d  of a tag in the inventory : %d\n" %
+            (int(failed.sum()), int(fixed.sum()), int((fixed & (rows["entry"] >= 0)).sum())))
+
+
+def format_repairs(repairs: np.ndarray, names: Sequence[str]) -> str:
+    """CSV text, one line per repaired window in the order of `repairs` (Context.batch_repair_fetch: by trace, then by seq):
+    file,epc,pc,seq,t_s,n_flips,flips,cost,known -- epc / pc of the REPAIRED frame, t_s = start / 400e3 as in the tracks CSV,
+    flips: the reversed decisions joined by +, cost with %.9g (a binary32 value survives the round trip), known: 1 when the
+    trace's inventory holds the repaired frame."""
+    lines = [REPAIRS_HEADER]
+    for r in repairs:
+        pc, epc = frame_fields(r["frame"])
+        lines.append("%s,%s,%04x,%d,%.9g,%d,%s,%.9g,%d" %
+                     (names[int(r["stream"])], epc, pc, int(r["seq"]), int(r["start"]) / TRACKS_RATE, int(r["n_flips"]),
+                      "+".join(map(str, repair_flips(r))), float(r["cost"]), 1 if int(r["entry"]) >= 0 else 0))
+    return "\n".join(lines) + "\n"
+
+
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -271,19 +319,24 @@ def main(argv=None) -> int:
     ap.add_argument("--quality", action="store_true",
                     help="one line per file on the SNR and decision margin of its EPC windows (built on the device); with --tracks the "
                          "CSV gains the columns snr_db,margin")
+    ap.add_argument("--repair", metavar="OUT.csv", default=None,
+                    help="search the CRC-failed EPC windows for one to three weak decisions whose reversal makes the frame pass "
+                         "(built on the device); one line per file, the repaired windows to this CSV file; implies --inventory")
     args = ap.parse_args(argv)
-    if args.tracks:
+    if args.tracks or args.repair:
         args.inventory = True
     dec = BatchDecoder(device=args.device, fixed_q=args.fixed_q, max_num_queries=args.max_queries)
     try:
         timing = {}
         stats, _, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
-                                            tracks=bool(args.tracks), quality=args.quality)
+                                            tracks=bool(args.tracks), quality=args.quality, repair=bool(args.repair))
         for i, (path, row) in enumerate(zip(args.files, stats)):
             print(path)
             print(format_results(row), end="")
             if args.quality:
                 print(format_quality(dec.ctx.batch_window_quality(i)), end="")
+            if args.repair:
+                print(format_repair_summary(dec.ctx.batch_window_repairs(i)), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
               (len(args.files), timing["raw_samples"] / 1e6, timing["total_s"], timing["h2d_s"], timing["gpu_s"]))
         if args.inventory:
@@ -300,6 +353,9 @@ def main(argv=None) -> int:
             reads, offsets = dec.last_tracks
             with open(args.tracks, "w") as f:
                 f.write(format_tracks(dec.last_inventory[0], reads, offsets, args.files, dec.last_quality if args.quality else None))
+        if args.repair:
+            with open(args.repair, "w") as f:
+                f.write(format_repairs(dec.last_repairs, args.files))
     finally:
         dec.close()
     return 0

@@ -393,6 +393,49 @@ class Context:
     def batch_quality_ms(self) -> float:
         return self._stage_ms(self._lib.rfid_batch_quality_ms)
 
+    def batch_plan_repair(self) -> None:
+        """Reserves the repair workspace of the current plan (behind batch_plan_inventory; a new plan or a new
+        batch_plan_inventory drops it, batch_plan_tracks / batch_plan_quality do not)."""
+        self._chk(self._lib.rfid_batch_plan_repair(self._h))
+
+    def batch_repair_enqueue(self) -> None:
+        """Asynchronous: the repair of the last pass, behind its inventory (rfid_batch_repair)."""
+        self._chk(self._lib.rfid_batch_repair(self._h))
+
+    def batch_repair_fetch(self) -> np.ndarray:
+        """-> capi.REPAIR_DTYPE records of the last batch_repair_enqueue (synchronises): the repaired windows only
+        (n_flips > 0), ordered by (stream, seq)."""
+        return self._sized_fetch(self._lib.rfid_batch_get_repairs, capi.REPAIR_DTYPE)
+
+    def batch_repair(self) -> np.ndarray:
+        """The CRC-failed EPC windows of the last pass that reversing one to three of their eight weakest decisions makes
+        pass, built on the device behind batch_inventory(): see batch_repair_fetch.  A repair is not a read: `entry` says
+        whether the trace's inventory holds the repaired frame."""
+        self.batch_repair_enqueue()
+        return self.batch_repair_fetch()
+
+    def batch_window_repairs(self, stream: int, extra: int = 0) -> np.ndarray:
+        """One trace's row of the repair table (synchronises): the record of EVERY EPC window before the cut-off, in seq
+        order (n_windows_used // 2 of them), of the last batch_repair_enqueue.  extra > 0: up to that many of the table's
+        rows behind them as well (zeroed by the stage)."""
+        return self._sized_fetch(self._lib.rfid_batch_get_window_repairs, capi.REPAIR_DTYPE, head=(int(stream),),
+                                 extra=max(int(extra), 0))
+
+    def batch_repair_ms(self) -> float:
+        return self._stage_ms(self._lib.rfid_batch_repair_ms)
+
+    def repair_window(self, gated, result) -> np.ndarray:
+        """The repair search for ONE EPC window in host memory (rfid_repair_window): gated = its 1370 gated, DC-free
+        samples, result = its capi.RESULT_DTYPE record (what decoder_work returned).  -> one capi.REPAIR_DTYPE record."""
+        gated = np.ascontiguousarray(gated, dtype=np.complex64)
+        if len(gated) != 1370:
+            raise ValueError("an EPC window has 1370 samples")
+        res = np.zeros(1, dtype=capi.RESULT_DTYPE)
+        res[0] = result
+        out = np.zeros(1, dtype=capi.REPAIR_DTYPE)
+        self._chk(self._lib.rfid_repair_window(self._h, gated.ctypes.data, res.ctypes.data, out.ctypes.data))
+        return out[0]
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

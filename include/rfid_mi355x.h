@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 #define RFID_API __attribute__((visibility("default")))
-#define RFID_MI355X_ABI 5   /* see rfid_abi_version() */
+#define RFID_MI355X_ABI 6   /* see rfid_abi_version() */
 
 typedef enum rfid_status {
   RFID_OK = 0,
@@ -175,6 +175,40 @@ typedef struct rfid_read_quality {   /* 32 bytes */
   int32_t flags;                     /* bit 0: crc_ok of the window's result */
 } rfid_read_quality;
 
+/* what the repair stage (rfid_batch_repair, rfid_repair_window) finds for one EPC window: the cheapest way to make a frame
+ * whose CRC-16 failed pass by reversing up to RFID_REPAIR_MAX_FLIPS of its RFID_REPAIR_CANDIDATES weakest sign decisions.
+ * The decoder is differential (lib/tag_decoder_impl.cc:171-190: bit = "sign equals previous sign"), so reversing decision j
+ * toggles frame bits j and j + 1, and for j = 127 bit 127 only.  A repair is NOT a read: nothing else the library reports
+ * changes, and with 92 masks tried against a 16-bit CRC about one hopeless window in 700 is "repaired" by chance -- `entry`
+ * says whether the repaired frame is one the same trace's inventory already holds.
+ * THE DEFINITION (the contract; binary32 throughout, every operation rounded by itself, no fused multiply-add), for an EPC
+ * window with seq < n_windows_used and crc_ok == 0:
+ *   1. r_j, j = 0 .. 127, exactly as in the rfid_read_quality definition above (from the window's own result h_re, h_im, T,
+ *      index and s[i] = y[start + i] - dc); a_j = |r_j|; the frame bits b are rfid_decode_result::bits.
+ *   2. candidates c_0 .. c_7: the RFID_REPAIR_CANDIDATES decisions with the smallest (a_j, j) in that order -- a compared as
+ *      binary32 values, the smaller j first on equal a.
+ *   3. for every mask m in 1 .. 255 with at most RFID_REPAIR_MAX_FLIPS bits set: frame(m) = b XOR the toggles of all c_i with
+ *      bit i of m set (two neighbouring candidates toggle the bit they share twice).
+ *   4. m passes when the reference's check_crc (lib/tag_decoder_impl.cc:401-445) accepts frame(m).
+ *   5. cost(m) = ((0.0f + a_{c_i1}) + a_{c_i2}) + a_{c_i3}, i ascending.  The winner is the passing mask with the smallest
+ *      cost (binary32 <), the smaller m on equal cost.
+ * A window with a non-finite sample: unspecified, as its decoding is. */
+#define RFID_REPAIR_CANDIDATES 8
+#define RFID_REPAIR_MAX_FLIPS 3
+typedef struct rfid_repair {         /* 48 bytes */
+  int32_t  stream, seq;              /* the EPC window (rfid_window::stream / seq) */
+  int32_t  start;                    /* rfid_window::start of that window */
+  int32_t  flags;                    /* bit 0: crc_ok of the window's result (then nothing is searched);
+                                        bit 1: this trace's inventory overflowed, entry not looked up */
+  int32_t  n_flips;                  /* 0: not repaired; 1 .. 3: decisions reversed */
+  int32_t  flips;                    /* byte k (k < n_flips): decision index j of the k-th flip, ascending j;
+                                        unused bytes 0xFF; -1 when n_flips == 0 */
+  float    cost;                     /* cost of the winner; 0.0f when n_flips == 0 */
+  int32_t  entry;                    /* index into THIS trace's inventory list (as rfid_tag_read::entry) of the entry whose
+                                        128 frame bits equal the repaired frame; -1: none, or n_flips == 0 */
+  uint32_t frame[4];                 /* the repaired frame, packed as rfid_decode_result::bits; zeros when n_flips == 0 */
+} rfid_repair;
+
 /* timing of the last rfid_batch_* pass, from HIP events on the ctx stream */
 typedef struct rfid_batch_timing {
   float mf_ms, gate_ms, decode_ms, stats_ms; /* kernel time per pass (summed over the launches of a pass) */
@@ -229,7 +263,7 @@ RFID_API const char *rfid_strerror(int status);
 RFID_API const char *rfid_last_error(const rfid_ctx *ctx);
 RFID_API const char *rfid_version(void);
 /* RFID_MI355X_ABI of the library that was loaded: it changes whenever a struct of this header changes size or layout
- * (4: rfid_ls_report has 13 fields since round 3; 5: its last field is dc_finished since round 6).  A caller built against another value must not pass structs. */
+ * (4: rfid_ls_report has 13 fields since round 3; 5: its last field is dc_finished since round 6; 6: rfid_repair and the repair stage).  A caller built against another value must not pass structs. */
 RFID_API int rfid_abi_version(void);
 /* device self-test of the wave-level primitives the kernels rely on (DPP wave shift,
  * IEEE division, double sqrt).  0 = all good, >0 = number of failing checks. */
@@ -543,6 +577,40 @@ RFID_API int rfid_batch_get_quality(rfid_ctx *ctx, rfid_read_quality *q, int64_t
 RFID_API int rfid_batch_get_window_quality(rfid_ctx *ctx, int stream, rfid_read_quality *q, int64_t cap, int64_t *n);
 /* synchronises; device time of the last rfid_batch_quality (HIP events), from its first launch to the end of its last */
 RFID_API int rfid_batch_quality_ms(rfid_ctx *ctx, float *ms);
+/* ---- (2e) batch repair: CRC-failed EPC frames recovered from their weakest decisions, built on the device ------------- */
+/* Behind the inventory of a pass: one rfid_repair (see its definition above) per EPC window with seq < n_windows_used in a
+ * device table [n_streams][ceil(wmax / 2)] (row = seq >> 1; the rows of a trace behind its cut-off are zeroed: the table's
+ * bytes repeat from pass to pass), and the records with n_flips > 0 once more as ONE array ordered by (stream, seq).  Nothing
+ * else a pass reports changes: results, statistics, inventory, tracks and quality know nothing of a repair.
+ * rfid_batch_plan_repair reserves both (2 x 48 bytes per possible EPC window) and the counts and offsets between them.
+ * RFID_ERR_STATE without an inventory workspace; RFID_ERR_HIP when the allocation fails (the plan and every other workspace
+ * stay usable).  A new rfid_batch_plan or rfid_batch_plan_inventory drops it; it neither needs nor drops the tracks and
+ * quality workspaces, and rfid_batch_plan_tracks / rfid_batch_plan_quality do not drop it. */
+RFID_API int rfid_batch_plan_repair(rfid_ctx *ctx);
+/* enqueues the repair of the LAST pass behind its inventory (asynchronous, no host synchronisation).  RFID_ERR_STATE: no
+ * repair workspace, or no rfid_batch_inventory was enqueued since the last pass.  A side branch: rfid_batch_tracks and
+ * rfid_batch_quality may be enqueued before or behind it.  It reads that pass's matched-filter output, window table, results,
+ * statistics and inventory on the context's main stream and has rfid_batch_quality's duties there: with two result sets
+ * alternating it reads the set of that pass, and it records the long-stream front end's "free" event of the matched-filter
+ * buffer again behind its own launches. */
+RFID_API int rfid_batch_repair(rfid_ctx *ctx);
+/* synchronises; the records with n_flips > 0 of the last rfid_batch_repair, ordered by (stream, seq): every place is
+ * computed, the same pass gives the same bytes.  RFID_ERR_CAPACITY: cap too small (nothing lost: *n says how many there
+ * are, call again; out may be NULL with cap = 0).  An overflowed inventory is NOT an error here: the records of such a trace
+ * carry flag bit 1 and entry = -1. */
+RFID_API int rfid_batch_get_repairs(rfid_ctx *ctx, rfid_repair *out, int64_t cap, int64_t *n);
+/* synchronises; one trace's row of the table: every EPC window before the cut-off in seq order, verified, repaired or not:
+ * *n = n_windows_used / 2.  cap as rfid_batch_get_window_quality: RFID_ERR_CAPACITY when cap < *n (nothing is copied; out may
+ * be NULL with cap = 0); with cap > *n the zeroed rows behind *n are copied too, up to min(cap, ceil(wmax / 2)) in all. */
+RFID_API int rfid_batch_get_window_repairs(rfid_ctx *ctx, int stream, rfid_repair *out, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_repair (HIP events), from its first launch to the end of its last */
+RFID_API int rfid_batch_repair_ms(rfid_ctx *ctx, float *ms);
+/* the same search for ONE window in host memory: the per-call form (as rfid_decoder_work) for callers that work block by
+ * block.  gated: the window's 1 370 gated, DC-free samples (what rfid_gate_work wrote / rfid_decoder_work read); res: the
+ * result rfid_decoder_work gave for it (type RFID_DECODE_EPC, else RFID_ERR_INVALID).  One launch of the batch kernel's
+ * device function, synchronising.  out: stream = seq = start = 0, entry = -1; flags bit 0 = res->crc_ok (then nothing is
+ * searched). */
+RFID_API int rfid_repair_window(rfid_ctx *ctx, const rfid_cf32 *gated, const rfid_decode_result *res, rfid_repair *out);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
