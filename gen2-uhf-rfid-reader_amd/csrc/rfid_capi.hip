@@ -77,6 +77,9 @@ struct RfidKnobs {
   int inventory_slots = 0; // RFID_INVENTORY_SLOTS   2..1024 (a power of two): table slots per trace of the inventory stage, read by rfid_batch_plan_inventory (0: the next power of two >= 2 x max_tags_per_trace).  A small table makes frames collide: the stage's later rounds
 };
 
+// the timing events of a pass: stage i of the four took the time from event i to event i + 1
+enum { EV_MF_BEGIN, EV_MF_END, EV_GATE_END, EV_DECODE_END, EV_STATS_END, EV_COUNT };
+
 struct rfid_ctx {
   rfid_params prm;
   RfidKnobs knobs;
@@ -100,7 +103,7 @@ struct rfid_ctx {
                                   // output buffer the first launches of pass k + 1 -- the fused first pass: they touch the raw samples,
                                   // y and the work space only -- run on stream2 beside the rest of pass k; the two are used alternately
   bool ls2_mark_failed = false;   // (scratch of ls_enqueue's call-back)
-  bool y_touched = false;         // work outside that protocol has used c->d_y on the main stream since the last such pass
+  bool y_touched = false;         // work outside that protocol has used c->cur.d_y on the main stream since the last such pass
   Ls2Ctl *ls2_host = nullptr;     // page-locked copy of the control block of the last pass (report) + consumed[0]
   Ls2Ctl *d_ls2_ctl = nullptr;    // the control block of the last pass that ran the front end (device), else nullptr
   int ls2_P = 0;                  // its nominal piece length
@@ -244,53 +247,50 @@ struct rfid_ctx {
   int B = 0;        // traces the next pass processes (rfid_batch_set_streams), <= B_plan
   int B_plan = 0;   // traces the workspace was planned for; 0 = no plan
   int64_t max_raw = 0, y_stride = 0;
-  float2 *d_y = nullptr;
-  float2 *y_view = nullptr;       // (ymode stream) where the current pass's decimated samples lie instead of d_y
-  float2 *y() const { return y_view ? y_view : d_y; }
-  GateState *d_gstate = nullptr;
-  rfid_window *d_wtab = nullptr, *d_flat = nullptr;
-  int wmax = 0, flat_cap = 0;
-  int *d_wcount = nullptr, *d_flat_count = nullptr;
-  int *d_ticket = nullptr;   // RN16 pack counters of the decoder launches (two, used alternately)
-  int ticket_flip = 0;
-  rfid_decode_result *d_res = nullptr;
-  int *d_sum = nullptr;                          // plans of few, long traces: a one-word summary per result for the statistics kernel
-  const rfid_decode_result *sum_of = nullptr;    // (rfid_kernels.hpp, stats_summary()); sum_of: the result table they were last written for
-  rfid_scores *d_scores = nullptr;
-  rfid_stream_stats *d_stats = nullptr;
-  const int64_t *d_lens = nullptr;  // of the last rfid_batch_mf
-  int64_t last_n_raw = 0;
-  int decode_grid = 0;
-  int n_cus = 256;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  bool ev_valid[5] = {false, false, false, false, false};
-  // overlapped front end: matched filter on `stream`, gate scan on `stream2`, time-chunked
-  static const int MAX_CHUNKS = 16;
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ev_mf[MAX_CHUNKS + 1], ev_gate[2 * MAX_CHUNKS], ev_pass = nullptr, ev_front_end = nullptr;
-  // Decoder + statistics of pass k beside the front end of pass k + 1 (rfid_batch_process, fused front end): a second set
-  // of everything the front end writes and the decoder reads (the matched-filter output and the window / result tables), used
-  // alternately; the decoder and the statistics kernel of a pass run on stream2 behind that pass's front end.  Allocated by
-  // rfid_batch_plan when the device has the room (RFID_OVERLAP=0: never).
+  // Everything the front end of a pass writes and its decoder reads: the matched-filter output and the window / result
+  // tables.  `cur` is the set of the current (last) pass.  `alt`: a second set (rfid_batch_plan, RFID_OVERLAP=2, where the
+  // device has the room), used alternately -- decoder + statistics of pass k on stream2 behind that pass's front end, beside
+  // the front end of pass k + 1 (pass_fused); or its d_y alone, for the long-stream passes (pass_long_stream).
   struct ResultSet {
     float2 *d_y = nullptr;
     rfid_window *d_wtab = nullptr, *d_flat = nullptr;
     int *d_wcount = nullptr, *d_flat_count = nullptr;
     rfid_decode_result *d_res = nullptr;
     rfid_stream_stats *d_stats = nullptr;
-  } alt;
-  bool alt_have = false;
+  } cur, alt;
+  float2 *y_view = nullptr;       // (ymode stream) where the current pass's decimated samples lie instead of cur.d_y
+  float2 *y() const { return y_view ? y_view : cur.d_y; }
+  GateState *d_gstate = nullptr;
+  int wmax = 0, flat_cap = 0;
+  int *d_ticket = nullptr;   // RN16 pack counters of the decoder launches (two, used alternately)
+  int ticket_flip = 0;
+  int *d_sum = nullptr;                          // plans of few, long traces: a one-word summary per result for the statistics kernel
+  const rfid_decode_result *sum_of = nullptr;    // (rfid_kernels.hpp, stats_summary()); sum_of: the result table they were last written for
+  rfid_scores *d_scores = nullptr;
+  const int64_t *d_lens = nullptr;  // of the last rfid_batch_mf
+  int64_t last_n_raw = 0;
+  int decode_grid = 0;
+  int n_cus = 256;
+  // the timing events of a pass (rfid_batch_timing_get), recorded by ev_mark
+  hipEvent_t ev[EV_COUNT] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool ev_valid[EV_COUNT] = {false, false, false, false, false};
+  // overlapped front end: matched filter on `stream`, gate scan on `stream2`, time-chunked
+  static const int MAX_CHUNKS = 16;
+  hipStream_t stream2 = nullptr;
+  hipEvent_t ev_mf[MAX_CHUNKS + 1], ev_gate[2 * MAX_CHUNKS], ev_pass = nullptr, ev_front_end = nullptr;
+  // the hand-over of the two result sets (set_take_next / set_tails_on_stream2 / join_tails)
+  bool alt_have = false;                    // `alt` is a whole second set
   void *plan_blk = nullptr, *alt_blk = nullptr;   // the two allocations behind the plan's buffers (rfid_batch_plan)
   hipEvent_t ev_fe_done = nullptr, ev_tail_done[2] = {nullptr, nullptr};
   bool tail_recorded[2] = {false, false};   // ev_tail_done[i] has been recorded (set i's decoder / statistics were enqueued on stream2)
-  int set_idx = 0;                          // which of the two sets c->d_* currently name
+  int set_idx = 0;                          // which of the two sets c->cur currently names
   // (long-stream passes: only the matched-filter output alternates -- the filter of pass k + 1 beside the front end of pass k)
   void *alt_y_blk = nullptr;                // a second matched-filter output buffer alone (plans too small for a whole second set)
   hipEvent_t ev_y_free[2] = {nullptr, nullptr};
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
-  // ---- the stages behind a pass: inventory, tracks, quality.  What the three share ----
+  // ---- the stages behind a pass: inventory, tracks, quality, repair.  What the four share ----
   struct Stage {
     void *blk = nullptr;              // one allocation, carved up (stage_alloc)
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
@@ -461,7 +461,7 @@ void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
 // `stage` and everything behind it no longer belong to the last pass
 void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
 
-// ---- what the inventory, tracks and quality stages share on the host ----
+// ---- what the inventory, tracks, quality and repair stages share on the host ----
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void stage_free(rfid_ctx::Stage &st) {
@@ -524,6 +524,29 @@ int stage_fetch_head(rfid_ctx *c, const char *fn, const int *d_reads_head, int64
   return RFID_OK;
 }
 
+// One trace's rows of a stage's table (quality, repair: one record per EPC window, `rows` of them per trace).  *n: the EPC
+// windows before the cut-off (d_nrows).  RFID_ERR_CAPACITY under `fn`'s name when `cap` is smaller than that; else up to
+// `cap` rows are copied.
+int stage_fetch_rows(rfid_ctx *c, const char *fn, const int *d_nrows, const void *table, size_t record_bytes, int rows, int n_streams,
+                     int stream, void *out, int64_t cap, int64_t *n) {
+  if (stream < 0 || stream >= n_streams) return RFID_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  int nrows = 0;
+  HIPCHK(c, hipMemcpyAsync(&nrows, d_nrows + stream, sizeof(nrows), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n = nrows;
+  if (nrows > cap) {
+    snprintf(c->err, sizeof(c->err), "%s: cap is smaller than the number of EPC windows", fn);
+    return RFID_ERR_CAPACITY;
+  }
+  const int64_t take = (cap < rows) ? cap : rows;          // (the zeroed rows behind the cut-off too, as far as there is room)
+  if (take > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, (const char *)table + (size_t)stream * (size_t)rows * record_bytes, record_bytes * (size_t)take, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return RFID_OK;
+}
+
 // ---- launch geometry of the kernels that take one workgroup per trace (statistics, inventory, tracks) ----
 // one wave per trace; sixteen when a trace can hold thousands of windows (few long traces)
 static_assert(STATS_MAX_WAVES == INV_MAX_WAVES, "one rule for the three kernels");
@@ -531,6 +554,122 @@ bool wide_traces(const rfid_ctx *c) { return c->wmax > 2048; }
 dim3 trace_block(const rfid_ctx *c) { return dim3(wide_traces(c) ? 64 * INV_MAX_WAVES : 64); }
 // the one workgroup of an offsets scan over n traces (scan_share / scan_partials, csrc/rfid_inventory.hpp)
 dim3 scan_block(int n) { return dim3((unsigned)((n >= INV_SCAN_THREADS) ? INV_SCAN_THREADS : ((n + 63) & ~63))); }
+// a persistent grid: one single-wave workgroup per item, at most `most` of them (and one for nothing)
+dim3 persistent_grid(int64_t items, int64_t most) { return dim3((unsigned)(items < most ? (items > 0 ? items : 1) : most)); }
+// the gate scan's and the fused front end's: GATE_STREAMS_PER_WG traces per workgroup
+dim3 gate_grid(const rfid_ctx *c) { return dim3((unsigned)((c->B + GATE_STREAMS_PER_WG - 1) / GATE_STREAMS_PER_WG)); }
+
+// ---- the argument blocks of the batch front end: built here, a launch site sets only what it does differently ----
+// rows of raw samples whose float4 loads are aligned: an even stride from a 16-byte aligned base
+int rows_vec_ok(const void *d_raw, int64_t raw_stride) { return ((raw_stride & 1) == 0 && (((uintptr_t)d_raw) & 15) == 0) ? 1 : 0; }
+// the matched filter over the whole of every trace (c->d_lens), from d_raw into the current set's y
+MfArgs mf_args(const rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64_t n_raw) {
+  MfArgs a;
+  a.x = (const float2 *)d_raw; a.x_stride = raw_stride; a.n_raw = n_raw; a.lens = c->d_lens;
+  a.n_out = n_raw / DECIM; a.in_off = -(NTAPS - 1);
+  a.vec_ok = rows_vec_ok(d_raw, raw_stride);
+  a.y = c->cur.d_y; a.y_stride = c->y_stride; a.tile0 = 0; a.stream0 = 0;
+  return a;
+}
+// the gate scan over all n_dec samples of every trace, from the current set's y into its tables; a site sets what differs:
+// skip_if, the raw samples of the fused front end (raw*, y_w, single_step), pos0 / chunk_len of a time chunk
+GateArgs gate_args(const rfid_ctx *c, int64_t n_dec) {
+  GateArgs a = {};
+  a.y = c->cur.d_y; a.y_stride = c->y_stride; a.n_dec = n_dec; a.lens = c->d_lens;
+  a.pos0 = 0; a.chunk_len = n_dec;
+  a.state = c->d_gstate; a.n_streams = c->B; a.wtab = c->cur.d_wtab; a.wmax = c->wmax; a.wcount = c->cur.d_wcount;
+  a.flat = c->cur.d_flat; a.flat_count = c->cur.d_flat_count; a.flat_cap = c->flat_cap; a.mode = 0;
+  return a;
+}
+// A matched-filter kernel over all traces of the batch, tiles_x workgroups per trace: one launch per 65 535 traces (the
+// gridDim.y limit).  The argument block names the kernel.
+void mf_launch(dim3 grid, hipStream_t stream, const MfArgs &a) { hipLaunchKernelGGL(mf_boxcar25_decim5_kernel, grid, dim3(MF_THREADS), 0, stream, a); }
+void mf_launch(dim3 grid, hipStream_t stream, const MfFallbackArgs &f) { hipLaunchKernelGGL(mf_fallback_kernel, grid, dim3(MF_THREADS), 0, stream, f); }
+int &mf_stream0(MfArgs &a) { return a.stream0; }
+int &mf_stream0(MfFallbackArgs &f) { return f.m.stream0; }
+template <typename Args>
+int launch_mf_rows(rfid_ctx *c, hipStream_t stream, Args a, int64_t tiles_x) {
+  for (int s0 = 0; s0 < c->B && tiles_x > 0; s0 += 65535) {
+    mf_stream0(a) = s0;
+    const int ns = (c->B - s0 < 65535) ? (c->B - s0) : 65535;
+    mf_launch(dim3((unsigned)tiles_x, (unsigned)ns), stream, a);
+    HIPCHK(c, hipGetLastError());
+  }
+  return RFID_OK;
+}
+
+// ---- the timing events of a pass ----
+hipError_t ev_mark(rfid_ctx *c, int i, hipStream_t stream) {
+  c->ev_valid[i] = true;
+  return hipEventRecord(c->ev[i], stream);
+}
+
+// ---- hand-over of the matched-filter output between long-stream passes (pass_long_stream) ----
+// With a second output buffer (alt.d_y) and a second work space, the first launches of pass k + 1 run on stream2 beside the
+// rest of pass k: the buffers alternate (y_idx: which one cur.d_y names), and a buffer is written again only when the pass
+// before last and everything that read its y are through with it (ev_y_free[i], valid while y_recorded[i]).  y_touched: work
+// outside this protocol has used a buffer on the main stream since the last such pass -- the next one waits for all of it.
+// (An error between y_take_ahead and y_pass_done may leave the buffers / work spaces swapped without a pass behind them:
+// HIPCHK_T sets y_touched, whichever buffers the next pass gets.)
+int y_take_ahead(rfid_ctx *c) {
+  std::swap(c->cur.d_y, c->alt.d_y);
+  c->y_idx ^= 1;
+  if (c->y_touched) {   // (something outside this protocol used a buffer on the main stream: wait for all of it)
+    HIPCHK_T(c, hipEventRecord(c->ev_pass, c->stream));
+    HIPCHK_T(c, hipStreamWaitEvent(c->stream2, c->ev_pass, 0));
+    c->y_touched = false;
+  }
+  if (c->y_recorded[c->y_idx]) {
+    HIPCHK_T(c, hipStreamWaitEvent(c->stream2, c->ev_y_free[c->y_idx], 0));
+    c->y_recorded[c->y_idx] = false;
+  }
+  return RFID_OK;
+}
+// the pass does not run ahead after all: the buffers go back, the pass runs on the main stream alone
+void y_give_back(rfid_ctx *c) {
+  std::swap(c->cur.d_y, c->alt.d_y);
+  c->y_idx ^= 1;
+  c->y_touched = true;
+}
+// everything of the pass is enqueued
+int y_pass_done(rfid_ctx *c, bool ahead) {
+  if (!ahead) { c->y_touched = true; return RFID_OK; }
+  HIPCHK_T(c, hipEventRecord(c->ev_y_free[c->y_idx], c->stream));
+  c->y_recorded[c->y_idx] = true;
+  return RFID_OK;
+}
+// a stage behind the pass has read its y (quality, repair): the pass after next gets this buffer, its first launch runs on the
+// second stream as soon as the buffer's event has come -- the event is recorded again, behind the launches that read the buffer
+int y_read_again(rfid_ctx *c) {
+  if (c->y_recorded[c->y_idx]) HIPCHK(c, hipEventRecord(c->ev_y_free[c->y_idx], c->stream));
+  return RFID_OK;
+}
+
+// ---- hand-over of the two result sets between fused passes (pass_fused) ----
+// this pass works on the set the pass before last used; its decoder and statistics (stream2) must be through with it
+int set_take_next(rfid_ctx *c) {
+  std::swap(c->cur, c->alt);
+  c->set_idx ^= 1;
+  if (c->tail_recorded[c->set_idx]) {
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_tail_done[c->set_idx], 0));
+    c->tail_recorded[c->set_idx] = false;
+  }
+  return RFID_OK;
+}
+// decoder + statistics of this pass on stream2, behind this front end; the next pass's front end does not wait for them
+int set_tails_on_stream2(rfid_ctx *c) {
+  HIPCHK(c, hipEventRecord(c->ev_fe_done, c->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fe_done, 0));
+  c->tail_stream = c->stream2;
+  c->ev_valid[EV_GATE_END] = false;           // (re-recorded on stream2: the decoder's time starts when it can start)
+  int rc = rfid_batch_decode(c, 0);
+  if (!rc) rc = rfid_batch_stats(c);
+  c->tail_stream = nullptr;
+  if (rc) return rc;
+  HIPCHK(c, hipEventRecord(c->ev_tail_done[c->set_idx], c->stream2));
+  c->tail_recorded[c->set_idx] = true;
+  return RFID_OK;
+}
 
 void free_quality(rfid_ctx *c) {
   stage_free(c->qual);
@@ -569,10 +708,8 @@ void free_plan(rfid_ctx *c) {
   c->y_recorded[0] = c->y_recorded[1] = false;
   c->y_idx = 0;
   c->y_touched = false;
-  c->d_y = nullptr; c->d_gstate = nullptr; c->d_wtab = nullptr; c->d_flat = nullptr;
-  c->d_wcount = nullptr; c->d_flat_count = nullptr; c->d_res = nullptr; c->d_scores = nullptr;
-  c->d_stats = nullptr;
-  c->alt = rfid_ctx::ResultSet();
+  c->cur = c->alt = rfid_ctx::ResultSet();
+  c->d_gstate = nullptr; c->d_scores = nullptr;
   c->alt_have = false;
   c->tail_recorded[0] = c->tail_recorded[1] = false;
   c->set_idx = 0;
@@ -661,10 +798,10 @@ struct LsOpts {
   bool ahead = false;       // (fused first pass) its launches on stream2 and in the work space the pass before did not use; the rest of the
                             // list on the main stream behind them
   // the fused first pass (ls2_front_kernel): the raw samples in HBM -- the matched filter runs inside the front end's first
-  // launch and writes c->d_y; nullptr: c->d_y holds the filter's output already
+  // launch and writes c->cur.d_y; nullptr: c->cur.d_y holds the filter's output already
   const void *raw = nullptr; int64_t raw_stride = 0;
 };
-// Enqueues one pass of the front end over c->d_y (n_dec decimated samples per trace, c->d_lens).  *enqueued = 0: not
+// Enqueues one pass of the front end over c->cur.d_y (n_dec decimated samples per trace, c->d_lens).  *enqueued = 0: not
 // applicable here (traces too short, no work space) -- nothing was launched.  Whether the pass produced the window
 // tables is known on the device only (Ls2Ctl::ok); the caller enqueues the sequential scan behind it with
 // GateArgs::skip_if = &ctl->ok, or synchronises and looks at c->ls2_host.
@@ -703,14 +840,14 @@ int ls_enqueue(rfid_ctx *c, int64_t n_dec, const LsOpts &opt, int *enqueued) {
   a.y = c->y(); a.y_stride = c->y_stride; a.lens = c->d_lens; a.n_dec = n_dec; a.n_streams = c->B;
   if (ahead) std::swap(c->ls2_ws, c->ls2_ws_alt);   // (alternating with the matched-filter output buffers: nothing below returns without a pass)
   ls2_bind(a, (char *)c->ls2_ws.p, L, geo);
-  a.wtab = c->d_wtab; a.wmax = c->wmax; a.wcount = c->d_wcount; a.flat = c->d_flat; a.flat_count = c->d_flat_count; a.flat_cap = c->flat_cap;
+  a.wtab = c->cur.d_wtab; a.wmax = c->wmax; a.wcount = c->cur.d_wcount; a.flat = c->cur.d_flat; a.flat_count = c->cur.d_flat_count; a.flat_cap = c->flat_cap;
   a.carry = opt.carry ? c->d_gstate : nullptr; a.carry_out = opt.carry ? c->d_gstate : nullptr;
   a.hold_last = opt.hold_last ? 1 : 0; a.force = opt.force ? 1 : 0;
   if (opt.raw) {
     a.fused = 1;
     a.raw = (const float2 *)opt.raw; a.raw_stride = opt.raw_stride;
-    a.raw_vec_ok = ((opt.raw_stride & 1) == 0 && (((uintptr_t)opt.raw) & 15) == 0) ? 1 : 0;
-    a.y_w = c->d_y;
+    a.raw_vec_ok = rows_vec_ok(opt.raw, opt.raw_stride);
+    a.y_w = c->cur.d_y;
   }
   ls2_stream = ahead ? c->stream2 : c->stream;
   // The first pass's one-wave workgroups would take every wave slot of the chip; launched beside the rest of the pass before
@@ -734,7 +871,7 @@ int ls_enqueue(rfid_ctx *c, int64_t n_dec, const LsOpts &opt, int *enqueued) {
       // whose decoder reads the list counters that this pass's window assembly counts up from zero)
       if (ls2_stream == cc->stream2) {
         if (hipEventRecord(cc->ev_fe_done, cc->stream2) != hipSuccess || hipStreamWaitEvent(cc->stream, cc->ev_fe_done, 0) != hipSuccess ||
-            hipMemsetAsync(cc->d_flat_count, 0, 2 * sizeof(int), cc->stream) != hipSuccess) cc->ls2_mark_failed = true;
+            hipMemsetAsync(cc->cur.d_flat_count, 0, 2 * sizeof(int), cc->stream) != hipSuccess) cc->ls2_mark_failed = true;
         ls2_stream = cc->stream;
       }
       return;
@@ -1007,7 +1144,7 @@ int rfid_ctx_create(const rfid_params *p, int device, rfid_ctx **out) {
   do {
     if (hipSetDevice(device) != hipSuccess) { rc = RFID_ERR_NO_DEVICE; break; }
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { rc = RFID_ERR_HIP; break; }
-    for (int i = 0; i < 5; ++i)
+    for (int i = 0; i < EV_COUNT; ++i)
       if (hipEventCreate(&c->ev[i]) != hipSuccess) { rc = RFID_ERR_HIP; break; }
     if (rc) break;
     if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess) { rc = RFID_ERR_HIP; break; }
@@ -1063,8 +1200,8 @@ int rfid_ctx_destroy(rfid_ctx *c) {
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->ls2_host) (void)hipHostFree(c->ls2_host);
-  for (int i = 0; i < 5; ++i)
-    if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
+  for (hipEvent_t e : c->ev)
+    if (e) (void)hipEventDestroy(e);
   for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
@@ -1285,17 +1422,17 @@ int rfid_batch_plan(rfid_ctx *c, int n_streams, int64_t max_raw) {
                sz_c = up256(sizeof(int) * (size_t)n_streams), sz_fc = 256, sz_r = up256(sizeof(rfid_decode_result) * (size_t)c->flat_cap),
                sz_sc = up256(sizeof(rfid_scores) * (size_t)c->flat_cap), sz_st = up256(sizeof(rfid_stream_stats) * (size_t)n_streams);
   const size_t sz_set = sz_y + sz_w + sz_f + sz_c + sz_fc + sz_r + sz_st;     // what a result set holds
-  auto bind_set = [&](char *b, float2 *&y, rfid_window *&w, rfid_window *&f, int *&wc, int *&fc, rfid_decode_result *&r, rfid_stream_stats *&st) {
-    y = (float2 *)b; b += sz_y; w = (rfid_window *)b; b += sz_w; f = (rfid_window *)b; b += sz_f; wc = (int *)b; b += sz_c;
-    fc = (int *)b; b += sz_fc; r = (rfid_decode_result *)b; b += sz_r; st = (rfid_stream_stats *)b; b += sz_st;
+  auto bind_set = [&](char *b, rfid_ctx::ResultSet &s) {
+    s.d_y = (float2 *)b; b += sz_y; s.d_wtab = (rfid_window *)b; b += sz_w; s.d_flat = (rfid_window *)b; b += sz_f; s.d_wcount = (int *)b; b += sz_c;
+    s.d_flat_count = (int *)b; b += sz_fc; s.d_res = (rfid_decode_result *)b; b += sz_r; s.d_stats = (rfid_stream_stats *)b; b += sz_st;
     return b;
   };
   e = hipMalloc(&c->plan_blk, sz_set + sz_g + sz_sc);
   if (e == hipSuccess) {
-    char *b = bind_set((char *)c->plan_blk, c->d_y, c->d_wtab, c->d_flat, c->d_wcount, c->d_flat_count, c->d_res, c->d_stats);
+    char *b = bind_set((char *)c->plan_blk, c->cur);
     c->d_gstate = (GateState *)b; b += sz_g;
     c->d_scores = (rfid_scores *)b;
-    e = hipMemset(c->d_wcount, 0, sz_c + sz_fc);   // (the window counts and, right behind them, the two list counters)
+    e = hipMemset(c->cur.d_wcount, 0, sz_c + sz_fc);   // (the window counts and, right behind them, the two list counters)
   }
   if (e != hipSuccess) {
     (void)hipGetLastError();   // clear the sticky allocation error
@@ -1320,7 +1457,7 @@ int rfid_batch_plan(rfid_ctx *c, int n_streams, int64_t max_raw) {
     if (c->knobs.overlap >= 2 && n_streams >= 64 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need < free_b / 8) {
       hipError_t e2 = hipMalloc(&c->alt_blk, sz_set);
       if (e2 == hipSuccess) {
-        bind_set((char *)c->alt_blk, c->alt.d_y, c->alt.d_wtab, c->alt.d_flat, c->alt.d_wcount, c->alt.d_flat_count, c->alt.d_res, c->alt.d_stats);
+        bind_set((char *)c->alt_blk, c->alt);
         e2 = hipMemset(c->alt.d_wcount, 0, sz_c + sz_fc);
       }
       if (e2 == hipSuccess) c->alt_have = true;
@@ -1365,7 +1502,7 @@ int rfid_batch_plan(rfid_ctx *c, int n_streams, int64_t max_raw) {
   }
   // persistent decoders: the EPC kernel holds 18.6 KiB of LDS per single-wave workgroup -> 8 per CU
   c->decode_grid = c->n_cus * 8;
-  for (int i = 0; i < 5; ++i) c->ev_valid[i] = false;
+  for (bool &v : c->ev_valid) v = false;
   return RFID_OK;
 }
 
@@ -1390,23 +1527,12 @@ int rfid_batch_mf(rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64_t n_
 static int batch_mf_on(rfid_ctx *c, hipStream_t stream, const void *d_raw, int64_t raw_stride, int64_t n_raw, const void *d_lens) {
   c->d_lens = (const int64_t *)d_lens;
   c->last_n_raw = n_raw;
-  MfArgs a;
-  a.x = (const float2 *)d_raw; a.x_stride = raw_stride; a.n_raw = n_raw; a.lens = c->d_lens;
-  a.n_out = n_raw / DECIM; a.in_off = -(NTAPS - 1);
-  a.vec_ok = ((raw_stride & 1) == 0 && (((uintptr_t)d_raw) & 15) == 0) ? 1 : 0;
-  a.y = c->d_y; a.y_stride = c->y_stride; a.tile0 = 0; a.stream0 = 0;
+  const MfArgs a = mf_args(c, d_raw, raw_stride, n_raw);
   c->n_chunks_last = 0;
   c->fused_last = 0;
-  HIPCHK(c, hipEventRecord(c->ev[0], stream));
-  const int64_t tiles = (a.n_out + MF_TILE - 1) / MF_TILE;
-  for (int s0 = 0; s0 < c->B && tiles > 0; s0 += 65535) {   // gridDim.y limit
-    a.stream0 = s0;
-    const int ns = (c->B - s0 < 65535) ? (c->B - s0) : 65535;
-    hipLaunchKernelGGL(mf_boxcar25_decim5_kernel, dim3((unsigned)tiles, (unsigned)ns), dim3(MF_THREADS), 0, stream, a);
-    HIPCHK(c, hipGetLastError());
-  }
-  HIPCHK(c, hipEventRecord(c->ev[1], stream));
-  c->ev_valid[0] = c->ev_valid[1] = true;
+  HIPCHK(c, ev_mark(c, EV_MF_BEGIN, stream));
+  { int r = launch_mf_rows(c, stream, a, (a.n_out + MF_TILE - 1) / MF_TILE); if (r) return r; }
+  HIPCHK(c, ev_mark(c, EV_MF_END, stream));
   return RFID_OK;
 }
 
@@ -1418,20 +1544,14 @@ static int rfid_batch_gate_impl(rfid_ctx *c, const int *skip_if) {
   // fresh gate per trace (gate_impl ctor, gate_impl.cc:41-70): all-zero state; the kernel
   // arms n_samples_to_ungate for the first RN16 itself
   HIPCHK(c, hipMemsetAsync(c->d_gstate, 0, sizeof(GateState) * (size_t)c->B, c->stream));
-  if (!skip_if) HIPCHK(c, hipMemsetAsync(c->d_flat_count, 0, 2 * sizeof(int), c->stream));   // (else: zeroed before the front end)
-  GateArgs a = {};
+  if (!skip_if) HIPCHK(c, hipMemsetAsync(c->cur.d_flat_count, 0, 2 * sizeof(int), c->stream));   // (else: zeroed before the front end)
+  GateArgs a = gate_args(c, c->last_n_raw / DECIM);
   a.skip_if = skip_if;
-  a.y = c->d_y; a.y_stride = c->y_stride; a.n_dec = c->last_n_raw / DECIM; a.lens = c->d_lens;
-  a.pos0 = 0; a.chunk_len = a.n_dec;
-  a.state = c->d_gstate; a.n_streams = c->B; a.wtab = c->d_wtab; a.wmax = c->wmax; a.wcount = c->d_wcount;
-  a.flat = c->d_flat; a.flat_count = c->d_flat_count; a.flat_cap = c->flat_cap; a.mode = 0;
-  a.gated = nullptr; a.gated_cap = 0; a.io = nullptr;
   invalidate_from(c, rfid_ctx::CUR_STATS);
-  if (!c->ev_valid[1]) { HIPCHK(c, hipEventRecord(c->ev[1], c->stream)); c->ev_valid[1] = true; }
-  hipLaunchKernelGGL(gate_scan_kernel, dim3((unsigned)((c->B + GATE_STREAMS_PER_WG - 1) / GATE_STREAMS_PER_WG)), dim3(GATE_THREADS), 0, c->stream, a);
+  if (!c->ev_valid[EV_MF_END]) HIPCHK(c, ev_mark(c, EV_MF_END, c->stream));
+  hipLaunchKernelGGL(gate_scan_kernel, gate_grid(c), dim3(GATE_THREADS), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  c->ev_valid[2] = true;
+  HIPCHK(c, ev_mark(c, EV_GATE_END, c->stream));
   return RFID_OK;
 }
 int rfid_batch_gate(rfid_ctx *c) {
@@ -1444,14 +1564,14 @@ int rfid_batch_decode(rfid_ctx *c, int want_scores) {
   if (!c->B) return RFID_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   DecodeListArgs a;
-  a.y = c->y(); a.y_stride = c->y_stride; a.cap = c->flat_cap; a.res = c->d_res;
+  a.y = c->y(); a.y_stride = c->y_stride; a.cap = c->flat_cap; a.res = c->cur.d_res;
   a.scores = want_scores ? c->d_scores : nullptr; a.wmax = c->wmax;
   a.sum = c->alt_have ? nullptr : c->d_sum;   // (one array: not with two result sets in flight)
-  c->sum_of = a.sum ? c->d_res : nullptr;
+  c->sum_of = a.sum ? c->cur.d_res : nullptr;
   memcpy(a.t_cand, c->t_cand, sizeof(a.t_cand));
   hipStream_t ts = c->tail_stream ? c->tail_stream : c->stream;
   if (!c->tail_stream) { int rj = join_tails(c); if (rj) return rj; }
-  if (!c->ev_valid[2]) { HIPCHK(c, hipEventRecord(c->ev[2], ts)); c->ev_valid[2] = true; }
+  if (!c->ev_valid[EV_GATE_END]) HIPCHK(c, ev_mark(c, EV_GATE_END, ts));
   int grid = c->decode_grid;
   {   // (a small plan -- a stream call, a look-ahead pass -- holds few windows: no point in launching a chip's worth of waves)
     const int64_t most = ((int64_t)c->wmax * c->B + 2) / 3 + 1;
@@ -1461,16 +1581,15 @@ int rfid_batch_decode(rfid_ctx *c, int want_scores) {
   // one launch: EPC windows 3 per wavefront, then RN16 windows 4 per wavefront drawn from a counter
   DecodeAllArgs d;
   d.epc = a; d.rn16 = a;
-  d.epc.list = c->d_flat + c->flat_cap; d.epc.count = c->d_flat_count + 1;
-  d.rn16.list = c->d_flat; d.rn16.count = c->d_flat_count;
+  d.epc.list = c->cur.d_flat + c->flat_cap; d.epc.count = c->cur.d_flat_count + 1;
+  d.rn16.list = c->cur.d_flat; d.rn16.count = c->cur.d_flat_count;
   d.ticket = c->d_ticket + (c->ticket_flip & 1);        // (both zero after rfid_ctx_create; every launch zeroes the other one)
   d.ticket_next = c->d_ticket + ((c->ticket_flip & 1) ^ 1);
   c->ticket_flip ^= 1;
   invalidate_from(c, rfid_ctx::CUR_STATS);
   hipLaunchKernelGGL(decode_all_kernel, dim3((unsigned)grid), dim3(64), 0, ts, d);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev[3], ts));
-  c->ev_valid[3] = true;
+  HIPCHK(c, ev_mark(c, EV_DECODE_END, ts));
   return RFID_OK;
 }
 
@@ -1479,18 +1598,17 @@ int rfid_batch_stats(rfid_ctx *c) {
   if (!c->B) return RFID_ERR_STATE;
   HIPCHK(c, hipSetDevice(c->device));
   StatsArgs a;
-  a.res = c->d_res; a.wcount = c->d_wcount; a.wmax = c->wmax; a.n_streams = c->B;
-  a.sum = (c->d_sum && c->sum_of == c->d_res) ? c->d_sum : nullptr;   // (the summaries rfid_batch_decode left of THESE results)
+  a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.wmax = c->wmax; a.n_streams = c->B;
+  a.sum = (c->d_sum && c->sum_of == c->cur.d_res) ? c->d_sum : nullptr;   // (the summaries rfid_batch_decode left of THESE results)
   a.max_slot_number = (int)pow(2, c->prm.fixed_q);
   a.max_num_queries = c->prm.max_num_queries; a.number_unique_tags = c->prm.number_unique_tags;
-  a.out = c->d_stats;
+  a.out = c->cur.d_stats;
   hipStream_t ts = c->tail_stream ? c->tail_stream : c->stream;
   if (!c->tail_stream) { int rj = join_tails(c); if (rj) return rj; }
-  if (!c->ev_valid[3]) { HIPCHK(c, hipEventRecord(c->ev[3], ts)); c->ev_valid[3] = true; }
+  if (!c->ev_valid[EV_DECODE_END]) HIPCHK(c, ev_mark(c, EV_DECODE_END, ts));
   hipLaunchKernelGGL(stream_stats_kernel, dim3((unsigned)c->B), trace_block(c), 0, ts, a);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev[4], ts));
-  c->ev_valid[4] = true;
+  HIPCHK(c, ev_mark(c, EV_STATS_END, ts));
   mark_current(c, rfid_ctx::CUR_STATS);
   return RFID_OK;
 }
@@ -1528,7 +1646,7 @@ int rfid_batch_inventory(rfid_ctx *c) {
   // ran on the second stream: the main stream waits for them, and everything later on it waits for this
   { int rj = join_tails(c); if (rj) return rj; }
   InvArgs a;
-  a.res = c->d_res; a.wcount = c->d_wcount; a.stats = c->d_stats; a.wmax = c->wmax; a.n_streams = c->B;
+  a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats; a.wmax = c->wmax; a.n_streams = c->B;
   a.max_tags = v.max_tags; a.slots = v.slots; a.out = v.d_ent; a.counts = v.d_counts; a.overflow = v.d_over;
   InvPackArgs p;
   p.in = v.d_ent; p.counts = v.d_counts; p.overflow = v.d_over; p.n_streams = c->B; p.max_tags = v.max_tags;
@@ -1602,7 +1720,7 @@ int rfid_batch_tracks(rfid_ctx *c) {
   p.ent = v.d_ent; p.counts = v.d_counts; p.inv_head = v.d_head; p.n_streams = n; p.max_tags = v.max_tags;
   p.base = t.d_base; p.head = t.d_head; p.offsets = t.d_off;
   TrkArgs a;
-  a.res = c->d_res; a.wtab = c->d_wtab; a.wcount = c->d_wcount; a.stats = c->d_stats; a.wmax = c->wmax; a.n_streams = n;
+  a.res = c->cur.d_res; a.wtab = c->cur.d_wtab; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats; a.wmax = c->wmax; a.n_streams = n;
   a.ent = v.d_ent; a.counts = v.d_counts; a.ent_off = v.d_off; a.max_tags = v.max_tags; a.slots = v.slots;
   a.base = t.d_base; a.out = t.d_reads; a.cap = t.cap; a.offsets = t.d_off;
   { int r = stage_record(c, t, 0); if (r) return r; }
@@ -1673,15 +1791,14 @@ int rfid_batch_quality(rfid_ctx *c) {
   { int rj = join_tails(c); if (rj) return rj; }
   const int n = c->inv.n_streams;     // the traces the inventory and the tracks covered
   QualArgs a;
-  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->d_wtab; a.res = c->d_res; a.wcount = c->d_wcount; a.stats = c->d_stats;
+  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->cur.d_wtab; a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats;
   a.wmax = c->wmax; a.n_streams = n; a.rows = q.rows; a.table = q.d_table; a.nrows = q.d_nrows;
   QualGatherArgs g;
   g.reads = t.d_reads; g.head = t.d_head; g.cap = t.cap; g.table = q.d_table; g.n_streams = n; g.rows = q.rows; g.out = q.d_packed;
   { int r = stage_record(c, q, 0); if (r) return r; }
   // single-wave workgroups, each walking packs of eight rows (12.6 KB of LDS each)
   const int64_t items = (int64_t)n * ((q.rows + QUAL_PACK - 1) / QUAL_PACK);
-  const int64_t most = (int64_t)c->n_cus * QUAL_WGS_PER_CU;
-  hipLaunchKernelGGL(quality_kernel, dim3((unsigned)(items < most ? (items > 0 ? items : 1) : most)), dim3(64), 0, c->stream, a);
+  hipLaunchKernelGGL(quality_kernel, persistent_grid(items, (int64_t)c->n_cus * QUAL_WGS_PER_CU), dim3(64), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   const int64_t words = t.cap * QUAL_WORDS, gmost = (int64_t)c->n_cus * 8;
   int64_t gblocks = (words + QUAL_GATHER_THREADS - 1) / QUAL_GATHER_THREADS;
@@ -1690,9 +1807,7 @@ int rfid_batch_quality(rfid_ctx *c) {
   hipLaunchKernelGGL(quality_gather_kernel, dim3((unsigned)gblocks), dim3(QUAL_GATHER_THREADS), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
   { int r = stage_record(c, q, 1); if (r) return r; }
-  // the long-stream front end hands this pass's matched-filter buffer to the pass after next, whose first launch runs on the
-  // second stream as soon as the buffer's event has come: the event is recorded again, behind the launches that read the buffer
-  if (c->y_recorded[c->y_idx]) HIPCHK(c, hipEventRecord(c->ev_y_free[c->y_idx], c->stream));
+  { int r = y_read_again(c); if (r) return r; }
   q.enqueued = true;
   q.n_streams = n;
   return RFID_OK;
@@ -1718,19 +1833,7 @@ int rfid_batch_get_window_quality(rfid_ctx *c, int stream, rfid_read_quality *ou
   if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
   rfid_ctx::Quality &q = c->qual;
   if (!q.blk || !q.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_quality: no rfid_batch_quality behind this plan");
-  if (stream < 0 || stream >= q.n_streams) return RFID_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  int nrows = 0;
-  HIPCHK(c, hipMemcpyAsync(&nrows, q.d_nrows + stream, sizeof(nrows), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *n = nrows;
-  if (nrows > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_window_quality: cap is smaller than the number of EPC windows");
-  const int64_t take = (cap < q.rows) ? cap : q.rows;      // (the zeroed rows behind the cut-off too, as far as there is room)
-  if (take > 0) {
-    HIPCHK(c, hipMemcpyAsync(out, q.d_table + (size_t)stream * (size_t)q.rows, sizeof(rfid_read_quality) * (size_t)take, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return RFID_OK;
+  return stage_fetch_rows(c, "rfid_batch_get_window_quality", q.d_nrows, q.d_table, sizeof(rfid_read_quality), q.rows, q.n_streams, stream, out, cap, n);
 }
 
 int rfid_batch_quality_ms(rfid_ctx *c, float *ms) {
@@ -1769,7 +1872,7 @@ int rfid_batch_repair(rfid_ctx *c) {
   { int rj = join_tails(c); if (rj) return rj; }
   const int n = v.n_streams;          // the traces the inventory covered
   RepArgs a;
-  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->d_wtab; a.res = c->d_res; a.wcount = c->d_wcount; a.stats = c->d_stats;
+  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->cur.d_wtab; a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats;
   a.wmax = c->wmax; a.n_streams = n; a.rows = p.rows; a.blocks = p.blocks;
   a.ent = v.d_ent; a.ent_counts = v.d_counts; a.ent_over = v.d_over; a.max_tags = v.max_tags;
   a.table = p.d_table; a.nrows = p.d_nrows; a.counts = p.d_counts;
@@ -1778,8 +1881,8 @@ int rfid_batch_repair(rfid_ctx *c) {
   g.offsets = p.d_off; g.head = p.d_head; g.packed = p.d_packed; g.cap = (int64_t)p.rows * c->B_plan;
   { int r = stage_record(c, p, 0); if (r) return r; }
   // single-wave workgroups, each walking blocks of 64 rows (no LDS)
-  const int64_t items = (int64_t)n * p.blocks, most = (int64_t)c->n_cus * REP_WGS_PER_CU;
-  const dim3 grid((unsigned)(items < most ? (items > 0 ? items : 1) : most));
+  const int64_t items = (int64_t)n * p.blocks;
+  const dim3 grid = persistent_grid(items, (int64_t)c->n_cus * REP_WGS_PER_CU);
   hipLaunchKernelGGL(repair_kernel, grid, dim3(64), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(repair_offsets_kernel, dim3(1), scan_block((int)items), 0, c->stream, g);
@@ -1787,8 +1890,7 @@ int rfid_batch_repair(rfid_ctx *c) {
   hipLaunchKernelGGL(repair_pack_kernel, grid, dim3(64), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
   { int r = stage_record(c, p, 1); if (r) return r; }
-  // (as rfid_batch_quality: the pass after next gets this pass's matched-filter buffer and waits for the launches that read it)
-  if (c->y_recorded[c->y_idx]) HIPCHK(c, hipEventRecord(c->ev_y_free[c->y_idx], c->stream));
+  { int r = y_read_again(c); if (r) return r; }
   p.enqueued = true;
   p.n_streams = n;
   return RFID_OK;
@@ -1815,19 +1917,7 @@ int rfid_batch_get_window_repairs(rfid_ctx *c, int stream, rfid_repair *out, int
   if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
   rfid_ctx::Repair &p = c->rep;
   if (!p.blk || !p.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_repairs: no rfid_batch_repair behind this plan");
-  if (stream < 0 || stream >= p.n_streams) return RFID_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  int nrows = 0;
-  HIPCHK(c, hipMemcpyAsync(&nrows, p.d_nrows + stream, sizeof(nrows), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *n = nrows;
-  if (nrows > cap) return fail(c, RFID_ERR_CAPACITY, "rfid_batch_get_window_repairs: cap is smaller than the number of EPC windows");
-  const int64_t take = (cap < p.rows) ? cap : p.rows;      // (the zeroed rows behind the cut-off too, as far as there is room)
-  if (take > 0) {
-    HIPCHK(c, hipMemcpyAsync(out, p.d_table + (size_t)stream * (size_t)p.rows, sizeof(rfid_repair) * (size_t)take, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return RFID_OK;
+  return stage_fetch_rows(c, "rfid_batch_get_window_repairs", p.d_nrows, p.d_table, sizeof(rfid_repair), p.rows, p.n_streams, stream, out, cap, n);
 }
 
 int rfid_batch_repair_ms(rfid_ctx *c, float *ms) {
@@ -1853,179 +1943,110 @@ int rfid_repair_window(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_re
   return RFID_OK;
 }
 
-// mf -> gate -> decode -> stats.  The matched filter (HBM-bound) and the gate scan (bound by the
+}  // extern "C"
+
+// ======================================================================================
+// the four front-end paths of a batch pass (rfid_batch_process chooses)
+// ======================================================================================
+namespace {
+
+// few long traces: matched filter, then the gate scan as the long-stream front end -- every launch of it enqueued
+// here, the sequential scan behind them as the fallback that skips itself when the front end succeeded
+int pass_long_stream(rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64_t n_raw, const void *d_lens, int want_scores) {
+  HIPCHK(c, hipSetDevice(c->device));
+  { int rj = join_tails(c); if (rj) return rj; }
+  const int64_t n_out = n_raw / DECIM;
+  const int64_t tiles = (n_out + MF_TILE - 1) / MF_TILE;
+  int rc, enq = 0;
+  bool ahead = false;
+  // ---- first half ----
+  // The fused first pass (round 5, the default for traces that start from the fresh gate): no matched-filter launch -- the
+  // front end's first launch filters the raw samples itself (ls2_front_kernel), one sweep over the raw samples instead of the
+  // filter's and three over its output.  When the front end gives up the sequential scan behind it needs all of y: a filter
+  // launch and the scan are enqueued behind the list, both skipping themselves on Ls2Ctl::ok.
+  if (raw_stride >= 2) {
+    c->d_lens = (const int64_t *)d_lens;
+    c->last_n_raw = n_raw;
+    c->n_chunks_last = 0;
+    // Passes enqueued back to back: with a second matched-filter output buffer and a second work space (rfid_batch_plan) the
+    // fused first pass of THIS pass -- bound by the HBM, and touching nothing but the raw samples, y and its work space --
+    // runs on stream2 beside the rest of the pass before (re-run rounds, state machine, dc_est, decoder: instruction- and
+    // latency-bound launches that leave most of the HBM's bandwidth unused); the rest of this pass follows on the main
+    // stream.  The buffers alternate; a buffer is written again only when the pass before last is through with it.
+    // (an error anywhere below may leave the alternating buffers / work spaces swapped without a pass behind them: HIPCHK_T marks
+    // the context so that the next pass waits for everything enqueued so far before its second stream starts, whichever
+    // buffers it gets)
+    ahead = c->alt.d_y != nullptr && c->ls2_ws_alt.p != nullptr && !c->alt_have && (c->knobs.overlap != 0);
+    if (ahead && (rc = y_take_ahead(c))) return rc;
+    HIPCHK_T(c, ev_mark(c, EV_MF_BEGIN, c->stream));
+    HIPCHK_T(c, ev_mark(c, EV_MF_END, c->stream));   // mf_ms = 0: the filter runs inside the front end's first launch
+    LsOpts lo;
+    lo.raw = d_raw; lo.raw_stride = raw_stride; lo.ahead = ahead;
+    if ((rc = ls_enqueue(c, n_out, lo, &enq))) { c->y_touched = true; return rc; }
+    if (!enq && ahead) {
+      // (not applicable with the second stream after all: the buffers go back, the pass runs on the main stream alone)
+      y_give_back(c);
+      ahead = lo.ahead = false;
+      if ((rc = ls_enqueue(c, n_out, lo, &enq))) return rc;   // (y_touched: y_give_back has set it)
+    }
+  }
+  if (enq) {
+    c->fused_last = 2;
+    MfFallbackArgs f;
+    f.m = mf_args(c, d_raw, raw_stride, n_raw);
+    f.skip_if = &c->d_ls2_ctl->ok; f.n_tiles = tiles;
+    if ((rc = launch_mf_rows(c, c->stream, f, (tiles < 4096) ? tiles : 4096)) || (rc = rfid_batch_gate_impl(c, &c->d_ls2_ctl->ok)) ||
+        (rc = rfid_batch_decode(c, want_scores)) || (rc = rfid_batch_stats(c))) { c->y_touched = true; return rc; }
+    return y_pass_done(c, ahead);
+  }
+  // ---- second half ----
+  // (rows of a single raw sample, or no work space for the fused first pass: the matched filter by itself, then the front end over
+  // its output -- the list the streaming calls use)
+  c->y_touched = true;
+  if ((rc = batch_mf_on(c, c->stream, d_raw, raw_stride, n_raw, d_lens))) return rc;
+  LsOpts lo;
+  if ((rc = ls_enqueue(c, n_out, lo, &enq))) return rc;
+  if ((rc = rfid_batch_gate_impl(c, enq ? &c->d_ls2_ctl->ok : nullptr))) return rc;
+  if ((rc = rfid_batch_decode(c, want_scores))) return rc;
+  return rfid_batch_stats(c);
+}
+
+// default: fused front end -- the gate's producer waves run the matched filter themselves
+// (one read of the raw samples, one write of y for the decoder, no second pass over y)
+int pass_fused(rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64_t n_raw, const void *d_lens, int want_scores) {
+  HIPCHK(c, hipSetDevice(c->device));
+  c->d_lens = (const int64_t *)d_lens;
+  c->last_n_raw = n_raw;
+  c->n_chunks_last = 0;
+  const bool overlap = c->alt_have && !want_scores;
+  { int rj = overlap ? set_take_next(c) : join_tails(c); if (rj) return rj; }
+  HIPCHK(c, ev_mark(c, EV_MF_BEGIN, c->stream));
+  HIPCHK(c, ev_mark(c, EV_MF_END, c->stream));   // mf_ms = 0: the filter runs inside the gate launch
+  HIPCHK(c, hipMemsetAsync(c->d_gstate, 0, sizeof(GateState) * (size_t)c->B, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->cur.d_flat_count, 0, 2 * sizeof(int), c->stream));
+  GateArgs g = gate_args(c, n_raw / DECIM);
+  g.y_w = c->cur.d_y;
+  g.raw = (const float2 *)d_raw; g.raw_stride = raw_stride; g.n_raw = n_raw;
+  g.raw_vec_ok = rows_vec_ok(d_raw, raw_stride);
+  g.single_step = c->knobs.front_single_step;
+  hipLaunchKernelGGL(front_end_fused_kernel, gate_grid(c), dim3(GATE_THREADS), 0, c->stream, g);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, ev_mark(c, EV_GATE_END, c->stream));
+  c->fused_last = 1;
+  if (overlap) return set_tails_on_stream2(c);
+  int rc = rfid_batch_decode(c, want_scores);
+  if (rc) return rc;
+  return rfid_batch_stats(c);
+}
+
+// The matched filter (HBM-bound) and the gate scan (bound by the
 // latency of its in-order sums, one wave per SIMD) are overlapped: the traces are cut along
 // time into chunks; chunk k of the gate scan runs on a second stream as soon as chunk k of the
 // matched filter is done, carrying the gate state from chunk to chunk (exactly the state a
 // streaming call sequence would carry).
-int rfid_batch_process(rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64_t n_raw, const void *d_lens,
-                       int want_scores) {
-  if (!c || !d_raw || n_raw < 0 || raw_stride < n_raw) return RFID_ERR_INVALID;
-  if (!c->B) return RFID_ERR_STATE;
-  if (n_raw > c->max_raw) return RFID_ERR_CAPACITY;
-  ls_note_last_pass(c);
-  const int64_t n_out = n_raw / DECIM;
-  const int64_t tiles = (n_out + MF_TILE - 1) / MF_TILE;
-  // measured on MI355X (1024 traces): the overlap paid off while the gate scan took 4 ms (-5 %), but the
-  // scan is slowed down by anything that shares its SIMDs; since it runs in 2.9 ms the plain sequence is
-  // faster, so chunking is opt-in (RFID_FRONT_CHUNKS=8)
+int pass_chunked(rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64_t n_raw, const void *d_lens, int want_scores) {
   const int nch = c->knobs.front_chunks;
-  if (nch < 2 && ls_applicable(c, c->B, n_out)) {
-    // few long traces: matched filter, then the gate scan as the long-stream front end -- every launch of it enqueued
-    // here, the sequential scan behind them as the fallback that skips itself when the front end succeeded
-    HIPCHK(c, hipSetDevice(c->device));
-    { int rj = join_tails(c); if (rj) return rj; }
-    int rc;
-    // The fused first pass (round 5, the default for traces that start from the fresh gate): no matched-filter launch -- the
-    // front end's first launch filters the raw samples itself (ls2_front_kernel), one sweep over the raw samples instead of the
-    // filter's and three over its output.  When the front end gives up the sequential scan behind it needs all of y: a filter
-    // launch and the scan are enqueued behind the list, both skipping themselves on Ls2Ctl::ok.
-    if (raw_stride >= 2) {
-      c->d_lens = (const int64_t *)d_lens;
-      c->last_n_raw = n_raw;
-      c->n_chunks_last = 0;
-      // Passes enqueued back to back: with a second matched-filter output buffer and a second work space (rfid_batch_plan) the
-      // fused first pass of THIS pass -- bound by the HBM, and touching nothing but the raw samples, y and its work space --
-      // runs on stream2 beside the rest of the pass before (re-run rounds, state machine, dc_est, decoder: instruction- and
-      // latency-bound launches that leave most of the HBM's bandwidth unused); the rest of this pass follows on the main
-      // stream.  The buffers alternate; a buffer is written again only when the pass before last is through with it.
-      // (an error anywhere below may leave the alternating buffers / work spaces swapped without a pass behind them: HIPCHK_T marks
-      // the context so that the next pass waits for everything enqueued so far before its second stream starts, whichever
-      // buffers it gets)
-      const bool ahead = c->alt.d_y != nullptr && c->ls2_ws_alt.p != nullptr && !c->alt_have && (c->knobs.overlap != 0);
-      if (ahead) {
-        std::swap(c->d_y, c->alt.d_y);
-        c->y_idx ^= 1;
-        if (c->y_touched) {   // (something outside this protocol used a buffer on the main stream: wait for all of it)
-          HIPCHK_T(c, hipEventRecord(c->ev_pass, c->stream));
-          HIPCHK_T(c, hipStreamWaitEvent(c->stream2, c->ev_pass, 0));
-          c->y_touched = false;
-        }
-        if (c->y_recorded[c->y_idx]) {
-          HIPCHK_T(c, hipStreamWaitEvent(c->stream2, c->ev_y_free[c->y_idx], 0));
-          c->y_recorded[c->y_idx] = false;
-        }
-      }
-      HIPCHK_T(c, hipEventRecord(c->ev[0], c->stream));
-      HIPCHK_T(c, hipEventRecord(c->ev[1], c->stream));   // mf_ms = 0: the filter runs inside the front end's first launch
-      c->ev_valid[0] = c->ev_valid[1] = true;
-      int enq = 0;
-      LsOpts lo;
-      lo.raw = d_raw; lo.raw_stride = raw_stride; lo.ahead = ahead;
-      if ((rc = ls_enqueue(c, n_out, lo, &enq))) { c->y_touched = true; return rc; }
-      if (!enq && ahead) {
-        // (not applicable with the second stream after all: the buffers go back, the pass runs on the main stream alone)
-        std::swap(c->d_y, c->alt.d_y); c->y_idx ^= 1;
-        c->y_touched = true;
-        lo.ahead = false;
-        if ((rc = ls_enqueue(c, n_out, lo, &enq))) { c->y_touched = true; return rc; }
-      }
-      const bool ahead_now = ahead && lo.ahead;
-      if (enq) {
-        c->fused_last = 2;
-        MfFallbackArgs f;
-        f.m.x = (const float2 *)d_raw; f.m.x_stride = raw_stride; f.m.n_raw = n_raw; f.m.lens = c->d_lens;
-        f.m.n_out = n_out; f.m.in_off = -(NTAPS - 1);
-        f.m.vec_ok = ((raw_stride & 1) == 0 && (((uintptr_t)d_raw) & 15) == 0) ? 1 : 0;
-        f.m.y = c->d_y; f.m.y_stride = c->y_stride; f.m.tile0 = 0; f.m.stream0 = 0;
-        f.skip_if = &c->d_ls2_ctl->ok; f.n_tiles = tiles;
-        const int64_t gx = (tiles < 4096) ? tiles : 4096;
-        for (int s0 = 0; s0 < c->B && gx > 0; s0 += 65535) {
-          f.m.stream0 = s0;
-          const int ns = (c->B - s0 < 65535) ? (c->B - s0) : 65535;
-          hipLaunchKernelGGL(mf_fallback_kernel, dim3((unsigned)gx, (unsigned)ns), dim3(MF_THREADS), 0, c->stream, f);
-          HIPCHK_T(c, hipGetLastError());
-        }
-        if ((rc = rfid_batch_gate_impl(c, &c->d_ls2_ctl->ok)) || (rc = rfid_batch_decode(c, want_scores)) || (rc = rfid_batch_stats(c))) { c->y_touched = true; return rc; }
-        if (ahead_now) {
-          HIPCHK_T(c, hipEventRecord(c->ev_y_free[c->y_idx], c->stream));
-          c->y_recorded[c->y_idx] = true;
-        } else {
-          c->y_touched = true;
-        }
-        return RFID_OK;
-      }
-      // (no work space: the plain sequence below)
-    }
-    // (rows of a single raw sample, or no work space for the fused first pass: the matched filter by itself, then the front end over
-    // its output -- the list the streaming calls use)
-    c->y_touched = true;
-    if ((rc = batch_mf_on(c, c->stream, d_raw, raw_stride, n_raw, d_lens))) return rc;
-    int enq = 0;
-    LsOpts lo;
-    if ((rc = ls_enqueue(c, n_out, lo, &enq))) return rc;
-    if ((rc = rfid_batch_gate_impl(c, enq ? &c->d_ls2_ctl->ok : nullptr))) return rc;
-    if ((rc = rfid_batch_decode(c, want_scores))) return rc;
-    return rfid_batch_stats(c);
-  }
-  c->d_ls2_ctl = nullptr;   // (this pass does not run the long-stream front end)
-  c->y_touched = true;
-  if (nch < 2 && raw_stride >= 2 && !c->knobs.front_unfused) {
-    // default: fused front end -- the gate's producer waves run the matched filter themselves
-    // (one read of the raw samples, one write of y for the decoder, no second pass over y)
-    HIPCHK(c, hipSetDevice(c->device));
-    c->d_lens = (const int64_t *)d_lens;
-    c->last_n_raw = n_raw;
-    c->n_chunks_last = 0;
-    const bool overlap = c->alt_have && !want_scores;
-    if (overlap) {
-      // this pass works on the set the pass before last used; its decoder and statistics (stream2) must be through with it
-      std::swap(c->d_y, c->alt.d_y); std::swap(c->d_wtab, c->alt.d_wtab); std::swap(c->d_flat, c->alt.d_flat);
-      std::swap(c->d_wcount, c->alt.d_wcount); std::swap(c->d_flat_count, c->alt.d_flat_count);
-      std::swap(c->d_res, c->alt.d_res); std::swap(c->d_stats, c->alt.d_stats);
-      c->set_idx ^= 1;
-      if (c->tail_recorded[c->set_idx]) {
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_tail_done[c->set_idx], 0));
-        c->tail_recorded[c->set_idx] = false;
-      }
-    } else {
-      int rj = join_tails(c);
-      if (rj) return rj;
-    }
-    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    HIPCHK(c, hipEventRecord(c->ev[1], c->stream));   // mf_ms = 0: the filter runs inside the gate launch
-    HIPCHK(c, hipMemsetAsync(c->d_gstate, 0, sizeof(GateState) * (size_t)c->B, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_flat_count, 0, 2 * sizeof(int), c->stream));
-    GateArgs g = {};
-    g.y = c->d_y; g.y_w = c->d_y; g.y_stride = c->y_stride; g.n_dec = n_out; g.lens = c->d_lens;
-    g.pos0 = 0; g.chunk_len = n_out;
-    g.state = c->d_gstate; g.n_streams = c->B; g.wtab = c->d_wtab; g.wmax = c->wmax; g.wcount = c->d_wcount;
-    g.flat = c->d_flat; g.flat_count = c->d_flat_count; g.flat_cap = c->flat_cap; g.mode = 0;
-    g.raw = (const float2 *)d_raw; g.raw_stride = raw_stride; g.n_raw = n_raw;
-    g.raw_vec_ok = ((raw_stride & 1) == 0 && (((uintptr_t)d_raw) & 15) == 0) ? 1 : 0;
-    g.single_step = c->knobs.front_single_step;
-    hipLaunchKernelGGL(front_end_fused_kernel, dim3((unsigned)((c->B + GATE_STREAMS_PER_WG - 1) / GATE_STREAMS_PER_WG)),
-                       dim3(GATE_THREADS), 0, c->stream, g);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-    c->ev_valid[0] = c->ev_valid[1] = c->ev_valid[2] = true;
-    c->fused_last = 1;
-    if (overlap) {
-      // decoder + statistics of this pass on stream2, behind this front end; the next pass's front end does not wait for them
-      HIPCHK(c, hipEventRecord(c->ev_fe_done, c->stream));
-      HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fe_done, 0));
-      c->tail_stream = c->stream2;
-      c->ev_valid[2] = false;           // (ev[2] is re-recorded on stream2: the decoder's time starts when it can start)
-      int rc = rfid_batch_decode(c, 0);
-      if (!rc) rc = rfid_batch_stats(c);
-      c->tail_stream = nullptr;
-      if (rc) return rc;
-      HIPCHK(c, hipEventRecord(c->ev_tail_done[c->set_idx], c->stream2));
-      c->tail_recorded[c->set_idx] = true;
-      return RFID_OK;
-    }
-    int rc = rfid_batch_decode(c, want_scores);
-    if (rc) return rc;
-    return rfid_batch_stats(c);
-  }
-  c->fused_last = 0;
-  if (tiles < 4 * (int64_t)nch || nch < 2) {   // plain sequence of the stage kernels
-    int rc = rfid_batch_mf(c, d_raw, raw_stride, n_raw, d_lens);
-    if (rc) return rc;
-    if ((rc = rfid_batch_gate(c))) return rc;
-    if ((rc = rfid_batch_decode(c, want_scores))) return rc;
-    return rfid_batch_stats(c);
-  }
+  const int64_t tiles = (n_raw / DECIM + MF_TILE - 1) / MF_TILE;
   HIPCHK(c, hipSetDevice(c->device));
   { int rj = join_tails(c); if (rj) return rj; }
   if (!c->ev_mf[0]) {
@@ -2039,18 +2060,10 @@ int rfid_batch_process(rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64
   HIPCHK(c, hipEventRecord(c->ev_pass, c->stream));
   HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_pass, 0));
   HIPCHK(c, hipMemsetAsync(c->d_gstate, 0, sizeof(GateState) * (size_t)c->B, c->stream2));
-  HIPCHK(c, hipMemsetAsync(c->d_flat_count, 0, 2 * sizeof(int), c->stream2));
-  MfArgs m;
-  m.x = (const float2 *)d_raw; m.x_stride = raw_stride; m.n_raw = n_raw; m.lens = c->d_lens;
-  m.n_out = n_out; m.in_off = -(NTAPS - 1);
-  m.vec_ok = ((raw_stride & 1) == 0 && (((uintptr_t)d_raw) & 15) == 0) ? 1 : 0;
-  m.y = c->d_y; m.y_stride = c->y_stride; m.stream0 = 0;
-  GateArgs g = {};
-  g.y = c->d_y; g.y_stride = c->y_stride; g.n_dec = n_out; g.lens = c->d_lens;
-  g.state = c->d_gstate; g.n_streams = c->B; g.wtab = c->d_wtab; g.wmax = c->wmax; g.wcount = c->d_wcount;
-  g.flat = c->d_flat; g.flat_count = c->d_flat_count; g.flat_cap = c->flat_cap; g.mode = 0;
-  g.gated = nullptr; g.gated_cap = 0; g.io = nullptr;
-  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  HIPCHK(c, hipMemsetAsync(c->cur.d_flat_count, 0, 2 * sizeof(int), c->stream2));
+  MfArgs m = mf_args(c, d_raw, raw_stride, n_raw);
+  GateArgs g = gate_args(c, n_raw / DECIM);
+  HIPCHK(c, ev_mark(c, EV_MF_BEGIN, c->stream));
   HIPCHK(c, hipEventRecord(c->ev_mf[0], c->stream));
   int used = 0;
   for (int k = 0; k < nch; ++k) {
@@ -2058,18 +2071,12 @@ int rfid_batch_process(rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64
     if (t0 >= tiles) break;
     const int64_t tn = (t0 + tiles_per_chunk <= tiles) ? tiles_per_chunk : (tiles - t0);
     m.tile0 = t0;
-    for (int s0 = 0; s0 < c->B; s0 += 65535) {   // gridDim.y limit
-      m.stream0 = s0;
-      const int ns = (c->B - s0 < 65535) ? (c->B - s0) : 65535;
-      hipLaunchKernelGGL(mf_boxcar25_decim5_kernel, dim3((unsigned)tn, (unsigned)ns), dim3(MF_THREADS), 0, c->stream, m);
-      HIPCHK(c, hipGetLastError());
-    }
+    { int r = launch_mf_rows(c, c->stream, m, tn); if (r) return r; }
     HIPCHK(c, hipEventRecord(c->ev_mf[k + 1], c->stream));
     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_mf[k + 1], 0));
     g.pos0 = t0 * MF_TILE; g.chunk_len = tn * MF_TILE;
     HIPCHK(c, hipEventRecord(c->ev_gate[2 * k], c->stream2));
-    hipLaunchKernelGGL(gate_scan_kernel, dim3((unsigned)((c->B + GATE_STREAMS_PER_WG - 1) / GATE_STREAMS_PER_WG)),
-                       dim3(GATE_THREADS), 0, c->stream2, g);
+    hipLaunchKernelGGL(gate_scan_kernel, gate_grid(c), dim3(GATE_THREADS), 0, c->stream2, g);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev_gate[2 * k + 1], c->stream2));
     used = k + 1;
@@ -2077,11 +2084,43 @@ int rfid_batch_process(rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64
   c->n_chunks_last = used;
   HIPCHK(c, hipEventRecord(c->ev_front_end, c->stream2));
   HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_front_end, 0));
-  HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  c->ev_valid[0] = true; c->ev_valid[1] = false; c->ev_valid[2] = true;
+  c->ev_valid[EV_MF_END] = false;
+  HIPCHK(c, ev_mark(c, EV_GATE_END, c->stream));
   int rc = rfid_batch_decode(c, want_scores);
   if (rc) return rc;
   return rfid_batch_stats(c);
+}
+
+}  // namespace
+
+extern "C" {
+
+// mf -> gate -> decode -> stats, by one of four front-end paths
+int rfid_batch_process(rfid_ctx *c, const void *d_raw, int64_t raw_stride, int64_t n_raw, const void *d_lens,
+                       int want_scores) {
+  if (!c || !d_raw || n_raw < 0 || raw_stride < n_raw) return RFID_ERR_INVALID;
+  if (!c->B) return RFID_ERR_STATE;
+  if (n_raw > c->max_raw) return RFID_ERR_CAPACITY;
+  ls_note_last_pass(c);
+  const int64_t n_out = n_raw / DECIM;
+  const int64_t tiles = (n_out + MF_TILE - 1) / MF_TILE;
+  // measured on MI355X (1024 traces): the overlap paid off while the gate scan took 4 ms (-5 %), but the
+  // scan is slowed down by anything that shares its SIMDs; since it runs in 2.9 ms the plain sequence is
+  // faster, so chunking is opt-in (RFID_FRONT_CHUNKS=8)
+  const int nch = c->knobs.front_chunks;
+  if (nch < 2 && ls_applicable(c, c->B, n_out)) return pass_long_stream(c, d_raw, raw_stride, n_raw, d_lens, want_scores);
+  c->d_ls2_ctl = nullptr;   // (this pass does not run the long-stream front end)
+  c->y_touched = true;
+  if (nch < 2 && raw_stride >= 2 && !c->knobs.front_unfused) return pass_fused(c, d_raw, raw_stride, n_raw, d_lens, want_scores);
+  c->fused_last = 0;
+  if (tiles < 4 * (int64_t)nch || nch < 2) {   // plain sequence of the stage kernels
+    int rc = rfid_batch_mf(c, d_raw, raw_stride, n_raw, d_lens);
+    if (rc) return rc;
+    if ((rc = rfid_batch_gate(c))) return rc;
+    if ((rc = rfid_batch_decode(c, want_scores))) return rc;
+    return rfid_batch_stats(c);
+  }
+  return pass_chunked(c, d_raw, raw_stride, n_raw, d_lens, want_scores);
 }
 
 int rfid_batch_set_long_stream(rfid_ctx *c, int mode) {
@@ -2156,11 +2195,11 @@ int rfid_batch_timing_get(rfid_ctx *c, rfid_batch_timing *out) {
       ms[1] += t;
     }
     HIPCHK(c, hipEventElapsedTime(&front, c->ev_mf[0], c->ev_front_end));
-    for (int i = 2; i < 4; ++i)
+    for (int i = EV_GATE_END; i < EV_STATS_END; ++i)
       if (c->ev_valid[i] && c->ev_valid[i + 1]) HIPCHK(c, hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
     out->total_ms = front + ms[2] + ms[3];
   } else {
-    for (int i = 0; i < 4; ++i)
+    for (int i = EV_MF_BEGIN; i < EV_STATS_END; ++i)
       if (c->ev_valid[i] && c->ev_valid[i + 1]) HIPCHK(c, hipEventElapsedTime(&ms[i], c->ev[i], c->ev[i + 1]));
     out->total_ms = ms[0] + ms[1] + ms[2] + ms[3];
   }
@@ -2179,7 +2218,7 @@ int rfid_batch_get_stats(rfid_ctx *c, rfid_stream_stats *out, int n_streams) {
   if (n_streams > c->B) n_streams = c->B;
   HIPCHK(c, hipSetDevice(c->device));
   { int rj = join_tails(c); if (rj) return rj; }
-  HIPCHK(c, hipMemcpyAsync(out, c->d_stats, sizeof(rfid_stream_stats) * (size_t)n_streams, hipMemcpyDeviceToHost,
+  HIPCHK(c, hipMemcpyAsync(out, c->cur.d_stats, sizeof(rfid_stream_stats) * (size_t)n_streams, hipMemcpyDeviceToHost,
                            c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
@@ -2192,7 +2231,7 @@ int rfid_batch_get_windows(rfid_ctx *c, rfid_window *windows, rfid_decode_result
   HIPCHK(c, hipSetDevice(c->device));
   { int rj = join_tails(c); if (rj) return rj; }
   std::vector<int> wc((size_t)c->B);
-  HIPCHK(c, hipMemcpyAsync(wc.data(), c->d_wcount, sizeof(int) * (size_t)c->B, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(wc.data(), c->cur.d_wcount, sizeof(int) * (size_t)c->B, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   int64_t total = 0;
   for (int s = 0; s < c->B; ++s) {
@@ -2202,10 +2241,10 @@ int rfid_batch_get_windows(rfid_ctx *c, rfid_window *windows, rfid_decode_result
     if (take > 0) {
       const size_t off = (size_t)s * (size_t)c->wmax;
       if (windows)
-        HIPCHK(c, hipMemcpyAsync(windows + total, c->d_wtab + off, sizeof(rfid_window) * (size_t)take,
+        HIPCHK(c, hipMemcpyAsync(windows + total, c->cur.d_wtab + off, sizeof(rfid_window) * (size_t)take,
                                  hipMemcpyDeviceToHost, c->stream));
       if (results)
-        HIPCHK(c, hipMemcpyAsync(results + total, c->d_res + off, sizeof(rfid_decode_result) * (size_t)take,
+        HIPCHK(c, hipMemcpyAsync(results + total, c->cur.d_res + off, sizeof(rfid_decode_result) * (size_t)take,
                                  hipMemcpyDeviceToHost, c->stream));
       if (scores)
         HIPCHK(c, hipMemcpyAsync(scores + total, c->d_scores + off, sizeof(rfid_scores) * (size_t)take,
@@ -2223,10 +2262,10 @@ int rfid_batch_device_ptrs(rfid_ctx *c, void **d_mf_out, int64_t *mf_stride, voi
   if (!c->B) return RFID_ERR_STATE;
   // (the buffers of the LAST pass; with the second result set in use they alternate from pass to pass)
   { int rj = join_tails(c); if (rj) return rj; }
-  if (d_mf_out) *d_mf_out = c->d_y;
+  if (d_mf_out) *d_mf_out = c->cur.d_y;
   if (mf_stride) *mf_stride = c->y_stride;
-  if (d_stats) *d_stats = c->d_stats;
-  if (d_flat_count) *d_flat_count = c->d_flat_count;
+  if (d_stats) *d_stats = c->cur.d_stats;
+  if (d_flat_count) *d_flat_count = c->cur.d_flat_count;
   return RFID_OK;
 }
 
@@ -2247,7 +2286,7 @@ int rfid_batch_get_mf(rfid_ctx *c, int stream, rfid_cf32 *out, int64_t cap, int6
   *n = k;
   if (k > cap) k = cap;
   if (k > 0)
-    HIPCHK(c, hipMemcpyAsync(out, c->d_y + (size_t)stream * (size_t)c->y_stride, sizeof(float2) * (size_t)k,
+    HIPCHK(c, hipMemcpyAsync(out, c->cur.d_y + (size_t)stream * (size_t)c->y_stride, sizeof(float2) * (size_t)k,
                              hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
@@ -2260,15 +2299,15 @@ int rfid_batch_get_gated(rfid_ctx *c, int stream, int seq, rfid_cf32 *out, int64
   { int rj = join_tails(c); if (rj) return rj; }
   int wc = 0;
   rfid_window w;
-  HIPCHK(c, hipMemcpyAsync(&wc, c->d_wcount + stream, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&w, c->d_wtab + (size_t)stream * (size_t)c->wmax + (size_t)seq, sizeof(w), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&wc, c->cur.d_wcount + stream, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&w, c->cur.d_wtab + (size_t)stream * (size_t)c->wmax + (size_t)seq, sizeof(w), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (seq >= wc) return fail(c, RFID_ERR_INVALID, "rfid_batch_get_gated: no such window");
   const int64_t len = w.type ? EPC_WIN : RN16_WIN;
   *n = len;
   const int64_t k = len < cap ? len : cap;
   if (k > 0) {
-    HIPCHK(c, hipMemcpyAsync(out, c->d_y + (size_t)stream * (size_t)c->y_stride + (size_t)w.start, sizeof(float2) * (size_t)k,
+    HIPCHK(c, hipMemcpyAsync(out, c->cur.d_y + (size_t)stream * (size_t)c->y_stride + (size_t)w.start, sizeof(float2) * (size_t)k,
                              hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     // in[i] - dc_est: one binary32 subtraction per component, the same operation on any IEEE host (no sample arithmetic

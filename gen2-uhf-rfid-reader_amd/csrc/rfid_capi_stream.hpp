@@ -82,7 +82,7 @@ int sio_enqueue_packet(rfid_ctx *c, int n_hdr, int usual, const int *only_if) {
   // the kernel writes the packet into page-locked host memory itself (half a megabyte over the bus at the end of a pass): a
   // device-side packet + hipMemcpyAsync cost the submitting call ~90 us of host time per pass
   GatedPack gp;
-  gp.wtab = c->d_wtab; gp.wcount = c->d_wcount; gp.res = c->d_res; gp.wmax = n_hdr; gp.y = c->y();
+  gp.wtab = c->cur.d_wtab; gp.wcount = c->cur.d_wcount; gp.res = c->cur.d_res; gp.wmax = n_hdr; gp.y = c->y();
   gp.pack = c->la.h_pack; gp.n_hdr = n_hdr; gp.usual = usual;
   gp.only_if = only_if;
   hipLaunchKernelGGL(gated_windows_kernel, dim3((unsigned)n_hdr), dim3(256), 0, c->stream, gp);
@@ -119,7 +119,7 @@ int sio_submit(rfid_ctx *c, int b, int64_t n_new, bool flush) {
     a.x = data - SIO_HIST; a.x_stride = SIO_HIST + n_have; a.n_raw = SIO_HIST + n_have; a.lens = nullptr;
     a.n_out = n_out; a.in_off = SIO_HIST - (NTAPS - 1);
     a.vec_ok = ((((uintptr_t)a.x) & 15) == 0) ? 1 : 0;
-    a.y = c->d_y; a.y_stride = c->y_stride; a.tile0 = 0; a.stream0 = 0;
+    a.y = c->cur.d_y; a.y_stride = c->y_stride; a.tile0 = 0; a.stream0 = 0;
     const int64_t tiles = (n_out + MF_TILE - 1) / MF_TILE;
     hipLaunchKernelGGL(mf_boxcar25_decim5_kernel, dim3((unsigned)tiles, 1), dim3(MF_THREADS), 0, c->stream, a);
     HIPCHK(c, hipGetLastError());
@@ -136,17 +136,17 @@ int sio_submit(rfid_ctx *c, int b, int64_t n_new, bool flush) {
     ps.small = true;
     ps.seq_end = flush ? n_out : (n_out - EPC_WIN);
     if (ps.seq_end > 0) {
-      HIPCHK(c, hipMemsetAsync(c->d_flat_count, 0, 2 * sizeof(int), c->stream));
+      HIPCHK(c, hipMemsetAsync(c->cur.d_flat_count, 0, 2 * sizeof(int), c->stream));
       HIPCHK(c, hipMemsetAsync(&c->d_gstate->win_seq, 0, sizeof(int), c->stream));   // windows are numbered per call
-      HIPCHK(c, hipMemsetAsync(c->d_wcount, 0, sizeof(int), c->stream));
+      HIPCHK(c, hipMemsetAsync(c->cur.d_wcount, 0, sizeof(int), c->stream));
       c->d_ls2_ctl = nullptr;
       GateArgs g = {};
       g.y = c->y(); g.y_stride = c->y_stride; g.n_dec = n_out; g.lens = nullptr; g.pos0 = 0; g.chunk_len = ps.seq_end;
-      g.state = c->d_gstate; g.n_streams = 1; g.wtab = c->d_wtab; g.wmax = c->wmax; g.wcount = c->d_wcount;
-      g.flat = c->d_flat; g.flat_count = c->d_flat_count; g.flat_cap = c->flat_cap; g.mode = 0;
+      g.state = c->d_gstate; g.n_streams = 1; g.wtab = c->cur.d_wtab; g.wmax = c->wmax; g.wcount = c->cur.d_wcount;
+      g.flat = c->cur.d_flat; g.flat_count = c->cur.d_flat_count; g.flat_cap = c->flat_cap; g.mode = 0;
       hipLaunchKernelGGL(gate_scan_kernel, dim3(1), dim3(GATE_THREADS), 0, c->stream, g);
       HIPCHK(c, hipGetLastError());
-      c->ev_valid[2] = false;
+      c->ev_valid[EV_GATE_END] = false;
       int rc = rfid_batch_decode(c, 0);
       if (rc) return rc;
       if (c->la.on) {
@@ -168,7 +168,7 @@ int sio_submit(rfid_ctx *c, int b, int64_t n_new, bool flush) {
     if (ps.enq && c->la.on) {
       // look-ahead: nearly every pass ends with the front end's tables -- decode them and pack the results right behind
       // it (a pass that ends otherwise is decoded and packed again by sio_collect)
-      c->ev_valid[2] = false;
+      c->ev_valid[EV_GATE_END] = false;
       const double t_d0 = la_now();
       if ((rc = rfid_batch_decode(c, 0))) return rc;
       const double t_d1 = la_now();
@@ -211,7 +211,7 @@ int sio_collect(rfid_ctx *c) {
       if (ok) consumed = flush ? n_out : *(const int *)((const char *)c->ls2_host + sizeof(Ls2Ctl));
       if (ok && consumed <= 0) ok = false;
     } else {
-      HIPCHK(c, hipMemsetAsync(c->d_flat_count, 0, 2 * sizeof(int), c->stream));
+      HIPCHK(c, hipMemsetAsync(c->cur.d_flat_count, 0, 2 * sizeof(int), c->stream));
     }
     // What the front end could not take -- no idle cut in what is available (a silent or noise-only stretch, not a Gen2
     // trace), rounds exhausted, or so much behind the last cut that it would not fit the hold-back area -- goes through
@@ -225,14 +225,14 @@ int sio_collect(rfid_ctx *c) {
     bool prefetched = ps.prefetched && ok;   // the packet behind the pass holds the front end's windows
     if (!ps.small && (!ok || tail_too_long) && seq_end > consumed) {
       if (!ok) {
-        HIPCHK(c, hipMemsetAsync(c->d_flat_count, 0, 2 * sizeof(int), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->cur.d_flat_count, 0, 2 * sizeof(int), c->stream));
         HIPCHK(c, hipMemsetAsync(&c->d_gstate->win_seq, 0, sizeof(int), c->stream));   // windows are numbered per call
-        HIPCHK(c, hipMemsetAsync(c->d_wcount, 0, sizeof(int), c->stream));
+        HIPCHK(c, hipMemsetAsync(c->cur.d_wcount, 0, sizeof(int), c->stream));
       }
       GateArgs g = {};
       g.y = c->y(); g.y_stride = c->y_stride; g.n_dec = n_out; g.lens = nullptr; g.pos0 = consumed; g.chunk_len = seq_end - consumed;
-      g.state = c->d_gstate; g.n_streams = 1; g.wtab = c->d_wtab; g.wmax = c->wmax; g.wcount = c->d_wcount;
-      g.flat = c->d_flat; g.flat_count = c->d_flat_count; g.flat_cap = c->flat_cap; g.mode = 0;
+      g.state = c->d_gstate; g.n_streams = 1; g.wtab = c->cur.d_wtab; g.wmax = c->wmax; g.wcount = c->cur.d_wcount;
+      g.flat = c->cur.d_flat; g.flat_count = c->cur.d_flat_count; g.flat_cap = c->flat_cap; g.mode = 0;
       hipLaunchKernelGGL(gate_scan_kernel, dim3(1), dim3(GATE_THREADS), 0, c->stream, g);
       HIPCHK(c, hipGetLastError());
       consumed = seq_end;
@@ -243,7 +243,7 @@ int sio_collect(rfid_ctx *c) {
       // ---- decode what the gate found (unless that is done), fetch it ----
       int rc;
       if (!prefetched) {
-        c->ev_valid[2] = false;
+        c->ev_valid[EV_GATE_END] = false;
         if ((rc = rfid_batch_decode(c, 0))) return rc;
       }
       int wc = 0;
@@ -282,7 +282,7 @@ int sio_collect(rfid_ctx *c) {
           c->la.n_hdr = wc + wc / 4 + 8;
         }
       } else {
-        HIPCHK(c, hipMemcpyAsync(&wc, c->d_wcount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&wc, c->cur.d_wcount, sizeof(int), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
       }
       n_windows = wc;
@@ -290,8 +290,8 @@ int sio_collect(rfid_ctx *c) {
         if (!c->la.on) {
           w.assign((size_t)wc, rfid_window());
           r.assign((size_t)wc, rfid_decode_result());
-          HIPCHK(c, hipMemcpyAsync(w.data(), c->d_wtab, sizeof(rfid_window) * (size_t)wc, hipMemcpyDeviceToHost, c->stream));
-          HIPCHK(c, hipMemcpyAsync(r.data(), c->d_res, sizeof(rfid_decode_result) * (size_t)wc, hipMemcpyDeviceToHost, c->stream));
+          HIPCHK(c, hipMemcpyAsync(w.data(), c->cur.d_wtab, sizeof(rfid_window) * (size_t)wc, hipMemcpyDeviceToHost, c->stream));
+          HIPCHK(c, hipMemcpyAsync(r.data(), c->cur.d_res, sizeof(rfid_decode_result) * (size_t)wc, hipMemcpyDeviceToHost, c->stream));
           HIPCHK(c, hipStreamSynchronize(c->stream));
         }
         const int64_t n0 = io.raw_base / io.dec();
@@ -791,10 +791,10 @@ int la_exact_step(rfid_ctx *c, int n_in, rfid_cf32 *out, int *consumed, int *wri
     m.x = data - SIO_HIST; m.x_stride = SIO_HIST + (int64_t)DECIM * n_scan; m.n_raw = m.x_stride; m.lens = nullptr;
     m.n_out = n_scan; m.in_off = SIO_HIST - (NTAPS - 1);
     m.vec_ok = ((((uintptr_t)m.x) & 15) == 0) ? 1 : 0;
-    m.y = c->d_y; m.y_stride = c->y_stride; m.tile0 = 0; m.stream0 = 0;
+    m.y = c->cur.d_y; m.y_stride = c->y_stride; m.tile0 = 0; m.stream0 = 0;
     hipLaunchKernelGGL(mf_boxcar25_decim5_kernel, dim3((unsigned)((n_scan + MF_TILE - 1) / MF_TILE), 1), dim3(MF_THREADS), 0, c->stream, m);
     HIPCHK(c, hipGetLastError());
-    ysrc = c->d_y;
+    ysrc = c->cur.d_y;
   }
   int rc = grow(c, c->s_out, sizeof(float2) * (size_t)(n_scan + 2));
   if (rc) return rc;

@@ -1,6 +1,6 @@
 """What the modules that run csrc/rfid_capi.hip on the CPU share: tests/fake_hip's library (the kernels on the wave emulator) in
-place of librfid_mi355x.so, and the helpers of the stage modules (test_inventory_emu, test_tracks_emu, test_quality_emu) that are
-the same in each."""
+place of librfid_mi355x.so, and the helpers of the four stage modules (test_inventory_emu, test_tracks_emu, test_quality_emu,
+test_repair_emu) that are the same in each."""
 import contextlib
 import ctypes as C
 import os

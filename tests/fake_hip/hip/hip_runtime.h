@@ -10,7 +10,12 @@
 // becomes runnable only n runtime-API calls later -- the host then meets passes that are still "running" (hipStreamQuery ==
 // hipErrorNotReady, flag words not written yet), as it does on a device; a wait (hipStreamSynchronize, hipEventSynchronize, a
 // synchronous copy) and fakehip::idle() (what a host spin loop calls) run what is due.  n = 0: every call finishes at once.
+//
+// FAKE_HIP_TRACE = path (environment, read per process): every launch, event record / wait, asynchronous copy / fill, allocation and
+// synchronisation appends one line to that file, in enqueue order -- streams and events by their number in creation order, sizes in
+// bytes, no pointer values: two builds of the host code that enqueue the same work write the same bytes (tests/tools/host_call_trace.py).
 #pragma once
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,14 +41,24 @@ struct hipPointerAttribute_t { hipMemoryType type; void *devicePointer; void *ho
 namespace fakehip {
 struct Event;
 struct Op { std::function<void()> fn; uint64_t due; Event *wait; uint64_t wait_gen; };
-struct Stream { std::deque<Op> q; };
-struct Event { uint64_t gen = 0, done_gen = 0; double t_ms = 0.0; };   // gen: records enqueued; done_gen: records executed
+struct Stream { std::deque<Op> q; int id = 0; };
+struct Event { uint64_t gen = 0, done_gen = 0; double t_ms = 0.0; int id = 0; };   // gen: records enqueued; done_gen: records executed
 struct State {
   uint64_t tick = 0; int lag = 0; hipError_t last = hipSuccess;
   std::vector<Stream *> streams; std::map<const char *, size_t> pinned;
-  State() { const char *v = getenv("FAKE_HIP_LAG"); lag = v ? atoi(v) : 0; }
+  FILE *trace = nullptr; int n_streams = 0, n_events = 0; std::map<void *, size_t> sizes;   // (FAKE_HIP_TRACE)
+  State() {
+    const char *v = getenv("FAKE_HIP_LAG"); lag = v ? atoi(v) : 0;
+    const char *t = getenv("FAKE_HIP_TRACE"); if (t && *t) trace = fopen(t, "a");
+  }
 };
 inline State &st() { static State s; return s; }
+inline void trace(const char *fmt, ...) {
+  FILE *f = st().trace;
+  if (!f) return;
+  va_list ap; va_start(ap, fmt); vfprintf(f, fmt, ap); va_end(ap);
+  fputc('\n', f); fflush(f);
+}
 inline double now_ms() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return 1e3 * (double)ts.tv_sec + 1e-6 * (double)ts.tv_nsec; }
 // runs what is runnable on `s` (everything when force); an op behind an event record that has not executed stays put
 inline bool run_stream(Stream *s, bool force) {
@@ -82,6 +97,7 @@ typedef fakehip::Event *hipEvent_t;
   do {                                                                                                                      \
     const dim3 g__ = (grid), b__ = (block);                                                                                 \
     fakehip::api_call();                                                                                                    \
+    fakehip::trace("launch %s grid %u %u %u block %u %u %u stream %d", #kernel, g__.x, g__.y, g__.z, b__.x, b__.y, b__.z, (stream)->id); \
     fakehip::enqueue((stream), [=]() { emu::launch(fakehip::idx3(g__), fakehip::idx3(b__), [&]() { kernel(__VA_ARGS__); }); }); \
   } while (0)
 
@@ -91,8 +107,8 @@ inline hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
 inline hipError_t hipSetDevice(int d) { return d == 0 ? hipSuccess : hipErrorInvalidValue; }
 inline hipError_t hipGetDeviceProperties(hipDeviceProp_t *p, int) { memset(p, 0, sizeof(*p)); strcpy(p->gcnArchName, "gfx950:sramecc+:xnack-"); p->multiProcessorCount = 256; p->totalGlobalMem = (size_t)16 << 30; return hipSuccess; }
 inline hipError_t hipMemGetInfo(size_t *f, size_t *t) { *f = (size_t)2 << 30; *t = (size_t)16 << 30; return hipSuccess; }
-inline hipError_t hipMalloc(void **p, size_t n) { fakehip::api_call(); *p = nullptr; if (posix_memalign(p, 256, n ? n : 256)) return hipErrorOutOfMemory; return hipSuccess; }
-inline hipError_t hipFree(void *p) { fakehip::pump(true); free(p); return hipSuccess; }
+inline hipError_t hipMalloc(void **p, size_t n) { fakehip::api_call(); fakehip::trace("malloc %zu", n); *p = nullptr; if (posix_memalign(p, 256, n ? n : 256)) return hipErrorOutOfMemory; fakehip::st().sizes[*p] = n; return hipSuccess; }
+inline hipError_t hipFree(void *p) { fakehip::pump(true); fakehip::trace("free %zu", fakehip::st().sizes[p]); fakehip::st().sizes.erase(p); free(p); return hipSuccess; }
 inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { fakehip::api_call(); *p = nullptr; if (posix_memalign(p, 256, n ? n : 256)) return hipErrorOutOfMemory; fakehip::st().pinned[(const char *)*p] = n; return hipSuccess; }
 inline hipError_t hipHostFree(void *p) { fakehip::pump(true); fakehip::st().pinned.erase((const char *)p); free(p); return hipSuccess; }
 inline hipError_t hipHostRegister(void *p, size_t n, unsigned) { fakehip::st().pinned[(const char *)p] = n; return hipSuccess; }
@@ -102,36 +118,39 @@ inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t *a, const void *
   a->type = hipMemoryTypeUnregistered; a->devicePointer = nullptr; a->hostPointer = (void *)p; a->device = 0;
   return hipErrorInvalidValue;     // (as the runtime answers for pageable memory)
 }
-inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = new fakehip::Stream; fakehip::st().streams.push_back(*s); return hipSuccess; }
+inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s = new fakehip::Stream; (*s)->id = fakehip::st().n_streams++; fakehip::st().streams.push_back(*s); return hipSuccess; }
 inline hipError_t hipStreamDestroy(hipStream_t s) {
   fakehip::drain_stream(s);
   auto &v = fakehip::st().streams;
   for (size_t i = 0; i < v.size(); ++i) if (v[i] == s) { v.erase(v.begin() + (long)i); break; }
   delete s; return hipSuccess;
 }
-inline hipError_t hipStreamSynchronize(hipStream_t s) { fakehip::api_call(); fakehip::drain_stream(s); return hipSuccess; }
+inline hipError_t hipStreamSynchronize(hipStream_t s) { fakehip::api_call(); fakehip::trace("stream_sync stream %d", s->id); fakehip::drain_stream(s); return hipSuccess; }
 inline hipError_t hipStreamQuery(hipStream_t s) { fakehip::api_call(); return s->q.empty() ? hipSuccess : hipErrorNotReady; }
-inline hipError_t hipEventCreate(hipEvent_t *e) { *e = new fakehip::Event; return hipSuccess; }
+inline hipError_t hipEventCreate(hipEvent_t *e) { *e = new fakehip::Event; (*e)->id = fakehip::st().n_events++; return hipSuccess; }
 inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
 inline hipError_t hipEventDestroy(hipEvent_t e) { fakehip::pump(true); delete e; return hipSuccess; }
 inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
   fakehip::api_call();
+  fakehip::trace("event_record event %d stream %d", e->id, s->id);
   const uint64_t g = ++e->gen;
   fakehip::enqueue(s, [e, g]() { e->done_gen = g; e->t_ms = fakehip::now_ms(); });
   return hipSuccess;
 }
 inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
   fakehip::api_call();
+  fakehip::trace("stream_wait_event event %d stream %d", e->id, s->id);
   fakehip::enqueue(s, []() {}, e, e->gen);     // (a no-op that cannot run before the record it names has)
   return hipSuccess;
 }
-inline hipError_t hipEventSynchronize(hipEvent_t e) { fakehip::api_call(); while (e->done_gen < e->gen) fakehip::pump(true); return hipSuccess; }
+inline hipError_t hipEventSynchronize(hipEvent_t e) { fakehip::api_call(); fakehip::trace("event_sync event %d", e->id); while (e->done_gen < e->gen) fakehip::pump(true); return hipSuccess; }
 inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t a, hipEvent_t b) { *ms = (float)(b->t_ms - a->t_ms); if (*ms < 0.0f) *ms = 0.0f; return hipSuccess; }
-inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t st_) {
+inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind kind, hipStream_t st_) {
   fakehip::api_call();
+  fakehip::trace("memcpy_async %zu kind %d stream %d", n, (int)kind, st_->id);
   fakehip::enqueue(st_, [=]() { memmove(d, s, n); });
   return hipSuccess;
 }
-inline hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t st_) { fakehip::api_call(); fakehip::enqueue(st_, [=]() { memset(d, v, n); }); return hipSuccess; }
+inline hipError_t hipMemsetAsync(void *d, int v, size_t n, hipStream_t st_) { fakehip::api_call(); fakehip::trace("memset_async %zu stream %d", n, st_->id); fakehip::enqueue(st_, [=]() { memset(d, v, n); }); return hipSuccess; }
 inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { fakehip::api_call(); fakehip::pump(true); memmove(d, s, n); return hipSuccess; }
 inline hipError_t hipMemset(void *d, int v, size_t n) { fakehip::api_call(); fakehip::pump(true); memset(d, v, n); return hipSuccess; }
