@@ -25,6 +25,7 @@
 #include "rfid_tracks.hpp"
 #include "rfid_quality.hpp"
 #include "rfid_repair.hpp"
+#include "rfid_slots.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
 // the launch list of the long-stream front end, on the stream named by the enclosing scope's `ls2_stream`
@@ -290,7 +291,7 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
-  // ---- the stages behind a pass: inventory, tracks, quality, repair.  What the four share ----
+  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots.  What the five share ----
   struct Stage {
     void *blk = nullptr;              // one allocation, carved up (stage_alloc)
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
@@ -330,6 +331,14 @@ struct rfid_ctx {
     int n_streams = 0;                // traces it covered
   } rep;
   DevBuf rep_one;                     // rfid_repair_window: the window, its result, the record
+  // ---- slots stage (rfid_batch_plan_slots): lives and dies with the plan; needs the pass's statistics only ----
+  struct Slots : Stage {
+    rfid_window_moments *d_table = nullptr;   // [B_plan][wmax]: the row of a window is its seq
+    int *d_nrows = nullptr;           // [B_plan]: windows before the cut-off
+    int rows = 0;                     // wmax
+    int n_streams = 0;                // traces it covered
+  } slt;
+  DevBuf mom_one;                     // rfid_window_moments_of: the windows, their records
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
   // (rfid_batch_stats ran behind the last decode), the inventory was enqueued behind those statistics, the tracks behind
   // that inventory.  A stage is current only while every stage before it is: one ordered level, moved by mark_current and
@@ -461,7 +470,7 @@ void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
 // `stage` and everything behind it no longer belong to the last pass
 void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
 
-// ---- what the inventory, tracks, quality and repair stages share on the host ----
+// ---- what the inventory, tracks, quality, repair and slots stages share on the host ----
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void stage_free(rfid_ctx::Stage &st) {
@@ -524,11 +533,11 @@ int stage_fetch_head(rfid_ctx *c, const char *fn, const int *d_reads_head, int64
   return RFID_OK;
 }
 
-// One trace's rows of a stage's table (quality, repair: one record per EPC window, `rows` of them per trace).  *n: the EPC
-// windows before the cut-off (d_nrows).  RFID_ERR_CAPACITY under `fn`'s name when `cap` is smaller than that; else up to
-// `cap` rows are copied.
+// One trace's rows of a stage's table (quality, repair: one record per EPC window; slots: one per window -- `what`; `rows` of
+// them per trace).  *n: those before the cut-off (d_nrows).  RFID_ERR_CAPACITY under `fn`'s name when `cap` is smaller than
+// that; else up to `cap` rows are copied.
 int stage_fetch_rows(rfid_ctx *c, const char *fn, const int *d_nrows, const void *table, size_t record_bytes, int rows, int n_streams,
-                     int stream, void *out, int64_t cap, int64_t *n) {
+                     int stream, void *out, int64_t cap, int64_t *n, const char *what = "EPC windows") {
   if (stream < 0 || stream >= n_streams) return RFID_ERR_INVALID;
   HIPCHK(c, hipSetDevice(c->device));
   int nrows = 0;
@@ -536,7 +545,7 @@ int stage_fetch_rows(rfid_ctx *c, const char *fn, const int *d_nrows, const void
   HIPCHK(c, hipStreamSynchronize(c->stream));
   *n = nrows;
   if (nrows > cap) {
-    snprintf(c->err, sizeof(c->err), "%s: cap is smaller than the number of EPC windows", fn);
+    snprintf(c->err, sizeof(c->err), "%s: cap is smaller than the number of %s", fn, what);
     return RFID_ERR_CAPACITY;
   }
   const int64_t take = (cap < rows) ? cap : rows;          // (the zeroed rows behind the cut-off too, as far as there is room)
@@ -688,6 +697,11 @@ void free_repair(rfid_ctx *c) {
   c->rep.rows = 0; c->rep.blocks = 0;
 }
 
+void free_slots(rfid_ctx *c) {
+  stage_free(c->slt);
+  c->slt.rows = 0;
+}
+
 void free_inventory(rfid_ctx *c) {
   free_tracks(c);                      // (sized by this workspace, and reading it)
   free_repair(c);                      // (reading it)
@@ -698,6 +712,7 @@ void free_inventory(rfid_ctx *c) {
 
 void free_plan(rfid_ctx *c) {
   free_inventory(c);
+  free_slots(c);
   invalidate_from(c, rfid_ctx::CUR_STATS);
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
@@ -1196,13 +1211,14 @@ int rfid_ctx_destroy(rfid_ctx *c) {
   la_free(c);
   sio_free(c);
   free_plan(c);
-  void *ptrs[] = {c->d_small, c->s_in.p, c->s_out.p, c->synth_tab.p, c->ls2_ws.p, c->ls2_ws_alt.p, c->rep_one.p};
+  void *ptrs[] = {c->d_small, c->s_in.p, c->s_out.p, c->synth_tab.p, c->ls2_ws.p, c->ls2_ws_alt.p, c->rep_one.p, c->mom_one.p};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->ls2_host) (void)hipHostFree(c->ls2_host);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);
-  for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep})
+  for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep,
+                               (rfid_ctx::Stage *)&c->slt})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
@@ -1939,6 +1955,78 @@ int rfid_repair_window(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_re
                      (rfid_repair *)(b + sz_w + sz_r));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
+}
+
+// ---- slots stage: the second-order moments of every window, behind the statistics of a pass (csrc/rfid_slots.hpp) ----
+int rfid_batch_plan_slots(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  if (!c->B_plan) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_slots: no plan (rfid_batch_plan)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  rfid_ctx::Slots &p = c->slt;
+  free_slots(c);
+  const int r = stage_alloc(c, p, "rfid_batch_plan_slots: workspace allocation",
+                            {{(void **)&p.d_table, sizeof(rfid_window_moments) * (size_t)c->wmax * (size_t)c->B_plan},
+                             {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan}});
+  if (r) return r;
+  p.rows = c->wmax;
+  return RFID_OK;
+}
+
+int rfid_batch_slots(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Slots &p = c->slt;
+  if (!c->B || !p.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_slots: no plan with a slots workspace (rfid_batch_plan_slots)");
+  if (c->current < rfid_ctx::CUR_STATS) return fail(c, RFID_ERR_STATE, "rfid_batch_slots: no pass with statistics yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  // as rfid_batch_quality: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
+  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
+  { int rj = join_tails(c); if (rj) return rj; }
+  const int n = c->B;
+  MomArgs a;
+  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->cur.d_wtab; a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats;
+  a.wmax = c->wmax; a.n_streams = n; a.table = p.d_table; a.nrows = p.d_nrows;
+  { int r = stage_record(c, p, 0); if (r) return r; }
+  // single-wave workgroups, each walking packs of eight rows (15.7 KB of LDS each)
+  const int64_t items = (int64_t)n * ((p.rows + MOM_PACK - 1) / MOM_PACK);
+  hipLaunchKernelGGL(moments_kernel, persistent_grid(items, (int64_t)c->n_cus * MOM_WGS_PER_CU), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  { int r = stage_record(c, p, 1); if (r) return r; }
+  { int r = y_read_again(c); if (r) return r; }
+  p.enqueued = true;
+  p.n_streams = n;
+  return RFID_OK;
+}
+
+int rfid_batch_get_window_moments(rfid_ctx *c, int stream, rfid_window_moments *out, int64_t cap, int64_t *n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
+  rfid_ctx::Slots &p = c->slt;
+  if (!p.blk || !p.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_moments: no rfid_batch_slots behind this plan");
+  return stage_fetch_rows(c, "rfid_batch_get_window_moments", p.d_nrows, p.d_table, sizeof(rfid_window_moments), p.rows, p.n_streams, stream, out, cap, n,
+                          "windows");
+}
+
+int rfid_batch_slots_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  return stage_ms(c, c->slt, ms);
+}
+
+// the per-call form: windows in host memory through the batch kernel's device function (one launch, synchronising)
+int rfid_window_moments_of(rfid_ctx *c, const rfid_cf32 *gated, int n_windows, rfid_window_moments *out) {
+  if (!c || n_windows < 0 || (n_windows > 0 && (!gated || !out))) return RFID_ERR_INVALID;
+  if (n_windows == 0) return RFID_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_in = up256(sizeof(float2) * (size_t)MOM_N * (size_t)n_windows), sz_out = sizeof(rfid_window_moments) * (size_t)n_windows;
+  { int r = grow(c, c->mom_one, sz_in + sz_out); if (r) return r; }
+  char *b = (char *)c->mom_one.p;
+  HIPCHK(c, hipMemcpyAsync(b, gated, sizeof(float2) * (size_t)MOM_N * (size_t)n_windows, hipMemcpyHostToDevice, c->stream));
+  const int64_t packs = ((int64_t)n_windows + MOM_PACK - 1) / MOM_PACK;
+  hipLaunchKernelGGL(moments_of_kernel, persistent_grid(packs, (int64_t)c->n_cus * MOM_WGS_PER_CU), dim3(64), 0, c->stream,
+                     (const float2 *)b, n_windows, (rfid_window_moments *)(b + sz_in));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_in, sz_out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
 }

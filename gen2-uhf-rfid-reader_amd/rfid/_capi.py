@@ -86,6 +86,10 @@ REPAIR_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("
                          ("flips", "<i4"), ("cost", "<f4"), ("entry", "<i4"), ("frame", "<u4", (4,))])
 REPAIR_CANDIDATES, REPAIR_MAX_FLIPS = 8, 3
 assert REPAIR_DTYPE.itemsize == 48
+MOMENTS_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("sx", "<f4"), ("sy", "<f4"), ("sxx", "<f4"), ("sxy", "<f4"),
+                          ("syy", "<f4"), ("flags", "<i4")])
+MOMENTS_SAMPLES = 240
+assert MOMENTS_DTYPE.itemsize == 32
 assert WINDOW_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 48
 assert SCORES_DTYPE.itemsize == 144 and STATS_DTYPE.itemsize == 1056
 
@@ -161,6 +165,11 @@ SIGNATURES = {
     "rfid_batch_get_window_repairs": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_repair_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_repair_window": (_i, [_vp, _vp, _vp, _vp]),
+    "rfid_batch_plan_slots": (_i, [_vp]),
+    "rfid_batch_slots": (_i, [_vp]),
+    "rfid_batch_get_window_moments": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_slots_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_window_moments_of": (_i, [_vp, _vp, _i, _vp]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

@@ -47,6 +47,8 @@ class BatchDecoder:
         self.last_quality = None      # one record per read, aligned with last_tracks[0], of the last decode(..., quality=True)
         self._rep_planned = False
         self.last_repairs = None      # the repaired windows, ordered by (stream, seq), of the last decode(..., repair=True)
+        self._slots_planned = False
+        self.last_slots = None        # one moments array per trace (every window before the cut-off) of the last decode(..., slots=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -61,6 +63,7 @@ class BatchDecoder:
             self._trk_planned = False
             self._qual_planned = False
             self._rep_planned = False
+            self._slots_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -71,7 +74,7 @@ class BatchDecoder:
 
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
                inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False,
-               repair: bool = False):
+               repair: bool = False, slots: bool = False):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
@@ -84,7 +87,9 @@ class BatchDecoder:
         `self.ctx.batch_window_quality(stream)`.  repair=True (implies inventory=True): the CRC-failed EPC windows that
         reversing one to three of their eight weakest decisions makes pass are searched behind the inventory;
         `self.last_repairs` keeps their records (capi.REPAIR_DTYPE, ordered by (stream, seq)); a repair is not a read and
-        changes nothing else; a trace's whole row: `self.ctx.batch_window_repairs(stream)`."""
+        changes nothing else; a trace's whole row: `self.ctx.batch_window_repairs(stream)`.  slots=True (implies nothing):
+        the second-order moments of every window, RN16 and EPC alike, are worked out behind the pass; `self.last_slots` keeps
+        one capi.MOMENTS_DTYPE array per trace (classify_slots() turns it into empty / single / collided per slot)."""
         torch = self._torch
         n = len(traces)
         lens = np.array([len(t) for t in traces], dtype=np.int64)
@@ -119,6 +124,9 @@ class BatchDecoder:
         if quality and not self._qual_planned:
             self.ctx.batch_plan_quality()
             self._qual_planned = True
+        if slots and not self._slots_planned:
+            self.ctx.batch_plan_slots()
+            self._slots_planned = True
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
         if inventory:
             self.ctx.batch_inventory_enqueue()
@@ -128,6 +136,8 @@ class BatchDecoder:
             self.ctx.batch_quality_enqueue()
         if repair:
             self.ctx.batch_repair_enqueue()
+        if slots:
+            self.ctx.batch_slots_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
@@ -138,6 +148,8 @@ class BatchDecoder:
             self.last_quality = self.ctx.batch_quality_fetch()
         if repair:
             self.last_repairs = self.ctx.batch_repair_fetch()
+        if slots:
+            self.last_slots = [self.ctx.batch_window_moments(b) for b in range(n)]
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -304,8 +316,107 @@ def format_repairs(repairs: np.ndarray, names: Sequence[str]) -> str:
     return "\n".join(lines) + "\n"
 
 
+MOMENTS_N = 240           # RFID_MOMENTS_SAMPLES: the samples of a window its moments are taken over
+SLOT_EMPTY, SLOT_SINGLE, SLOT_COLLIDED, SLOT_UNKNOWN = 0, 1, 2, -1
+SCHOUTE = 2.39            # Schoute's estimate of the tags behind a collided slot of a framed-ALOHA round
+SLOT_DTYPE = np.dtype([("seq", "<i4"), ("cls", "<i4"), ("answered", "<i4"), ("crc_ok", "<i4"), ("l1", "<f8"), ("l2", "<f8"),
+                       ("floor", "<f8")])
+SLOTS_HEADER = "file,slot,seq,t_s,class,l1_db,l2_db,floor_db,answered,crc_ok"
+
+
+def moment_fields(rows: np.ndarray):
+    """rfid_window_moments records -> (l1, l2), float64 arrays: the eigenvalues l1 >= l2 >= 0 of the windows' 2 x 2 scatter
+    matrices, per sample.  With n = 240: cxx = sxx - sx^2 / n, cyy = syy - sy^2 / n, cxy = sxy - sx sy / n, tr = cxx + cyy,
+    d = hypot(cxx - cyy, 2 cxy), l1 = (tr + d) / 2 / n, l2 = max((tr - d) / 2, 0) / n."""
+    rows = np.asarray(rows)
+    n = float(MOMENTS_N)
+    sx, sy = rows["sx"].astype(np.float64), rows["sy"].astype(np.float64)
+    cxx = rows["sxx"].astype(np.float64) - sx * sx / n
+    cyy = rows["syy"].astype(np.float64) - sy * sy / n
+    cxy = rows["sxy"].astype(np.float64) - sx * sy / n
+    tr, d = cxx + cyy, np.hypot(cxx - cyy, 2.0 * cxy)
+    return (tr + d) / 2.0 / n, np.maximum((tr - d) / 2.0, 0.0) / n
+
+
+def classify_slots(rows: np.ndarray, empty_k: float = 3.0, collided_k: float = 3.0) -> np.ndarray:
+    """One trace's moments (Context.batch_window_moments: every window before the cut-off, in seq order) -> one SLOT_DTYPE
+    record per slot.  Slot k is rows 2k (its RN16 window) and 2k + 1 (its EPC window); a last RN16 without its EPC is left out.
+    floor: the median l2 over the trace's EPC rows -- the minor eigenvalue of an EPC window is noise whether the slot was
+    empty, single or collided (a floor from the RN16 windows breaks down once most slots collide).  cls: SLOT_EMPTY when the
+    RN16 window's l1 <= empty_k floor, else SLOT_COLLIDED when its l2 > collided_k floor, else SLOT_SINGLE; answered: the
+    EPC window's l1 > empty_k floor (somebody answered the ACK); crc_ok: of the EPC window; seq, l1, l2: the RN16 window's.
+    A floor that is 0 or not finite (a noise-free trace): cls = SLOT_UNKNOWN for every slot.  The defaults are "three times
+    the noise floor": at sigma = 0.03 empty slots stay below 1.93 floors and occupied ones above 22 (l1), single replies below
+    1.55 and collided ones above 4.8 (l2)."""
+    rows = np.asarray(rows)
+    n_slots = len(rows) // 2
+    out = np.zeros(n_slots, dtype=SLOT_DTYPE)
+    if n_slots == 0:
+        return out
+    l1, l2 = moment_fields(rows[: 2 * n_slots])
+    rn_l1, rn_l2, epc_l1, epc_l2 = l1[0::2], l2[0::2], l1[1::2], l2[1::2]
+    floor = float(np.median(epc_l2))
+    out["seq"] = rows["seq"][0: 2 * n_slots: 2]
+    out["crc_ok"] = rows["flags"][1: 2 * n_slots: 2] & 1
+    out["l1"], out["l2"], out["floor"] = rn_l1, rn_l2, floor
+    if not (np.isfinite(floor) and floor > 0.0):
+        out["cls"] = SLOT_UNKNOWN
+        return out
+    out["cls"] = np.where(rn_l1 <= empty_k * floor, SLOT_EMPTY, np.where(rn_l2 > collided_k * floor, SLOT_COLLIDED, SLOT_SINGLE))
+    out["answered"] = epc_l1 > empty_k * floor
+    return out
+
+
+def estimate_population(cls, n_rounds: int) -> float:
+    """Schoute's estimate of the tags in the field, per inventory round: (singles + 2.39 collided) / rounds."""
+    cls = np.asarray(cls)
+    if n_rounds <= 0:
+        return 0.0
+    return (float((cls == SLOT_SINGLE).sum()) + SCHOUTE * float((cls == SLOT_COLLIDED).sum())) / float(n_rounds)
+
+
+def suggest_q(n: float) -> int:
+    """The Q whose 2^Q slots per round suit n tags best: clamp(round(log2(max(n, 1))), 0, 15)."""
+    return int(min(max(int(round(float(np.log2(max(float(n), 1.0))))), 0), 15))
+
+
+def format_slots(slots: np.ndarray, fixed_q: int) -> str:
+    """One line for one trace's slots (classify_slots): how many there are, how many were empty / single / collided, in how
+    many the ACK was answered, how many gave a CRC-verified read, the efficiency (reads per slot), the estimated tags per
+    round (rounds = slots / 2^Q, rounded up) and the Q that would suit them beside the Q in use."""
+    slots = np.asarray(slots)
+    n = len(slots)
+    cls = slots["cls"]
+    read = int((slots["crc_ok"] != 0).sum())
+    if n and (cls == SLOT_UNKNOWN).all():
+        return "| slots : %d  not classified (no noise floor)  read : %d  efficiency : %.3f\n" % (n, read, read / n)
+    rounds = -(-n // (1 << int(fixed_q)))
+    est = estimate_population(cls, rounds)
+    return ("| slots : %d  empty : %d  single : %d  collided : %d  answered : %d  read : %d  efficiency : %.3f  "
+            "tags per round : %.2f  suggested Q : %d (in use : %d)\n" %
+            (n, int((cls == SLOT_EMPTY).sum()), int((cls == SLOT_SINGLE).sum()), int((cls == SLOT_COLLIDED).sum()),
+             int((slots["answered"] != 0).sum()), read, (read / n) if n else 0.0, est, suggest_q(est), int(fixed_q)))
+
+
+def format_slots_csv(slots: Sequence[np.ndarray], starts: Sequence[np.ndarray], names: Sequence[str]) -> str:
+    """CSV text, one line per slot, by trace, then by slot: file,slot,seq,t_s,class,l1_db,l2_db,floor_db,answered,crc_ok.
+    slots[b]: classify_slots of trace b; starts[b][seq]: rfid_window::start of its windows; names[b]: its file.  seq is the
+    slot's RN16 window, t_s = start / 400e3 as in the tracks CSV, class one of empty / single / collided / unknown, the three
+    levels 10 log10 of l1, l2 (the RN16 window's) and the floor, printed with %.9g."""
+    label = {SLOT_EMPTY: "empty", SLOT_SINGLE: "single", SLOT_COLLIDED: "collided", SLOT_UNKNOWN: "unknown"}
+    lines = [SLOTS_HEADER]
+    with np.errstate(divide="ignore"):
+        for b, (rec, name) in enumerate(zip(slots, names)):
+            for k, r in enumerate(rec):
+                db = [10.0 * np.log10(np.float64(r[f])) for f in ("l1", "l2", "floor")]
+                lines.append("%s,%d,%d,%.9g,%s,%.9g,%.9g,%.9g,%d,%d" %
+                             (name, k, int(r["seq"]), int(starts[b][int(r["seq"])]) / TRACKS_RATE, label[int(r["cls"])],
+                              float(db[0]), float(db[1]), float(db[2]), int(r["answered"]), int(r["crc_ok"])))
+    return "\n".join(lines) + "\n"
+
+
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -322,14 +433,18 @@ def main(argv=None) -> int:
     ap.add_argument("--repair", metavar="OUT.csv", default=None,
                     help="search the CRC-failed EPC windows for one to three weak decisions whose reversal makes the frame pass "
                          "(built on the device); one line per file, the repaired windows to this CSV file; implies --inventory")
+    ap.add_argument("--slots", metavar="OUT.csv", default=None,
+                    help="classify every slot as empty, single or collided from the second-order moments of its windows (built "
+                         "on the device); one line per file, the slots to this CSV file")
     args = ap.parse_args(argv)
     if args.tracks or args.repair:
         args.inventory = True
     dec = BatchDecoder(device=args.device, fixed_q=args.fixed_q, max_num_queries=args.max_queries)
     try:
         timing = {}
-        stats, _, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
-                                            tracks=bool(args.tracks), quality=args.quality, repair=bool(args.repair))
+        stats, windows, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
+                                            tracks=bool(args.tracks), quality=args.quality, repair=bool(args.repair),
+                                            slots=bool(args.slots))
         for i, (path, row) in enumerate(zip(args.files, stats)):
             print(path)
             print(format_results(row), end="")
@@ -337,6 +452,8 @@ def main(argv=None) -> int:
                 print(format_quality(dec.ctx.batch_window_quality(i)), end="")
             if args.repair:
                 print(format_repair_summary(dec.ctx.batch_window_repairs(i)), end="")
+            if args.slots:
+                print(format_slots(classify_slots(dec.last_slots[i]), args.fixed_q), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
               (len(args.files), timing["raw_samples"] / 1e6, timing["total_s"], timing["h2d_s"], timing["gpu_s"]))
         if args.inventory:
@@ -356,6 +473,10 @@ def main(argv=None) -> int:
         if args.repair:
             with open(args.repair, "w") as f:
                 f.write(format_repairs(dec.last_repairs, args.files))
+        if args.slots:
+            starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
+            with open(args.slots, "w") as f:
+                f.write(format_slots_csv([classify_slots(m) for m in dec.last_slots], starts, args.files))
     finally:
         dec.close()
     return 0

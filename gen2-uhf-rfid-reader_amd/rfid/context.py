@@ -436,6 +436,39 @@ class Context:
         self._chk(self._lib.rfid_repair_window(self._h, gated.ctypes.data, res.ctypes.data, out.ctypes.data))
         return out[0]
 
+    def batch_plan_slots(self) -> None:
+        """Reserves the slots workspace of the current plan (a new plan drops it; it needs none of the other workspaces)."""
+        self._chk(self._lib.rfid_batch_plan_slots(self._h))
+
+    def batch_slots_enqueue(self) -> None:
+        """Asynchronous: the second-order moments of every window of the last pass, behind its statistics
+        (rfid_batch_slots)."""
+        self._chk(self._lib.rfid_batch_slots(self._h))
+
+    def batch_window_moments(self, stream: int, extra: int = 0) -> np.ndarray:
+        """One trace's row of the moments table (synchronises): the capi.MOMENTS_DTYPE record of EVERY window before the
+        cut-off, RN16 and EPC alike, in seq order (n_windows_used of them), of the last batch_slots_enqueue.  extra > 0: up
+        to that many of the table's rows behind them as well (zeroed by the stage).  rfid.batch.classify_slots turns a row
+        into one record per slot."""
+        return self._sized_fetch(self._lib.rfid_batch_get_window_moments, capi.MOMENTS_DTYPE, head=(int(stream),),
+                                 extra=max(int(extra), 0))
+
+    def batch_slots_ms(self) -> float:
+        return self._stage_ms(self._lib.rfid_batch_slots_ms)
+
+    def window_moments(self, gated) -> np.ndarray:
+        """The same sums for windows in host memory (rfid_window_moments_of): gated = [n_windows][240] gated, DC-free samples
+        (the first 240 of each window the gate handed out).  -> capi.MOMENTS_DTYPE records, stream = 0, seq = the window's
+        position, flags = 0."""
+        gated = np.ascontiguousarray(gated, dtype=np.complex64)
+        if gated.ndim == 1:
+            gated = gated.reshape(-1, capi.MOMENTS_SAMPLES) if len(gated) else gated.reshape(0, capi.MOMENTS_SAMPLES)
+        if gated.ndim != 2 or gated.shape[1] != capi.MOMENTS_SAMPLES:
+            raise ValueError("the moments of a window are taken over 240 samples")
+        out = np.zeros(len(gated), dtype=capi.MOMENTS_DTYPE)
+        self._chk(self._lib.rfid_window_moments_of(self._h, gated.ctypes.data, len(gated), out.ctypes.data))
+        return out
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

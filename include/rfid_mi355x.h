@@ -40,7 +40,7 @@ extern "C" {
 #endif
 
 #define RFID_API __attribute__((visibility("default")))
-#define RFID_MI355X_ABI 6   /* see rfid_abi_version() */
+#define RFID_MI355X_ABI 7   /* see rfid_abi_version() */
 
 typedef enum rfid_status {
   RFID_OK = 0,
@@ -209,6 +209,30 @@ typedef struct rfid_repair {         /* 48 bytes */
   uint32_t frame[4];                 /* the repaired frame, packed as rfid_decode_result::bits; zeros when n_flips == 0 */
 } rfid_repair;
 
+/* the second-order moments of one window's gated samples: what the slots stage (rfid_batch_slots, rfid_window_moments_of)
+ * works out for EVERY window before the TERMINATED cut-off, RN16 and EPC alike.  The reference ACKs every slot, so a
+ * FIXED_Q > 0 trace yields an RN16 / EPC window pair per slot whatever was on the air; the moments tell an empty slot (an
+ * isotropic noise blob) from a single reply (samples on a line along h) from a collision (samples spread over a plane).
+ * THE DEFINITION (the contract; binary32 throughout, every operation rounded by itself, no fused multiply-add):
+ *   for i = 0 .. RFID_MOMENTS_SAMPLES - 1:
+ *     x_i = y[start + i].x - dc_re,  y_i = y[start + i].y - dc_im
+ *   (y: the matched filter's output of the pass, start / dc: the window's rfid_window -- the gate's output samples), and the
+ *   five sums are IN-ORDER sums (((0.0f + t_0) + t_1) + ...) + t_239 of t_i = x_i, y_i, x_i * x_i, x_i * y_i, y_i * y_i.  They
+ *   start from 0.0f: a first term of -0.0 gives +0.0.  A record is a function of the input alone and is compared by bit
+ *   pattern.  (A window with a non-finite sample: unspecified.)
+ * 240 samples fit both window kinds: an RN16 reply ends by sample 244 of its 250; of an EPC window the preamble and the first
+ * 17 bits are used.
+ * What a host makes of it (rfid.batch.moment_fields / classify_slots, in binary64): the eigenvalues l1 >= l2 of the scatter
+ * matrix per sample; the median l2 of a trace's EPC windows is its noise floor -- noise whether the slot was empty, single or
+ * collided. */
+#define RFID_MOMENTS_SAMPLES 240
+typedef struct rfid_window_moments {   /* 32 bytes */
+  int32_t stream, seq;                 /* the window (rfid_window::stream / seq); type = seq & 1 */
+  float   sx, sy;                      /* sum x_i, sum y_i */
+  float   sxx, sxy, syy;               /* sum x_i*x_i, sum x_i*y_i, sum y_i*y_i */
+  int32_t flags;                       /* bit 0: crc_ok of the window's result (0 for RN16); bit 1: the window is an EPC window */
+} rfid_window_moments;
+
 /* timing of the last rfid_batch_* pass, from HIP events on the ctx stream */
 typedef struct rfid_batch_timing {
   float mf_ms, gate_ms, decode_ms, stats_ms; /* kernel time per pass (summed over the launches of a pass) */
@@ -263,7 +287,7 @@ RFID_API const char *rfid_strerror(int status);
 RFID_API const char *rfid_last_error(const rfid_ctx *ctx);
 RFID_API const char *rfid_version(void);
 /* RFID_MI355X_ABI of the library that was loaded: it changes whenever a struct of this header changes size or layout
- * (4: rfid_ls_report has 13 fields since round 3; 5: its last field is dc_finished since round 6; 6: rfid_repair and the repair stage).  A caller built against another value must not pass structs. */
+ * (4: rfid_ls_report has 13 fields since round 3; 5: its last field is dc_finished since round 6; 6: rfid_repair and the repair stage; 7: rfid_window_moments and the slots stage).  A caller built against another value must not pass structs. */
 RFID_API int rfid_abi_version(void);
 /* device self-test of the wave-level primitives the kernels rely on (DPP wave shift,
  * IEEE division, double sqrt).  0 = all good, >0 = number of failing checks. */
@@ -611,6 +635,32 @@ RFID_API int rfid_batch_repair_ms(rfid_ctx *ctx, float *ms);
  * device function, synchronising.  out: stream = seq = start = 0, entry = -1; flags bit 0 = res->crc_ok (then nothing is
  * searched). */
 RFID_API int rfid_repair_window(rfid_ctx *ctx, const rfid_cf32 *gated, const rfid_decode_result *res, rfid_repair *out);
+/* ---- (2f) batch slots: the second-order moments of every window, built on the device ---------------------------------- */
+/* Behind a pass: one rfid_window_moments (see its definition above) per window with seq < n_windows_used, RN16 and EPC
+ * alike, in a device table [n_streams][wmax] (row = seq; the rows of a trace behind its cut-off are zeroed: the table's
+ * bytes repeat from pass to pass).  Nothing else a pass reports changes.  rfid_batch_plan_slots reserves the table (32 bytes
+ * per possible window).  RFID_ERR_STATE without a plan; RFID_ERR_HIP when the allocation fails (the plan and every other
+ * workspace stay usable).  A new rfid_batch_plan drops it; it neither needs nor drops the inventory, tracks, quality and
+ * repair workspaces, and their plan calls do not drop it. */
+RFID_API int rfid_batch_plan_slots(rfid_ctx *ctx);
+/* enqueues the moments of the LAST pass behind its statistics (asynchronous, no host synchronisation).  RFID_ERR_STATE: no
+ * slots workspace, or no pass with statistics yet.  It needs no inventory and may be enqueued before or behind the other
+ * stages.  It reads that pass's matched-filter output, window table, results and statistics on the context's main stream
+ * and has rfid_batch_quality's duties there: with two result sets alternating it reads the set of that pass, and it records
+ * the long-stream front end's "free" event of the matched-filter buffer again behind its own launch. */
+RFID_API int rfid_batch_slots(rfid_ctx *ctx);
+/* synchronises; one trace's row of the table: every window before the cut-off in seq order: *n = n_windows_used.  cap as
+ * rfid_batch_get_window_quality: RFID_ERR_CAPACITY when cap < *n (nothing is copied; out may be NULL with cap = 0); with
+ * cap > *n the zeroed rows behind *n are copied too, up to min(cap, wmax) in all.  RFID_ERR_STATE before the first
+ * rfid_batch_slots of this plan. */
+RFID_API int rfid_batch_get_window_moments(rfid_ctx *ctx, int stream, rfid_window_moments *out, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_slots (HIP events) */
+RFID_API int rfid_batch_slots_ms(rfid_ctx *ctx, float *ms);
+/* the same sums for windows in host memory: the per-call form for callers that hold gated samples themselves.  gated:
+ * n_windows x RFID_MOMENTS_SAMPLES samples that are already DC-free -- the first 240 of what rfid_gate_work /
+ * rfid_stream_work hand out per window (dc = 0 in the definition).  One launch of the batch kernel's device function,
+ * synchronising.  out[k]: stream = 0, seq = k, flags = 0. */
+RFID_API int rfid_window_moments_of(rfid_ctx *ctx, const rfid_cf32 *gated, int n_windows, rfid_window_moments *out);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
