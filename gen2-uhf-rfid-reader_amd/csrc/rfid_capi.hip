@@ -26,6 +26,7 @@
 #include "rfid_quality.hpp"
 #include "rfid_repair.hpp"
 #include "rfid_slots.hpp"
+#include "rfid_commands.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
 // the launch list of the long-stream front end, on the stream named by the enclosing scope's `ls2_stream`
@@ -76,6 +77,7 @@ struct RfidKnobs {
   int la_upload_kernel = 1;  // RFID_LA_UPLOAD_KERNEL  look-ahead: 1 a call's samples are fetched from page-locked memory by a launch, 0 by a transfer
   int front_lds_kb = -1;   // RFID_LS_FRONT_LDS_KB   0..64: extra LDS per workgroup of the long-stream first pass (caps its waves per CU); -1: 10 for long traces
   int inventory_slots = 0; // RFID_INVENTORY_SLOTS   2..1024 (a power of two): table slots per trace of the inventory stage, read by rfid_batch_plan_inventory (0: the next power of two >= 2 x max_tags_per_trace).  A small table makes frames collide: the stage's later rounds
+  int commands_rows = 0;   // RFID_COMMANDS_ROWS     1..16: rows per wave and step of the commands stage (0: one while the launch has a wave per row, then the next powers of two up to 16)
 };
 
 // the timing events of a pass: stage i of the four took the time from event i to event i + 1
@@ -291,7 +293,7 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
-  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots.  What the five share ----
+  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands.  What the six share ----
   struct Stage {
     void *blk = nullptr;              // one allocation, carved up (stage_alloc)
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
@@ -339,6 +341,14 @@ struct rfid_ctx {
     int n_streams = 0;                // traces it covered
   } slt;
   DevBuf mom_one;                     // rfid_window_moments_of: the windows, their records
+  // ---- commands stage (rfid_batch_plan_commands): lives and dies with the plan; needs the pass's statistics only ----
+  struct Commands : Stage {
+    rfid_command *d_table = nullptr;  // [B_plan][wmax]: the row of a window is its seq
+    int *d_nrows = nullptr;           // [B_plan]: windows before the cut-off
+    int rows = 0;                     // wmax
+    int n_streams = 0;                // traces it covered
+  } cmd;
+  DevBuf cmd_one;                     // rfid_commands_of: the spans, their levels, their records
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
   // (rfid_batch_stats ran behind the last decode), the inventory was enqueued behind those statistics, the tracks behind
   // that inventory.  A stage is current only while every stage before it is: one ordered level, moved by mark_current and
@@ -387,6 +397,7 @@ const KnobEntry g_knob_table[] = {
   {"la_upload_kernel", "RFID_LA_UPLOAD_KERNEL", &RfidKnobs::la_upload_kernel, 0, 1},
   {"front_lds_kb", "RFID_LS_FRONT_LDS_KB", &RfidKnobs::front_lds_kb, -1, 64},
   {"inventory_slots", "RFID_INVENTORY_SLOTS", &RfidKnobs::inventory_slots, 0, 1024},
+  {"commands_rows", "RFID_COMMANDS_ROWS", &RfidKnobs::commands_rows, 0, CMD_ROWS},
 };
 int clamp_int(long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 // the environment, once per context: values out of range are clamped, anything that is not a number is ignored
@@ -470,7 +481,7 @@ void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
 // `stage` and everything behind it no longer belong to the last pass
 void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
 
-// ---- what the inventory, tracks, quality, repair and slots stages share on the host ----
+// ---- what the inventory, tracks, quality, repair, slots and commands stages share on the host ----
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void stage_free(rfid_ctx::Stage &st) {
@@ -533,7 +544,7 @@ int stage_fetch_head(rfid_ctx *c, const char *fn, const int *d_reads_head, int64
   return RFID_OK;
 }
 
-// One trace's rows of a stage's table (quality, repair: one record per EPC window; slots: one per window -- `what`; `rows` of
+// One trace's rows of a stage's table (quality, repair: one record per EPC window; slots, commands: one per window -- `what`; `rows` of
 // them per trace).  *n: those before the cut-off (d_nrows).  RFID_ERR_CAPACITY under `fn`'s name when `cap` is smaller than
 // that; else up to `cap` rows are copied.
 int stage_fetch_rows(rfid_ctx *c, const char *fn, const int *d_nrows, const void *table, size_t record_bytes, int rows, int n_streams,
@@ -702,6 +713,11 @@ void free_slots(rfid_ctx *c) {
   c->slt.rows = 0;
 }
 
+void free_commands(rfid_ctx *c) {
+  stage_free(c->cmd);
+  c->cmd.rows = 0;
+}
+
 void free_inventory(rfid_ctx *c) {
   free_tracks(c);                      // (sized by this workspace, and reading it)
   free_repair(c);                      // (reading it)
@@ -713,6 +729,7 @@ void free_inventory(rfid_ctx *c) {
 void free_plan(rfid_ctx *c) {
   free_inventory(c);
   free_slots(c);
+  free_commands(c);
   invalidate_from(c, rfid_ctx::CUR_STATS);
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
@@ -1211,14 +1228,14 @@ int rfid_ctx_destroy(rfid_ctx *c) {
   la_free(c);
   sio_free(c);
   free_plan(c);
-  void *ptrs[] = {c->d_small, c->s_in.p, c->s_out.p, c->synth_tab.p, c->ls2_ws.p, c->ls2_ws_alt.p, c->rep_one.p, c->mom_one.p};
+  void *ptrs[] = {c->d_small, c->s_in.p, c->s_out.p, c->synth_tab.p, c->ls2_ws.p, c->ls2_ws_alt.p, c->rep_one.p, c->mom_one.p, c->cmd_one.p};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->ls2_host) (void)hipHostFree(c->ls2_host);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);
   for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep,
-                               (rfid_ctx::Stage *)&c->slt})
+                               (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
@@ -2027,6 +2044,85 @@ int rfid_window_moments_of(rfid_ctx *c, const rfid_cf32 *gated, int n_windows, r
                      (const float2 *)b, n_windows, (rfid_window_moments *)(b + sz_in));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, b + sz_in, sz_out, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
+}
+
+// ---- commands stage: the reader's PIE command in front of every window, behind the statistics of a pass (csrc/rfid_commands.hpp) ----
+int rfid_batch_plan_commands(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  if (!c->B_plan) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_commands: no plan (rfid_batch_plan)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  rfid_ctx::Commands &p = c->cmd;
+  free_commands(c);
+  const int r = stage_alloc(c, p, "rfid_batch_plan_commands: workspace allocation",
+                            {{(void **)&p.d_table, sizeof(rfid_command) * (size_t)c->wmax * (size_t)c->B_plan},
+                             {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan}});
+  if (r) return r;
+  p.rows = c->wmax;
+  return RFID_OK;
+}
+
+int rfid_batch_commands(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Commands &p = c->cmd;
+  if (!c->B || !p.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_commands: no plan with a commands workspace (rfid_batch_plan_commands)");
+  if (c->current < rfid_ctx::CUR_STATS) return fail(c, RFID_ERR_STATE, "rfid_batch_commands: no pass with statistics yet");
+  HIPCHK(c, hipSetDevice(c->device));
+  // as rfid_batch_slots: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
+  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
+  { int rj = join_tails(c); if (rj) return rj; }
+  const int n = c->B;
+  CmdArgs a;
+  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->cur.d_wtab; a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats;
+  a.wmax = c->wmax; a.n_streams = n; a.table = p.d_table; a.nrows = p.d_nrows;
+  { int r = stage_record(c, p, 0); if (r) return r; }
+  // single-wave workgroups, each walking blocks of rows (1 KB of LDS each): one row per block while the launch has a wave for
+  // every row (a block's windows are worked on one after the other), up to sixteen in large batches (where most blocks lie behind
+  // the cut-off and a block's window records come in one round trip)
+  const int64_t most = (int64_t)c->n_cus * CMD_WGS_PER_CU;
+  a.rows_per = c->knobs.commands_rows ? c->knobs.commands_rows : 1;
+  while (!c->knobs.commands_rows && a.rows_per < CMD_ROWS && (int64_t)n * ((p.rows + a.rows_per - 1) / a.rows_per) > most) a.rows_per *= 2;
+  const int64_t items = (int64_t)n * ((p.rows + a.rows_per - 1) / a.rows_per);
+  hipLaunchKernelGGL(commands_kernel, persistent_grid(items, most), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  { int r = stage_record(c, p, 1); if (r) return r; }
+  { int r = y_read_again(c); if (r) return r; }
+  p.enqueued = true;
+  p.n_streams = n;
+  return RFID_OK;
+}
+
+int rfid_batch_get_window_commands(rfid_ctx *c, int stream, rfid_command *out, int64_t cap, int64_t *n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
+  rfid_ctx::Commands &p = c->cmd;
+  if (!p.blk || !p.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_commands: no rfid_batch_commands behind this plan");
+  return stage_fetch_rows(c, "rfid_batch_get_window_commands", p.d_nrows, p.d_table, sizeof(rfid_command), p.rows, p.n_streams, stream, out, cap, n,
+                          "windows");
+}
+
+int rfid_batch_commands_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  return stage_ms(c, c->cmd, ms);
+}
+
+// the per-call form: spans in host memory through the batch kernel's device function (one launch, synchronising)
+int rfid_commands_of(rfid_ctx *c, const rfid_cf32 *spans, const rfid_cf32 *levels, int n, rfid_command *out) {
+  if (!c || n < 0 || (n > 0 && (!spans || !levels || !out))) return RFID_ERR_INVALID;
+  if (n == 0) return RFID_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_in = up256(sizeof(float2) * (size_t)CMD_SPAN * (size_t)n), sz_lv = up256(sizeof(float2) * (size_t)n),
+               sz_out = sizeof(rfid_command) * (size_t)n;
+  { int r = grow(c, c->cmd_one, sz_in + sz_lv + sz_out); if (r) return r; }
+  char *b = (char *)c->cmd_one.p;
+  HIPCHK(c, hipMemcpyAsync(b, spans, sizeof(float2) * (size_t)CMD_SPAN * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_in, levels, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  // (the copies around it are what a call costs: two workgroups per compute unit will do)
+  hipLaunchKernelGGL(commands_of_kernel, persistent_grid(((int64_t)n + CMD_ROWS - 1) / CMD_ROWS, (int64_t)c->n_cus * 2), dim3(64), 0, c->stream,
+                     (const float2 *)b, (const float2 *)(b + sz_in), n, (rfid_command *)(b + sz_in + sz_lv));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_in + sz_lv, sz_out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
 }

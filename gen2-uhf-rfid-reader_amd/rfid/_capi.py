@@ -90,6 +90,11 @@ MOMENTS_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("sx", "<f4"), ("sy
                           ("syy", "<f4"), ("flags", "<i4")])
 MOMENTS_SAMPLES = 240
 assert MOMENTS_DTYPE.itemsize == 32
+COMMAND_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("cmd", "<i4"), ("n_edges", "<i4"), ("n_syms", "<i4"), ("end", "<i4"),
+                          ("d0", "<i4"), ("rtcal", "<i4"), ("trcal", "<i4"), ("n_bits", "<i4"), ("bits", "<u4"), ("flags", "<i4")])
+CMD_SPAN, CMD_MAX_EDGES, CMD_GAP = 704, 64, 120
+CMD_NONE, CMD_QUERY, CMD_QUERY_REP, CMD_ACK, CMD_NAK, CMD_QUERY_ADJUST, CMD_UNKNOWN = range(7)
+assert COMMAND_DTYPE.itemsize == 48
 assert WINDOW_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 48
 assert SCORES_DTYPE.itemsize == 144 and STATS_DTYPE.itemsize == 1056
 
@@ -170,6 +175,11 @@ SIGNATURES = {
     "rfid_batch_get_window_moments": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_slots_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_window_moments_of": (_i, [_vp, _vp, _i, _vp]),
+    "rfid_batch_plan_commands": (_i, [_vp]),
+    "rfid_batch_commands": (_i, [_vp]),
+    "rfid_batch_get_window_commands": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_commands_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_commands_of": (_i, [_vp, _vp, _vp, _i, _vp]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

@@ -13,6 +13,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from ._capi import CMD_ACK, CMD_QUERY, CMD_QUERY_REP, CMD_SPAN     # (RFID_CMD_*: one copy, the binding's)
 from .context import Context
 
 
@@ -49,6 +50,8 @@ class BatchDecoder:
         self.last_repairs = None      # the repaired windows, ordered by (stream, seq), of the last decode(..., repair=True)
         self._slots_planned = False
         self.last_slots = None        # one moments array per trace (every window before the cut-off) of the last decode(..., slots=True)
+        self._cmd_planned = False
+        self.last_commands = None     # one commands array per trace (every window before the cut-off) of the last decode(..., commands=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -64,6 +67,7 @@ class BatchDecoder:
             self._qual_planned = False
             self._rep_planned = False
             self._slots_planned = False
+            self._cmd_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -74,7 +78,7 @@ class BatchDecoder:
 
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
                inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False,
-               repair: bool = False, slots: bool = False):
+               repair: bool = False, slots: bool = False, commands: bool = False):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
@@ -89,7 +93,10 @@ class BatchDecoder:
         `self.last_repairs` keeps their records (capi.REPAIR_DTYPE, ordered by (stream, seq)); a repair is not a read and
         changes nothing else; a trace's whole row: `self.ctx.batch_window_repairs(stream)`.  slots=True (implies nothing):
         the second-order moments of every window, RN16 and EPC alike, are worked out behind the pass; `self.last_slots` keeps
-        one capi.MOMENTS_DTYPE array per trace (classify_slots() turns it into empty / single / collided per slot)."""
+        one capi.MOMENTS_DTYPE array per trace (classify_slots() turns it into empty / single / collided per slot).
+        commands=True (implies nothing): the reader's own PIE command in front of every window is decoded behind the pass;
+        `self.last_commands` keeps one capi.COMMAND_DTYPE array per trace (command_fields() turns it into names, Q, RN16 and
+        timings)."""
         torch = self._torch
         n = len(traces)
         lens = np.array([len(t) for t in traces], dtype=np.int64)
@@ -127,6 +134,9 @@ class BatchDecoder:
         if slots and not self._slots_planned:
             self.ctx.batch_plan_slots()
             self._slots_planned = True
+        if commands and not self._cmd_planned:
+            self.ctx.batch_plan_commands()
+            self._cmd_planned = True
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
         if inventory:
             self.ctx.batch_inventory_enqueue()
@@ -138,6 +148,8 @@ class BatchDecoder:
             self.ctx.batch_repair_enqueue()
         if slots:
             self.ctx.batch_slots_enqueue()
+        if commands:
+            self.ctx.batch_commands_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
@@ -150,6 +162,8 @@ class BatchDecoder:
             self.last_repairs = self.ctx.batch_repair_fetch()
         if slots:
             self.last_slots = [self.ctx.batch_window_moments(b) for b in range(n)]
+        if commands:
+            self.last_commands = [self.ctx.batch_window_commands(b) for b in range(n)]
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -415,8 +429,77 @@ def format_slots_csv(slots: Sequence[np.ndarray], starts: Sequence[np.ndarray], 
     return "\n".join(lines) + "\n"
 
 
+COMMAND_NAMES = ("none", "query", "queryrep", "ack", "nak", "queryadjust", "unknown")   # by RFID_CMD_*
+SAMPLE_US = 2.5           # one sample behind the decimation of a 2 Msps trace (400 ksps)
+COMMAND_FIELDS_DTYPE = np.dtype([("seq", "<i4"), ("name", "U11"), ("q", "<i4"), ("rn16", "<i4"), ("crc5_ok", "<i4"), ("ack_echo", "<i4"),
+                                 ("rtcal_us", "<f8"), ("trcal_us", "<f8"), ("t1_us", "<f8")])
+COMMANDS_HEADER = "file,seq,t_s,cmd,n_bits,bits,q,rn16,crc5_ok,ack_echo,rtcal_us,trcal_us,t1_us"
+
+
+def command_bits(rec) -> str:
+    """rfid_command::bits as sent: the first min(n_bits, 32) data bits, the first one sent leftmost"""
+    w = int(rec["bits"]) & 0xFFFFFFFF
+    return "".join(str((w >> k) & 1) for k in range(min(max(int(rec["n_bits"]), 0), 32)))
+
+
+def command_fields(rows: np.ndarray) -> np.ndarray:
+    """One trace's rfid_command records (Context.batch_window_commands) -> one COMMAND_FIELDS_DTYPE record per window: name
+    (COMMAND_NAMES); q: the Q a Query announces (data bits 13..16, MSB first), -1 for any other command; rn16: the RN16 an ACK
+    carries (data bits 2..17, MSB first, as the tag sent it), -1 otherwise; crc5_ok: a Query's CRC-5 holds (-1: not a Query);
+    ack_echo: the ACK carries the RN16 decoded in the window before (-1: not an ACK); rtcal / trcal in us at 2.5 us per sample
+    (nan when absent); t1_us: from the command's last rising edge to the window's first sample (nan without a command)."""
+    rows = np.asarray(rows)
+    out = np.zeros(len(rows), dtype=COMMAND_FIELDS_DTYPE)
+    for k, r in enumerate(rows):
+        cmd, w, flags = int(r["cmd"]), int(r["bits"]) & 0xFFFFFFFF, int(r["flags"])
+        msb_first = lambda lo, n: sum(((w >> (lo + i)) & 1) << (n - 1 - i) for i in range(n))
+        o = out[k]
+        o["seq"] = int(r["seq"])
+        o["name"] = COMMAND_NAMES[cmd] if 0 <= cmd < len(COMMAND_NAMES) else "unknown"
+        o["q"] = msb_first(13, 4) if cmd == CMD_QUERY else -1
+        o["rn16"] = msb_first(2, 16) if cmd == CMD_ACK else -1
+        o["crc5_ok"] = ((flags >> 1) & 1) if cmd == CMD_QUERY else -1
+        o["ack_echo"] = ((flags >> 2) & 1) if cmd == CMD_ACK else -1
+        o["rtcal_us"] = SAMPLE_US * int(r["rtcal"]) if int(r["rtcal"]) > 0 else np.nan
+        o["trcal_us"] = SAMPLE_US * int(r["trcal"]) if int(r["trcal"]) > 0 else np.nan
+        o["t1_us"] = SAMPLE_US * (CMD_SPAN - int(r["end"])) if int(r["n_syms"]) > 0 else np.nan
+    return out
+
+
+def format_commands(rows: np.ndarray) -> str:
+    """One line for one trace's commands (Context.batch_window_commands): how many windows were opened by a Query, a QueryRep,
+    an ACK, another command or none that could be found; the Q values the Queries announced; the Queries whose CRC-5 failed;
+    how many ACKs echo the RN16 decoded in the window before them; the median RTcal, TRcal and T1 in us."""
+    f = command_fields(rows)
+    name = f["name"]
+    count = lambda n: int((name == n).sum())
+    nq, nr, na, nn = count("query"), count("queryrep"), count("ack"), count("none")
+    qs = sorted(set(int(q) for q in f["q"][name == "query"]))
+    med = lambda v: ("%.1f" % float(np.median(v[~np.isnan(v)]))) if (~np.isnan(v)).any() else "-"
+    return ("| commands : %d  query : %d  queryrep : %d  ack : %d  other : %d  none : %d  Q : %s  failed CRC-5 : %d  "
+            "ACKs echoing the decoded RN16 : %d of %d  median RTcal us : %s  TRcal us : %s  T1 us : %s\n" %
+            (len(f), nq, nr, na, len(f) - nq - nr - na - nn, nn, ("{" + ",".join(map(str, qs)) + "}") if qs else "-",
+             int((f["crc5_ok"] == 0).sum()), int((f["ack_echo"] == 1).sum()), na, med(f["rtcal_us"]), med(f["trcal_us"]), med(f["t1_us"])))
+
+
+def format_commands_csv(rows: Sequence[np.ndarray], starts: Sequence[np.ndarray], names: Sequence[str]) -> str:
+    """CSV text, one line per window, by trace, then by seq: file,seq,t_s,cmd,n_bits,bits,q,rn16,crc5_ok,ack_echo,rtcal_us,
+    trcal_us,t1_us.  rows[b]: the rfid_command records of trace b; starts[b][seq]: rfid_window::start of its windows; names[b]:
+    its file.  t_s = start / 400e3 as in the tracks CSV; bits as sent (command_bits); rn16 as four hex digits; a field that
+    does not apply to the command is empty."""
+    lines = [COMMANDS_HEADER]
+    opt = lambda v, fmt: "" if (v < 0 or v != v) else fmt % v
+    for b, (rec, name) in enumerate(zip(rows, names)):
+        for r, f in zip(rec, command_fields(rec)):
+            lines.append("%s,%d,%.9g,%s,%d,%s,%s,%s,%s,%s,%s,%s,%s" %
+                         (name, int(r["seq"]), int(starts[b][int(r["seq"])]) / TRACKS_RATE, f["name"], int(r["n_bits"]), command_bits(r),
+                          opt(int(f["q"]), "%d"), opt(int(f["rn16"]), "%04x"), opt(int(f["crc5_ok"]), "%d"), opt(int(f["ack_echo"]), "%d"),
+                          opt(float(f["rtcal_us"]), "%.1f"), opt(float(f["trcal_us"]), "%.1f"), opt(float(f["t1_us"]), "%.1f")))
+    return "\n".join(lines) + "\n"
+
+
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -436,6 +519,10 @@ def main(argv=None) -> int:
     ap.add_argument("--slots", metavar="OUT.csv", default=None,
                     help="classify every slot as empty, single or collided from the second-order moments of its windows (built "
                          "on the device); one line per file, the slots to this CSV file")
+    ap.add_argument("--commands", metavar="OUT.csv", default=None,
+                    help="decode the reader's own PIE command in front of every window (built on the device): which command, "
+                         "which Q, which RN16 was ACKed and whether it is the one decoded; one line per file, the commands to "
+                         "this CSV file")
     args = ap.parse_args(argv)
     if args.tracks or args.repair:
         args.inventory = True
@@ -444,7 +531,7 @@ def main(argv=None) -> int:
         timing = {}
         stats, windows, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
                                             tracks=bool(args.tracks), quality=args.quality, repair=bool(args.repair),
-                                            slots=bool(args.slots))
+                                            slots=bool(args.slots), commands=bool(args.commands))
         for i, (path, row) in enumerate(zip(args.files, stats)):
             print(path)
             print(format_results(row), end="")
@@ -454,6 +541,8 @@ def main(argv=None) -> int:
                 print(format_repair_summary(dec.ctx.batch_window_repairs(i)), end="")
             if args.slots:
                 print(format_slots(classify_slots(dec.last_slots[i]), args.fixed_q), end="")
+            if args.commands:
+                print(format_commands(dec.last_commands[i]), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
               (len(args.files), timing["raw_samples"] / 1e6, timing["total_s"], timing["h2d_s"], timing["gpu_s"]))
         if args.inventory:
@@ -477,6 +566,10 @@ def main(argv=None) -> int:
             starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
             with open(args.slots, "w") as f:
                 f.write(format_slots_csv([classify_slots(m) for m in dec.last_slots], starts, args.files))
+        if args.commands:
+            starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
+            with open(args.commands, "w") as f:
+                f.write(format_commands_csv(dec.last_commands, starts, args.files))
     finally:
         dec.close()
     return 0

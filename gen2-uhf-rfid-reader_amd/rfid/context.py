@@ -469,6 +469,40 @@ class Context:
         self._chk(self._lib.rfid_window_moments_of(self._h, gated.ctypes.data, len(gated), out.ctypes.data))
         return out
 
+    def batch_plan_commands(self) -> None:
+        """Reserves the commands workspace of the current plan (a new plan drops it; it needs none of the other workspaces)."""
+        self._chk(self._lib.rfid_batch_plan_commands(self._h))
+
+    def batch_commands_enqueue(self) -> None:
+        """Asynchronous: the reader's PIE command in front of every window of the last pass, behind its statistics
+        (rfid_batch_commands)."""
+        self._chk(self._lib.rfid_batch_commands(self._h))
+
+    def batch_window_commands(self, stream: int, extra: int = 0) -> np.ndarray:
+        """One trace's row of the commands table (synchronises): the capi.COMMAND_DTYPE record of EVERY window before the
+        cut-off, RN16 and EPC alike, in seq order (n_windows_used of them), of the last batch_commands_enqueue.  extra > 0: up
+        to that many of the table's rows behind them as well (zeroed by the stage).  rfid.batch.command_fields turns a row
+        into names, Q, RN16 and timings."""
+        return self._sized_fetch(self._lib.rfid_batch_get_window_commands, capi.COMMAND_DTYPE, head=(int(stream),),
+                                 extra=max(int(extra), 0))
+
+    def batch_commands_ms(self) -> float:
+        return self._stage_ms(self._lib.rfid_batch_commands_ms)
+
+    def commands_of(self, spans, levels) -> np.ndarray:
+        """The same decode for spans in host memory (rfid_commands_of): spans = [n][704] samples of the matched filter's
+        output in front of a window each, levels = [n] the dc of each window.  -> capi.COMMAND_DTYPE records, stream = 0,
+        seq = the span's position, flag bits 0, 2 and 4 clear."""
+        spans = np.ascontiguousarray(spans, dtype=np.complex64)
+        levels = np.ascontiguousarray(levels, dtype=np.complex64).reshape(-1)
+        if spans.ndim != 2 or spans.shape[1] != capi.CMD_SPAN:
+            raise ValueError("a command is searched in the 704 samples before a window: spans must be (n, 704)")
+        if len(levels) != len(spans):
+            raise ValueError("one level per span")
+        out = np.zeros(len(spans), dtype=capi.COMMAND_DTYPE)
+        self._chk(self._lib.rfid_commands_of(self._h, spans.ctypes.data, levels.ctypes.data, len(spans), out.ctypes.data))
+        return out
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

@@ -233,6 +233,53 @@ typedef struct rfid_window_moments {   /* 32 bytes */
   int32_t flags;                       /* bit 0: crc_ok of the window's result (0 for RN16); bit 1: the window is an EPC window */
 } rfid_window_moments;
 
+/* the reader's own PIE command in front of one window: what the commands stage (rfid_batch_commands, rfid_commands_of) decodes
+ * for EVERY window before the TERMINATED cut-off.  Every window the gate opens was opened by a reader command on the same
+ * trace -- a Query or QueryRep before an RN16 window, an ACK before an EPC window -- at full carrier depth in the matched
+ * filter's output just before the window's start.  The record names the command, its calibration symbols and its data bits,
+ * and says whether an ACK echoes the RN16 decoded in the window before: a reader-side ground truth that needs no CRC.
+ * THE DEFINITION (the contract; integer apart from one binary32 comparison per sample; a record is a function of the input
+ * alone and is compared byte for byte), for a window with seq < n_windows_used, start a and dc (dr, di):
+ *   samples  span position p = 0 .. RFID_CMD_SPAN - 1 is sample y[a - RFID_CMD_SPAN + p] of that trace; a position whose index
+ *            is below 0 is HIGH (and flag bit 4 is set).  thr = 0.25f * (dr * dr + di * di); low[p] = (re * re + im * im) < thr,
+ *            in binary32, every operation rounded by itself, no fused multiply-add: a sample exactly at thr is high, thr == 0
+ *            means nothing is low.
+ *   edges    a rising edge is at p (1 <= p < RFID_CMD_SPAN) iff low[p - 1] && !low[p].  n_edges counts all of them; only the
+ *            last min(n_edges, RFID_CMD_MAX_EDGES) are kept: e_0 < ... < e_(n-1).
+ *   command  the longest suffix c_0 .. c_(m-1) of the kept edges whose consecutive distances are all <= RFID_CMD_GAP;
+ *            d_k = c_k - c_(k-1); n_syms = m; end = c_(m-1).
+ *   m < 3    cmd = RFID_CMD_NONE; d0 = d_1 if m >= 2; everything else 0.
+ *   m >= 3   d0 = d_1, rtcal = d_2; if m >= 4 and d_3 > rtcal: trcal = d_3 and the data starts at k = 4, otherwise trcal = 0 and
+ *            the data starts at k = 3.  Data bit = (2 * d_k > rtcal); n_bits counts all data symbols, bits keeps the first 32.
+ *   cmd      (patterns in the order the bits are sent)
+ *            QUERY         trcal > 0, n_bits == 22, the first four bits 1000
+ *            QUERY_REP     trcal == 0, n_bits == 4, the bits start with 00
+ *            ACK           trcal == 0, n_bits == 18, the bits start with 01
+ *            NAK           trcal == 0, n_bits == 8, the bits are 11000000
+ *            QUERY_ADJUST  trcal == 0, n_bits == 9, the bits start with 1001
+ *            UNKNOWN       anything else
+ *   flags    see the field; bits 0, 3 and 4 describe the span and are set whatever m is, bit 5 only when m >= 3.  CRC-5: poly x^5 + x^3 + 1, preset 01001, MSB first, over bits 0..16, equal to bits 17..21.
+ * Rows behind the cut-off are zero.  A non-finite sample in the span makes the record unspecified.
+ * 704 = 11 x 64: the longest Query is 12 + 24 + 72 + 200 + 22 x 48 = 1 364 us = 546 samples, T1 to the opening adds 98. */
+#define RFID_CMD_SPAN 704        /* decimated samples before a window's start that are searched: 11 x 64 */
+#define RFID_CMD_MAX_EDGES 64    /* rising edges kept (the last ones) */
+#define RFID_CMD_GAP 120         /* a longer distance between rising edges ends a command (1.5 x TRcal of 80) */
+enum { RFID_CMD_NONE = 0, RFID_CMD_QUERY, RFID_CMD_QUERY_REP, RFID_CMD_ACK, RFID_CMD_NAK, RFID_CMD_QUERY_ADJUST, RFID_CMD_UNKNOWN };
+typedef struct rfid_command {    /* 48 bytes */
+  int32_t stream, seq;           /* the window the command opened */
+  int32_t cmd;                   /* RFID_CMD_* */
+  int32_t n_edges;               /* rising edges in the span, all of them (before the cap) */
+  int32_t n_syms;                /* rising edges of the command, m above (0..64) */
+  int32_t end;                   /* span position of the command's last rising edge (0 when n_syms == 0);
+                                    RFID_CMD_SPAN - end = samples from it to the window's first sample */
+  int32_t d0, rtcal, trcal;      /* in samples; 0 when absent */
+  int32_t n_bits;                /* data symbols behind the frame-sync / preamble */
+  uint32_t bits;                 /* data bit k (k-th sent, k < 32) at bit k -- the packing of rfid_decode_result::bits */
+  int32_t flags;                 /* bit 0: EPC window (seq & 1); bit 1: Query whose CRC-5 holds; bit 2: ACK whose 16 RN bits
+                                    equal the RN16 decoded in window seq - 1; bit 3: n_edges > 64; bit 4: span clipped at the
+                                    trace's start; bit 5: 2 * d0 > rtcal (not a frame-sync) */
+} rfid_command;
+
 /* timing of the last rfid_batch_* pass, from HIP events on the ctx stream */
 typedef struct rfid_batch_timing {
   float mf_ms, gate_ms, decode_ms, stats_ms; /* kernel time per pass (summed over the launches of a pass) */
@@ -287,7 +334,7 @@ RFID_API const char *rfid_strerror(int status);
 RFID_API const char *rfid_last_error(const rfid_ctx *ctx);
 RFID_API const char *rfid_version(void);
 /* RFID_MI355X_ABI of the library that was loaded: it changes whenever a struct of this header changes size or layout
- * (4: rfid_ls_report has 13 fields since round 3; 5: its last field is dc_finished since round 6; 6: rfid_repair and the repair stage; 7: rfid_window_moments and the slots stage).  A caller built against another value must not pass structs. */
+ * (4: rfid_ls_report has 13 fields since round 3; 5: its last field is dc_finished since round 6; 6: rfid_repair and the repair stage; 7: rfid_window_moments and the slots stage; still 7 with rfid_command and the commands stage, which only add functions and one struct).  A caller built against another value must not pass structs. */
 RFID_API int rfid_abi_version(void);
 /* device self-test of the wave-level primitives the kernels rely on (DPP wave shift,
  * IEEE division, double sqrt).  0 = all good, >0 = number of failing checks. */
@@ -511,7 +558,7 @@ RFID_API int rfid_batch_set_long_stream(rfid_ctx *ctx, int mode);
 RFID_API int rfid_batch_ls_report(const rfid_ctx *ctx, rfid_ls_report *out);
 /* The switches the environment can set (INTEGRATION.md section 13 lists them: RFID_LONG_STREAM, RFID_OVERLAP,
  * RFID_LS_CALIBRATE, RFID_LS_DEBUG, RFID_LA_PROFILE, RFID_LA_UPLOAD_KERNEL, RFID_LS_FRONT_LDS_KB and the test hooks
- * RFID_FRONT_UNFUSED / RFID_FRONT_SINGLE_STEP / RFID_FRONT_CHUNKS / RFID_LS2_FSM_LANES_MIN / RFID_LS2_DC_ROUNDS / RFID_INVENTORY_SLOTS).  The environment is read ONCE,
+ * RFID_FRONT_UNFUSED / RFID_FRONT_SINGLE_STEP / RFID_FRONT_CHUNKS / RFID_LS2_FSM_LANES_MIN / RFID_LS2_DC_ROUNDS / RFID_INVENTORY_SLOTS / RFID_COMMANDS_ROWS).  The environment is read ONCE,
  * by rfid_ctx_create; these two change / read a value of a living context by its lower-case name without the RFID_
  * prefix ("overlap", "front_chunks", ...; LS2_FSM_LANES_MIN is "fsm_lanes_min", LS2_DC_ROUNDS "dc_rounds").  RFID_ERR_INVALID: unknown name or a
  * value outside the knob's range.  A change that concerns buffers (overlap) takes effect with the next rfid_batch_plan. */
@@ -661,6 +708,29 @@ RFID_API int rfid_batch_slots_ms(rfid_ctx *ctx, float *ms);
  * rfid_stream_work hand out per window (dc = 0 in the definition).  One launch of the batch kernel's device function,
  * synchronising.  out[k]: stream = 0, seq = k, flags = 0. */
 RFID_API int rfid_window_moments_of(rfid_ctx *ctx, const rfid_cf32 *gated, int n_windows, rfid_window_moments *out);
+/* ---- (2g) batch commands: the reader's PIE command in front of every window, decoded on the device --------------------- */
+/* Behind a pass: one rfid_command (see its definition above) per window with seq < n_windows_used, in a device table
+ * [n_streams][wmax] (row = seq; the rows of a trace behind its cut-off are zeroed: the table's bytes repeat from pass to
+ * pass).  Nothing else a pass reports changes.  rfid_batch_plan_commands reserves the table (48 bytes per possible window).
+ * RFID_ERR_STATE without a plan; RFID_ERR_HIP when the allocation fails (the plan and every other workspace stay usable).  A
+ * new rfid_batch_plan drops it; it neither needs nor drops any other stage's workspace, and their plan calls do not drop it. */
+RFID_API int rfid_batch_plan_commands(rfid_ctx *ctx);
+/* enqueues the commands of the LAST pass behind its statistics (asynchronous, no host synchronisation).  RFID_ERR_STATE: no
+ * commands workspace, or no pass with statistics yet.  It needs no inventory and may be enqueued before or behind the other
+ * stages: it neither needs nor changes their level.  It reads that pass's matched-filter output, window table, results and
+ * statistics on the context's main stream and has rfid_batch_slots' duties there.  There is ONE table per plan, also when two
+ * result sets alternate (RFID_OVERLAP=2): a later pass leaves it alone, but the next rfid_batch_commands overwrites it -- fetch a
+ * pass's rows before enqueueing the stage behind the next pass, or they are lost. */
+RFID_API int rfid_batch_commands(rfid_ctx *ctx);
+/* synchronises; one trace's row of the table: every window before the cut-off in seq order: *n = n_windows_used.  cap as
+ * rfid_batch_get_window_moments.  RFID_ERR_STATE before the first rfid_batch_commands of this plan. */
+RFID_API int rfid_batch_get_window_commands(rfid_ctx *ctx, int stream, rfid_command *out, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_commands (HIP events) */
+RFID_API int rfid_batch_commands_ms(rfid_ctx *ctx, float *ms);
+/* the same decode for spans in host memory: the per-call form.  spans: n x RFID_CMD_SPAN samples, the span of row k in front
+ * of a window whose dc is levels[k] (re, im).  One launch of the batch kernel's device function, synchronising.  out[k]:
+ * stream = 0, seq = k, flag bits 0, 2 and 4 are 0. */
+RFID_API int rfid_commands_of(rfid_ctx *ctx, const rfid_cf32 *spans, const rfid_cf32 *levels, int n, rfid_command *out);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
