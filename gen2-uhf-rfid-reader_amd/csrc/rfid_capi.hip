@@ -27,6 +27,7 @@
 #include "rfid_repair.hpp"
 #include "rfid_slots.hpp"
 #include "rfid_commands.hpp"
+#include "rfid_fine.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
 // the launch list of the long-stream front end, on the stream named by the enclosing scope's `ls2_stream`
@@ -78,6 +79,7 @@ struct RfidKnobs {
   int front_lds_kb = -1;   // RFID_LS_FRONT_LDS_KB   0..64: extra LDS per workgroup of the long-stream first pass (caps its waves per CU); -1: 10 for long traces
   int inventory_slots = 0; // RFID_INVENTORY_SLOTS   2..1024 (a power of two): table slots per trace of the inventory stage, read by rfid_batch_plan_inventory (0: the next power of two >= 2 x max_tags_per_trace).  A small table makes frames collide: the stage's later rounds
   int commands_rows = 0;   // RFID_COMMANDS_ROWS     1..16: rows per wave and step of the commands stage (0: one while the launch has a wave per row, then the next powers of two up to 16)
+  int fine_wgs = 0;        // RFID_FINE_WGS          1..65536: most single-wave workgroups of the fine stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many packs
 };
 
 // the timing events of a pass: stage i of the four took the time from event i to event i + 1
@@ -293,7 +295,7 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
-  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands.  What the six share ----
+  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine.  What the seven share ----
   struct Stage {
     void *blk = nullptr;              // one allocation, carved up (stage_alloc)
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
@@ -349,6 +351,15 @@ struct rfid_ctx {
     int n_streams = 0;                // traces it covered
   } cmd;
   DevBuf cmd_one;                     // rfid_commands_of: the spans, their levels, their records
+  // ---- fine stage (rfid_batch_plan_fine): lives and dies with the tracks workspace ----
+  struct Fine : Stage {
+    rfid_read_fine *d_table = nullptr;      // [B_plan][rows]
+    rfid_read_fine *d_packed = nullptr;     // [trk.cap]: aligned with the tracks
+    int *d_nrows = nullptr;           // [B_plan]: EPC windows before the cut-off
+    int rows = 0;                     // ceil(wmax / 2)
+    int n_streams = 0;                // traces it covered
+  } fin;
+  DevBuf fin_one;                     // rfid_fine_window: the window, its result, the record
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
   // (rfid_batch_stats ran behind the last decode), the inventory was enqueued behind those statistics, the tracks behind
   // that inventory.  A stage is current only while every stage before it is: one ordered level, moved by mark_current and
@@ -398,6 +409,7 @@ const KnobEntry g_knob_table[] = {
   {"front_lds_kb", "RFID_LS_FRONT_LDS_KB", &RfidKnobs::front_lds_kb, -1, 64},
   {"inventory_slots", "RFID_INVENTORY_SLOTS", &RfidKnobs::inventory_slots, 0, 1024},
   {"commands_rows", "RFID_COMMANDS_ROWS", &RfidKnobs::commands_rows, 0, CMD_ROWS},
+  {"fine_wgs", "RFID_FINE_WGS", &RfidKnobs::fine_wgs, 0, 65536},
 };
 int clamp_int(long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 // the environment, once per context: values out of range are clamped, anything that is not a number is ignored
@@ -481,7 +493,7 @@ void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
 // `stage` and everything behind it no longer belong to the last pass
 void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
 
-// ---- what the inventory, tracks, quality, repair, slots and commands stages share on the host ----
+// ---- what the inventory, tracks, quality, repair, slots, commands and fine stages share on the host ----
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void stage_free(rfid_ctx::Stage &st) {
@@ -696,8 +708,14 @@ void free_quality(rfid_ctx *c) {
   c->qual.rows = 0;
 }
 
+void free_fine(rfid_ctx *c) {
+  stage_free(c->fin);
+  c->fin.rows = 0;
+}
+
 void free_tracks(rfid_ctx *c) {
   free_quality(c);                     // (sized by this workspace, and reading it)
+  free_fine(c);                        // (likewise)
   invalidate_from(c, rfid_ctx::CUR_TRACKS);
   stage_free(c->trk);
   c->trk.cap = 0;
@@ -1228,14 +1246,14 @@ int rfid_ctx_destroy(rfid_ctx *c) {
   la_free(c);
   sio_free(c);
   free_plan(c);
-  void *ptrs[] = {c->d_small, c->s_in.p, c->s_out.p, c->synth_tab.p, c->ls2_ws.p, c->ls2_ws_alt.p, c->rep_one.p, c->mom_one.p, c->cmd_one.p};
+  void *ptrs[] = {c->d_small, c->s_in.p, c->s_out.p, c->synth_tab.p, c->ls2_ws.p, c->ls2_ws_alt.p, c->rep_one.p, c->mom_one.p, c->cmd_one.p, c->fin_one.p};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->ls2_host) (void)hipHostFree(c->ls2_host);
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);
   for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep,
-                               (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd})
+                               (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd, (rfid_ctx::Stage *)&c->fin})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
@@ -2123,6 +2141,106 @@ int rfid_commands_of(rfid_ctx *c, const rfid_cf32 *spans, const rfid_cf32 *level
                      (const float2 *)b, (const float2 *)(b + sz_in), n, (rfid_command *)(b + sz_in + sz_lv));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, b + sz_in + sz_lv, sz_out, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
+}
+
+// ---- fine stage: the data-aided channel estimate of every EPC window, behind the tracks of a pass (csrc/rfid_fine.hpp) ----
+int rfid_batch_plan_fine(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  if (!c->B_plan || !c->inv.blk || !c->trk.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_fine: no plan with a tracks workspace (rfid_batch_plan_tracks)");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  rfid_ctx::Fine &f = c->fin;
+  free_fine(c);
+  // EPC windows are every other window: ceil(wmax / 2) rows per trace, as many packed records as the tracks have reads
+  const int rows = (c->wmax + 1) / 2;
+  const int r = stage_alloc(c, f, "rfid_batch_plan_fine: workspace allocation",
+                            {{(void **)&f.d_table, sizeof(rfid_read_fine) * (size_t)rows * (size_t)c->B_plan},
+                             {(void **)&f.d_packed, sizeof(rfid_read_fine) * (size_t)c->trk.cap},
+                             {(void **)&f.d_nrows, sizeof(int) * (size_t)c->B_plan}});
+  if (r) return r;
+  f.rows = rows;
+  return RFID_OK;
+}
+
+int rfid_batch_fine(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Tracks &t = c->trk;
+  rfid_ctx::Fine &f = c->fin;
+  if (!c->B || !c->inv.blk || !t.blk || !f.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_fine: no plan with a fine workspace (rfid_batch_plan_fine)");
+  if (!t.enqueued || c->current < rfid_ctx::CUR_TRACKS) return fail(c, RFID_ERR_STATE, "rfid_batch_fine: no rfid_batch_tracks behind the last pass");
+  HIPCHK(c, hipSetDevice(c->device));
+  // as rfid_batch_quality: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
+  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
+  { int rj = join_tails(c); if (rj) return rj; }
+  const int n = c->inv.n_streams;     // the traces the inventory and the tracks covered
+  FineArgs a;
+  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->cur.d_wtab; a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats;
+  a.wmax = c->wmax; a.n_streams = n; a.rows = f.rows; a.table = f.d_table; a.nrows = f.d_nrows;
+  FineGatherArgs g;
+  g.reads = t.d_reads; g.head = t.d_head; g.cap = t.cap; g.table = f.d_table; g.n_streams = n; g.rows = f.rows; g.out = f.d_packed;
+  { int r = stage_record(c, f, 0); if (r) return r; }
+  // single-wave workgroups, each walking packs of eight rows (13.8 KB of LDS each)
+  const int64_t items = (int64_t)n * ((f.rows + FINE_PACK - 1) / FINE_PACK);
+  const int64_t most = c->knobs.fine_wgs ? (int64_t)c->knobs.fine_wgs : (int64_t)c->n_cus * FINE_WGS_PER_CU;
+  hipLaunchKernelGGL(fine_kernel, persistent_grid(items, most), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  const int64_t words = t.cap * FINE_WORDS, gmost = (int64_t)c->n_cus * 8;
+  int64_t gblocks = (words + FINE_GATHER_THREADS - 1) / FINE_GATHER_THREADS;
+  if (gblocks > gmost) gblocks = gmost;
+  if (gblocks < 1) gblocks = 1;
+  hipLaunchKernelGGL(fine_gather_kernel, dim3((unsigned)gblocks), dim3(FINE_GATHER_THREADS), 0, c->stream, g);
+  HIPCHK(c, hipGetLastError());
+  { int r = stage_record(c, f, 1); if (r) return r; }
+  { int r = y_read_again(c); if (r) return r; }
+  f.enqueued = true;
+  f.n_streams = n;
+  return RFID_OK;
+}
+
+int rfid_batch_get_fine(rfid_ctx *c, rfid_read_fine *out, int64_t cap, int64_t *n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
+  rfid_ctx::Inventory &v = c->inv;
+  rfid_ctx::Tracks &t = c->trk;
+  rfid_ctx::Fine &f = c->fin;
+  if (!v.blk || !t.blk || !f.blk || !f.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_fine: no rfid_batch_fine behind this plan");
+  HIPCHK(c, hipSetDevice(c->device));
+  int n_entries = 0;
+  { int r = stage_fetch_head(c, "rfid_batch_get_fine", t.d_head, cap, n, &n_entries); if (r) return r; }
+  if (*n > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, f.d_packed, sizeof(rfid_read_fine) * (size_t)*n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return RFID_OK;
+}
+
+int rfid_batch_get_window_fine(rfid_ctx *c, int stream, rfid_read_fine *out, int64_t cap, int64_t *n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
+  rfid_ctx::Fine &f = c->fin;
+  if (!f.blk || !f.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_fine: no rfid_batch_fine behind this plan");
+  return stage_fetch_rows(c, "rfid_batch_get_window_fine", f.d_nrows, f.d_table, sizeof(rfid_read_fine), f.rows, f.n_streams, stream, out, cap, n);
+}
+
+int rfid_batch_fine_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  return stage_ms(c, c->fin, ms);
+}
+
+// the per-call form: one window in host memory through the batch kernel's device functions (one launch, synchronising)
+int rfid_fine_window(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_result *res, rfid_read_fine *out) {
+  if (!c || !gated || !res || !out) return RFID_ERR_INVALID;
+  if (res->type != RFID_DECODE_EPC) return fail(c, RFID_ERR_INVALID, "rfid_fine_window: not the result of an EPC window");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_w = up256(sizeof(float2) * (size_t)EPC_WIN), sz_r = up256(sizeof(rfid_decode_result));
+  { int r = grow(c, c->fin_one, sz_w + sz_r + sizeof(rfid_read_fine)); if (r) return r; }
+  char *b = (char *)c->fin_one.p;
+  HIPCHK(c, hipMemcpyAsync(b, gated, sizeof(float2) * (size_t)EPC_WIN, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(fine_one_kernel, dim3(1), dim3(64), 0, c->stream, (const float2 *)b, (const rfid_decode_result *)(b + sz_w),
+                     (rfid_read_fine *)(b + sz_w + sz_r));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
 }

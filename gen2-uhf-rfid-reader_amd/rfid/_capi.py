@@ -95,6 +95,10 @@ COMMAND_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("cmd", "<i4"), ("n
 CMD_SPAN, CMD_MAX_EDGES, CMD_GAP = 704, 64, 120
 CMD_NONE, CMD_QUERY, CMD_QUERY_REP, CMD_ACK, CMD_NAK, CMD_QUERY_ADJUST, CMD_UNKNOWN = range(7)
 assert COMMAND_DTYPE.itemsize == 48
+FINE_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("flags", "<i4"), ("sum_re", "<f4"), ("sum_im", "<f4"),
+                       ("pow", "<f4"), ("reserved_", "<i4"), ("seg_re", "<f4", (8,)), ("seg_im", "<f4", (8,)), ("seg_pow", "<f4", (8,))])
+FINE_SEGMENTS, FINE_SEGMENT_BITS = 8, 16
+assert FINE_DTYPE.itemsize == 128
 assert WINDOW_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 48
 assert SCORES_DTYPE.itemsize == 144 and STATS_DTYPE.itemsize == 1056
 
@@ -180,6 +184,12 @@ SIGNATURES = {
     "rfid_batch_get_window_commands": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_commands_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_commands_of": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "rfid_batch_plan_fine": (_i, [_vp]),
+    "rfid_batch_fine": (_i, [_vp]),
+    "rfid_batch_get_fine": (_i, [_vp, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_get_window_fine": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_fine_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_fine_window": (_i, [_vp, _vp, _vp, _vp]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

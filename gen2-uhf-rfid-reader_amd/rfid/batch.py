@@ -13,6 +13,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from . import _capi as capi
 from ._capi import CMD_ACK, CMD_QUERY, CMD_QUERY_REP, CMD_SPAN     # (RFID_CMD_*: one copy, the binding's)
 from .context import Context
 
@@ -52,6 +53,8 @@ class BatchDecoder:
         self.last_slots = None        # one moments array per trace (every window before the cut-off) of the last decode(..., slots=True)
         self._cmd_planned = False
         self.last_commands = None     # one commands array per trace (every window before the cut-off) of the last decode(..., commands=True)
+        self._fine_planned = False
+        self.last_fine = None         # one record per read, aligned with last_tracks[0], of the last decode(..., fine=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -68,6 +71,7 @@ class BatchDecoder:
             self._rep_planned = False
             self._slots_planned = False
             self._cmd_planned = False
+            self._fine_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -78,7 +82,7 @@ class BatchDecoder:
 
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
                inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False,
-               repair: bool = False, slots: bool = False, commands: bool = False):
+               repair: bool = False, slots: bool = False, commands: bool = False, fine: bool = False):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
@@ -96,7 +100,10 @@ class BatchDecoder:
         one capi.MOMENTS_DTYPE array per trace (classify_slots() turns it into empty / single / collided per slot).
         commands=True (implies nothing): the reader's own PIE command in front of every window is decoded behind the pass;
         `self.last_commands` keeps one capi.COMMAND_DTYPE array per trace (command_fields() turns it into names, Q, RN16 and
-        timings)."""
+        timings).  fine=True (implies tracks=True): the data-aided channel estimate of every EPC window -- from all 256 half-bit
+        samples of the frame instead of six of the preamble -- and of its eight 16-bit segments is worked out behind the
+        tracks; `self.last_fine` keeps one capi.FINE_DTYPE record per read, aligned with the reads (fine_fields() turns them
+        into h, snr_db, the segments' h_k and the phase drift); a trace's whole row: `self.ctx.batch_window_fine(stream)`."""
         torch = self._torch
         n = len(traces)
         lens = np.array([len(t) for t in traces], dtype=np.int64)
@@ -114,7 +121,7 @@ class BatchDecoder:
             self._lens_dev = torch.from_numpy(lens).to(dev.device, non_blocking=True)
             torch.cuda.current_stream().synchronize()
         t1 = time.perf_counter()
-        tracks = tracks or quality
+        tracks = tracks or quality or fine
         inventory = inventory or tracks or repair
         if inventory and self._inv_tags != int(max_tags):
             self.ctx.batch_plan_inventory(int(max_tags))
@@ -128,9 +135,13 @@ class BatchDecoder:
             self.ctx.batch_plan_tracks()
             self._trk_planned = True
             self._qual_planned = False
+            self._fine_planned = False
         if quality and not self._qual_planned:
             self.ctx.batch_plan_quality()
             self._qual_planned = True
+        if fine and not self._fine_planned:
+            self.ctx.batch_plan_fine()
+            self._fine_planned = True
         if slots and not self._slots_planned:
             self.ctx.batch_plan_slots()
             self._slots_planned = True
@@ -150,6 +161,8 @@ class BatchDecoder:
             self.ctx.batch_slots_enqueue()
         if commands:
             self.ctx.batch_commands_enqueue()
+        if fine:
+            self.ctx.batch_fine_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
@@ -164,6 +177,8 @@ class BatchDecoder:
             self.last_slots = [self.ctx.batch_window_moments(b) for b in range(n)]
         if commands:
             self.last_commands = [self.ctx.batch_window_commands(b) for b in range(n)]
+        if fine:
+            self.last_fine = self.ctx.batch_fine_fetch()
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -269,17 +284,62 @@ def format_quality(rows: np.ndarray) -> str:
             (len(rows), int((~ok).sum()), med(snr_db[ok]), med(snr_db[~ok]), ("%.3f" % float(margin[ok].min())) if ok.any() else "-"))
 
 
+TRACKS_FINE_COLUMNS = ",hd_re,hd_im,hd_mag_db,hd_phase_rad,hd_snr_db,drift_rad_s"
+FINE_SEGMENT_S = 16 * 25e-6       # a segment of 16 bits at 40 kbps: the segments' centres are 400 us apart
+
+
+def fine_fields(f: np.ndarray) -> dict:
+    """rfid_read_fine records -> a dict of float64 / complex128 arrays, one value per record:
+    h = (sum_re + j sum_im) / 128, the data-aided channel estimate in the units of h_est; mag_db = 20 log10 |h|; phase_rad =
+    angle(h); noise = (pow - |sum|^2 / 128) / 127, the noise power of one of the 128 differences (both components; what is
+    left of their power when the part along the estimate is taken out); snr_db = 10 log10(|h|^2 / noise) (+inf when the noise
+    is not positive, nan for an all-zero record); h_seg [n][8] = seg / 16, the channel of each 16-bit segment; drift_rad_s =
+    the least-squares slope of angle(h_k conj(h)) over the segments' centres, 400 us apart."""
+    f = np.asarray(f)
+    re, im = f["sum_re"].astype(np.float64), f["sum_im"].astype(np.float64)
+    sq = re * re + im * im                    # |sum|^2
+    h = re / 128.0 + 1j * (im / 128.0)
+    mag = np.sqrt(sq) / 128.0
+    noise = (f["pow"].astype(np.float64) - sq / 128.0) / 127.0
+    h_seg = (f["seg_re"].astype(np.float64) + 1j * f["seg_im"].astype(np.float64)) / 16.0
+    t = (np.arange(capi.FINE_SEGMENTS) - (capi.FINE_SEGMENTS - 1) / 2.0) * FINE_SEGMENT_S
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mag_db = 20.0 * np.log10(mag)
+        snr_db = np.where(noise > 0, 10.0 * np.log10(mag ** 2 / np.where(noise > 0, noise, 1.0)), np.where(mag > 0, np.inf, np.nan))
+    ph = np.angle(h_seg * np.conj(h)[..., None])
+    drift = ((ph - ph.mean(axis=-1, keepdims=True)) * t).sum(axis=-1) / float((t * t).sum())
+    return dict(h=h, mag_db=mag_db, phase_rad=np.arctan2(im, re), noise=noise, snr_db=snr_db, h_seg=h_seg, drift_rad_s=drift)
+
+
+def format_fine(rows: np.ndarray) -> str:
+    """One line for one trace's EPC windows before the cut-off (Context.batch_window_fine): how many there are, how many
+    failed their CRC, and over the reads the median of the data-aided |h| in dB, of its SNR and of the magnitude of the
+    phase drift inside a read."""
+    rows = np.asarray(rows)
+    ok = (rows["flags"] & 1) != 0
+    ff = fine_fields(rows)
+    med = lambda v, fmt: fmt % float(np.median(v)) if len(v) else "-"
+    return ("| EPC windows : %d  failed : %d  data-aided h of the reads, medians: |h| dB : %s  SNR dB : %s  |drift| rad/s : %s\n" %
+            (len(rows), int((~ok).sum()), med(ff["mag_db"][ok], "%.2f"), med(ff["snr_db"][ok], "%.2f"),
+             med(np.abs(ff["drift_rad_s"][ok]), "%.1f")))
+
+
 def format_tracks(entries: np.ndarray, reads: np.ndarray, offsets: np.ndarray, names: Sequence[str],
-                  quality: Optional[np.ndarray] = None) -> str:
+                  quality: Optional[np.ndarray] = None, fine: Optional[np.ndarray] = None) -> str:
     """CSV text, one line per read in the order of `reads` (grouped by tag, time order inside a tag):
     file,epc,pc,seq,t_s,h_re,h_im,mag_db,phase_rad,T with t_s = start / 400e3.  entries / offsets: the packed inventory
     and the offsets aligned with it (Context.batch_inventory_fetch / batch_tracks_fetch); names[stream]: the trace's file.
     Floats are printed with %.9g: binary32 values survive the round trip.  quality (optional; the records aligned with
-    `reads`, Context.batch_quality_fetch): two more columns, snr_db,margin (quality_fields)."""
-    lines = [TRACKS_HEADER if quality is None else TRACKS_QUALITY_HEADER]
+    `reads`, Context.batch_quality_fetch): two more columns, snr_db,margin (quality_fields).  fine (optional; the records
+    aligned with `reads`, Context.batch_fine_fetch): behind those, hd_re,hd_im,hd_mag_db,hd_phase_rad,hd_snr_db,drift_rad_s
+    (fine_fields: the data-aided h, in the units of h_re,h_im)."""
+    lines = [(TRACKS_HEADER if quality is None else TRACKS_QUALITY_HEADER) + (TRACKS_FINE_COLUMNS if fine is not None else "")]
     if quality is not None:
         assert len(quality) == len(reads)
         snr_db, margin = quality_fields(quality)
+    if fine is not None:
+        assert len(fine) == len(reads)
+        ff = fine_fields(fine)
     for i, e in enumerate(entries):
         pc, epc = frame_fields(e["frame"])
         name = names[int(e["stream"])]
@@ -293,6 +353,9 @@ def format_tracks(entries: np.ndarray, reads: np.ndarray, offsets: np.ndarray, n
                      float(np.arctan2(im, re)), float(r["T"])))
             if quality is not None:
                 line += ",%.9g,%.9g" % (float(snr_db[k]), float(margin[k]))
+            if fine is not None:
+                line += ",%.9g,%.9g,%.9g,%.9g,%.9g,%.9g" % (float(ff["h"][k].real), float(ff["h"][k].imag), float(ff["mag_db"][k]),
+                                                            float(ff["phase_rad"][k]), float(ff["snr_db"][k]), float(ff["drift_rad_s"][k]))
             lines.append(line)
     return "\n".join(lines) + "\n"
 
@@ -499,7 +562,7 @@ def format_commands_csv(rows: Sequence[np.ndarray], starts: Sequence[np.ndarray]
 
 
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -523,6 +586,10 @@ def main(argv=None) -> int:
                     help="decode the reader's own PIE command in front of every window (built on the device): which command, "
                          "which Q, which RN16 was ACKed and whether it is the one decoded; one line per file, the commands to "
                          "this CSV file")
+    ap.add_argument("--fine", action="store_true",
+                    help="the data-aided channel estimate of every EPC window, from all 256 half-bit samples of its frame (built on "
+                         "the device); one line per file, and with --tracks the CSV gains the columns "
+                         "hd_re,hd_im,hd_mag_db,hd_phase_rad,hd_snr_db,drift_rad_s")
     args = ap.parse_args(argv)
     if args.tracks or args.repair:
         args.inventory = True
@@ -531,7 +598,7 @@ def main(argv=None) -> int:
         timing = {}
         stats, windows, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
                                             tracks=bool(args.tracks), quality=args.quality, repair=bool(args.repair),
-                                            slots=bool(args.slots), commands=bool(args.commands))
+                                            slots=bool(args.slots), commands=bool(args.commands), fine=args.fine)
         for i, (path, row) in enumerate(zip(args.files, stats)):
             print(path)
             print(format_results(row), end="")
@@ -543,6 +610,8 @@ def main(argv=None) -> int:
                 print(format_slots(classify_slots(dec.last_slots[i]), args.fixed_q), end="")
             if args.commands:
                 print(format_commands(dec.last_commands[i]), end="")
+            if args.fine:
+                print(format_fine(dec.ctx.batch_window_fine(i)), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
               (len(args.files), timing["raw_samples"] / 1e6, timing["total_s"], timing["h2d_s"], timing["gpu_s"]))
         if args.inventory:
@@ -558,7 +627,8 @@ def main(argv=None) -> int:
         if args.tracks:
             reads, offsets = dec.last_tracks
             with open(args.tracks, "w") as f:
-                f.write(format_tracks(dec.last_inventory[0], reads, offsets, args.files, dec.last_quality if args.quality else None))
+                f.write(format_tracks(dec.last_inventory[0], reads, offsets, args.files, dec.last_quality if args.quality else None,
+                                      dec.last_fine if args.fine else None))
         if args.repair:
             with open(args.repair, "w") as f:
                 f.write(format_repairs(dec.last_repairs, args.files))

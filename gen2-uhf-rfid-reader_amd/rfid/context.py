@@ -503,6 +503,50 @@ class Context:
         self._chk(self._lib.rfid_commands_of(self._h, spans.ctypes.data, levels.ctypes.data, len(spans), out.ctypes.data))
         return out
 
+    def batch_plan_fine(self) -> None:
+        """Reserves the fine-channel workspace of the current plan (behind batch_plan_tracks; a new plan, batch_plan_inventory or
+        batch_plan_tracks drops it, batch_plan_quality / batch_plan_repair do not)."""
+        self._chk(self._lib.rfid_batch_plan_fine(self._h))
+
+    def batch_fine_enqueue(self) -> None:
+        """Asynchronous: the data-aided channel estimates of the last pass, behind its tracks (rfid_batch_fine)."""
+        self._chk(self._lib.rfid_batch_fine(self._h))
+
+    def batch_fine_fetch(self) -> np.ndarray:
+        """-> capi.FINE_DTYPE records of the last batch_fine_enqueue (synchronises), one per CRC-verified read:
+        record i belongs to reads[i] of batch_tracks_fetch."""
+        return self._sized_fetch(self._lib.rfid_batch_get_fine, capi.FINE_DTYPE)
+
+    def batch_fine(self) -> np.ndarray:
+        """The data-aided channel estimate of every read of the last pass, and of its eight 16-bit segments, built on the
+        device behind batch_tracks(): see batch_fine_fetch; rfid.batch.fine_fields turns the records into h, snr_db, the
+        segments' h_k and the drift of their phase."""
+        self.batch_fine_enqueue()
+        return self.batch_fine_fetch()
+
+    def batch_window_fine(self, stream: int, extra: int = 0) -> np.ndarray:
+        """One trace's row of the fine table (synchronises): the record of EVERY EPC window before the cut-off, in seq order,
+        failed ones included (n_windows_used // 2 of them; flags bit 0 tells them apart), of the last batch_fine_enqueue.
+        extra > 0: up to that many of the table's rows behind them as well (zeroed by the stage)."""
+        return self._sized_fetch(self._lib.rfid_batch_get_window_fine, capi.FINE_DTYPE, head=(int(stream),),
+                                 extra=max(int(extra), 0))
+
+    def batch_fine_ms(self) -> float:
+        return self._stage_ms(self._lib.rfid_batch_fine_ms)
+
+    def fine_window(self, gated, result) -> np.ndarray:
+        """The same sums for ONE EPC window in host memory (rfid_fine_window): gated = its 1370 gated, DC-free samples,
+        result = its capi.RESULT_DTYPE record (what decoder_work returned, or that record with bits the caller has
+        corrected).  -> one capi.FINE_DTYPE record, stream = seq = start = 0."""
+        gated = np.ascontiguousarray(gated, dtype=np.complex64)
+        if len(gated) != 1370:
+            raise ValueError("an EPC window has 1370 samples")
+        res = np.zeros(1, dtype=capi.RESULT_DTYPE)
+        res[0] = result
+        out = np.zeros(1, dtype=capi.FINE_DTYPE)
+        self._chk(self._lib.rfid_fine_window(self._h, gated.ctypes.data, res.ctypes.data, out.ctypes.data))
+        return out[0]
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

@@ -209,6 +209,36 @@ typedef struct rfid_repair {         /* 48 bytes */
   uint32_t frame[4];                 /* the repaired frame, packed as rfid_decode_result::bits; zeros when n_flips == 0 */
 } rfid_repair;
 
+/* the data-aided channel estimate of one EPC window: what the fine stage (rfid_batch_fine, rfid_fine_window) works out for EVERY
+ * EPC window before the TERMINATED cut-off, CRC-verified or not.  rfid_decode_result::h_est is the mean of six matched-filter
+ * samples of the preamble relative to the gate's dc_est; the frame behind it carries 256 more half-bit samples of the same
+ * channel, and with the frame bits known so are their polarities.  Their signed sum does not depend on dc_est, its noise is some
+ * 3.3 times smaller, and taken over 16 bits (400 us) at a time it gives the channel at eight points inside the read.
+ * THE DEFINITION (the contract; binary32 throughout, every operation rounded by itself, no fused multiply-add):
+ *   from the window's own rfid_decode_result (T, index, bits; h_re / h_im are NOT used) and its gated samples
+ *   s[i] = y[start + i] - dc per component, with ia, ib of the rfid_read_quality definition above (clamped into 0 .. 1369),
+ *   for j = 0 .. 127:
+ *     dx_j = s[ia].x - s[ib].x,  dy_j = s[ia].y - s[ib].y
+ *     g_j  = +1.0f when the number of set bits among frame bits 0 .. j is even, else -1.0f   (the decoder's sign chain:
+ *            lib/tag_decoder_impl.cc:171-190, prev = 1 at the start; taken from the BITS, so the per-call form works on a
+ *            frame whose bits a caller has corrected)
+ *   segment k = 0 .. 7 covers j = 16 k .. 16 k + 15, its three sums IN-ORDER sums (((0.0f + t_16k) + t_16k+1) + ...):
+ *     seg_re[k] = sum g_j * dx_j,  seg_im[k] = sum g_j * dy_j,  seg_pow[k] = sum (dx_j * dx_j + dy_j * dy_j)
+ *   sum_re, sum_im, pow are the in-order sums of the eight segment values from 0.0f (the longest dependent chain is 16 + 8
+ *   additions, not 128).  A record is a function of the input alone and is compared by bit pattern.  For a window whose CRC
+ *   failed the record is decision-directed, and flags says so.  (A window with a non-finite sample: unspecified.)
+ * What a host makes of it (rfid.batch.fine_fields, in binary64): h = (sum_re + j sum_im) / 128 -- in the units of h_est -- the
+ * noise per difference (pow - |sum|^2 / 128) / 127, snr_db, the segments' h_k = seg / 16 and the drift of their phase. */
+typedef struct rfid_read_fine {      /* 128 bytes */
+  int32_t stream, seq;               /* the EPC window (rfid_window::stream / seq) */
+  int32_t start;                     /* rfid_window::start of that window */
+  int32_t flags;                     /* bit 0: crc_ok of the window's result */
+  float   sum_re, sum_im;            /* the eight seg_re / seg_im, added in order from 0.0f */
+  float   pow;                       /* the eight seg_pow, likewise */
+  int32_t reserved_;                 /* 0 */
+  float   seg_re[8], seg_im[8], seg_pow[8];
+} rfid_read_fine;
+
 /* the second-order moments of one window's gated samples: what the slots stage (rfid_batch_slots, rfid_window_moments_of)
  * works out for EVERY window before the TERMINATED cut-off, RN16 and EPC alike.  The reference ACKs every slot, so a
  * FIXED_Q > 0 trace yields an RN16 / EPC window pair per slot whatever was on the air; the moments tell an empty slot (an
@@ -731,6 +761,38 @@ RFID_API int rfid_batch_commands_ms(rfid_ctx *ctx, float *ms);
  * of a window whose dc is levels[k] (re, im).  One launch of the batch kernel's device function, synchronising.  out[k]:
  * stream = 0, seq = k, flag bits 0, 2 and 4 are 0. */
 RFID_API int rfid_commands_of(rfid_ctx *ctx, const rfid_cf32 *spans, const rfid_cf32 *levels, int n, rfid_command *out);
+/* ---- (2h) batch fine channel: the data-aided channel estimate of every EPC window, built on the device ------------------- */
+/* Behind the tracks of a pass: one rfid_read_fine (see its definition above) per EPC window with seq < n_windows_used,
+ * CRC-verified or not, in a device table [n_streams][ceil(wmax / 2)] (row = seq >> 1; the rows of a trace behind its cut-off
+ * are zeroed: the table's bytes repeat from pass to pass), and the records of the CRC-verified reads once more as ONE array
+ * aligned with the tracks: fine[i] belongs to reads[i] of rfid_batch_get_tracks.  Nothing else a pass reports changes.
+ * rfid_batch_plan_fine reserves both (2 x 128 bytes per possible EPC window).  RFID_ERR_STATE without a tracks workspace;
+ * RFID_ERR_HIP when the allocation fails (the plan and every other workspace stay usable).  A new rfid_batch_plan,
+ * rfid_batch_plan_inventory or rfid_batch_plan_tracks drops it; it neither needs nor drops the quality and repair workspaces,
+ * and their plan calls do not drop it. */
+RFID_API int rfid_batch_plan_fine(rfid_ctx *ctx);
+/* enqueues the fine stage of the LAST pass behind its tracks (asynchronous, no host synchronisation).  RFID_ERR_STATE: no fine
+ * workspace, or no rfid_batch_tracks was enqueued since the last pass.  It may be enqueued before or behind rfid_batch_quality
+ * and rfid_batch_repair and does not change the level of any stage.  It reads that pass's matched-filter output, window table,
+ * results and statistics on the context's main stream and has rfid_batch_quality's duties there: with two result sets
+ * alternating it reads the set of that pass, and it records the long-stream front end's "free" event of the matched-filter
+ * buffer again behind its own launches. */
+RFID_API int rfid_batch_fine(rfid_ctx *ctx);
+/* synchronises; *n = reads in all, the number rfid_batch_get_tracks reports; out[i] belongs to its reads[i].
+ * RFID_ERR_CAPACITY as there: cap too small (nothing lost: *n says how many there are, call again; out may be NULL with
+ * cap = 0), or a trace overflowed the inventory (rfid_last_error names the first such trace) */
+RFID_API int rfid_batch_get_fine(rfid_ctx *ctx, rfid_read_fine *out, int64_t cap, int64_t *n);
+/* synchronises; one trace's row of the table: every EPC window before the cut-off in seq order, failed ones included:
+ * *n = n_windows_used / 2.  cap as rfid_batch_get_window_quality: RFID_ERR_CAPACITY when cap < *n (nothing is copied; out may
+ * be NULL with cap = 0); with cap > *n the zeroed rows behind *n are copied too, up to min(cap, ceil(wmax / 2)) in all. */
+RFID_API int rfid_batch_get_window_fine(rfid_ctx *ctx, int stream, rfid_read_fine *out, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_fine (HIP events), from its first launch to the end of its last */
+RFID_API int rfid_batch_fine_ms(rfid_ctx *ctx, float *ms);
+/* the same sums for ONE window in host memory: the per-call form (as rfid_repair_window).  gated: the window's 1 370 gated,
+ * DC-free samples (dc = 0 in the definition); res: the result rfid_decoder_work gave for it (type RFID_DECODE_EPC, else
+ * RFID_ERR_INVALID) -- or that result with bits a caller has corrected, from rfid_repair::frame for instance.  One launch of
+ * the batch kernel's device functions, synchronising.  out: stream = seq = start = 0, flags bit 0 = res->crc_ok. */
+RFID_API int rfid_fine_window(rfid_ctx *ctx, const rfid_cf32 *gated, const rfid_decode_result *res, rfid_read_fine *out);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 

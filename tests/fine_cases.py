@@ -1,0 +1,91 @@
+"""What tests/test_fine_emu.py and tests/test_gpu_fine.py share: the crafted windows of the per-call form (rfid_fine_window) with the
+oracle's answers, and the checks on them.  Everything expected comes from tests/fine_ref.py, i.e. from the oracle alone."""
+import numpy as np
+import pytest
+
+import decoder_windows as dw
+import fine_ref as ref
+import repair_ref
+
+PHIS = (0.0, 0.3, 0.6)         # phase a frame gains over its 1370 samples
+SEG_SPAN = 1120.0              # samples between the centres of segments 0 and 7: 7 x 16 bits x 10 samples
+
+
+def rotated_frames(oracle_mod):
+    """the 15 noise-free EPC frames of decoder_windows.valid_frames (sync offsets 0..14), each turned by exp(j phi i / 1370):
+    -> [(name, window, the oracle's dump, phi)], every one decoded by the oracle with a good CRC and the frame's own bits"""
+    out = []
+    i = np.arange(ref.EPC_WIN, dtype=np.float64)
+    for m, (w, bits, tag_id) in enumerate(dw.valid_frames(dw.EPC)):
+        for phi in PHIS:
+            wr = np.ascontiguousarray(w.astype(np.complex128) * np.exp(1j * phi * i / ref.EPC_WIN)).astype(np.complex64)
+            d = oracle_mod.decode_window(wr, dw.EPC)
+            assert d["crc_ok"] == 1 and d["tag_id"] == tag_id and np.array_equal(d["bits"][:128], bits), (m, phi)
+            out.append(("frame@%d phi=%.1f" % (m, phi), wr, d, phi))
+    assert len(out) == 45
+    return out
+
+
+def check_crafted_windows(ctx, oracle_mod, rfid):
+    """rfid_fine_window on the rotated frames and the degenerate windows, by bytes against fine_ref; the drift of the rotated frames
+    from the device's own records; a frame with bits the caller changed; what the call refuses"""
+    frames = rotated_frames(oracle_mod)
+    for name, w, d, phi in frames:
+        want = ref.expected_window(w, d)
+        got = ctx.fine_window(w, repair_ref.result_of_dump(d))
+        ref.assert_equal(got, want, name)
+        assert got["flags"] == 1 and got["stream"] == 0 and got["seq"] == 0 and got["start"] == 0 and got["reserved_"] == 0
+        # the restatement gives 0.2449-0.2457 (phi = 0.3) and 0.4898-0.4915 (0.6) against phi x 1120 / 1370 = 0.2453 and 0.4905
+        s0 = complex(got["seg_re"][0], got["seg_im"][0])
+        s7 = complex(got["seg_re"][7], got["seg_im"][7])
+        turn = float(np.angle(s7 * np.conj(s0)))
+        assert abs(turn - phi * SEG_SPAN / ref.EPC_WIN) <= 0.005, (name, turn, phi * SEG_SPAN / ref.EPC_WIN)
+    deg = dw.degenerate(dw.EPC)
+    for name, w in deg.items():
+        d = oracle_mod.decode_window(w, dw.EPC)
+        want = ref.expected_window(w, d)
+        got = ctx.fine_window(w, repair_ref.result_of_dump(d))
+        ref.assert_equal(got, want, name)
+        assert got["flags"] == (int(d["crc_ok"]) & 1)
+    zero = ctx.fine_window(deg["zero"], repair_ref.result_of_dump(oracle_mod.decode_window(deg["zero"], dw.EPC)))
+    assert not zero.tobytes().strip(b"\0")                       # (+0.0 everywhere: the sums start from 0.0f, g x 0 = -0.0 or not)
+    # bits a caller has corrected: the signs follow the bits handed in, not the decoder's own
+    name, w, d, phi = frames[4]
+    bits = d["bits"][:128].copy()
+    bits[40] ^= 1
+    res = repair_ref.result_of_dump(d)
+    res["bits"] = repair_ref.inv.pack_frames(bits[None, :])[0]
+    res["crc_ok"] = 0
+    want = ref.expected_window(w, d, bits=bits)
+    want["flags"] = 0
+    got = ctx.fine_window(w, res)
+    ref.assert_equal(got, want, "changed bits")
+    plain = ref.expected_window(w, d)
+    assert got["seg_re"][:2].tobytes() == plain["seg_re"][:2].tobytes() and got["seg_re"][2:].tobytes() != plain["seg_re"][2:].tobytes()
+    assert got["seg_pow"].tobytes() == plain["seg_pow"].tobytes()
+    # not an EPC window's result; not an EPC window
+    rn16 = res.copy()
+    rn16["type"] = 0
+    with pytest.raises(rfid.capi.RfidError) as e:
+        ctx.fine_window(w, rn16)
+    assert e.value.status == rfid.capi.ERR_INVALID
+    with pytest.raises(ValueError):
+        ctx.fine_window(w[:250], res)
+
+
+def check_rows(ctx, want, what="", extra=3, stats=True):
+    """the packed records against want[0], every trace's row against want[1] (and `extra` zero rows behind it) -> all the bytes.
+    stats: the context's statistics are still those of the pass the stage ran behind"""
+    w_packed, w_rows = want
+    f = ctx.batch_fine_fetch()
+    ref.assert_equal(f, w_packed, what)
+    st = ctx.batch_stats() if stats else None
+    blob = f.tobytes()
+    for b, w in enumerate(w_rows):
+        r = ctx.batch_window_fine(b, extra=extra)
+        assert len(r) == len(w) + extra, (what, b, len(r), len(w))
+        assert st is None or int(st[b]["n_windows_used"]) // 2 == len(w), (what, b, len(w))
+        ref.assert_equal(r[:len(w)], w, (what, "row", b))
+        assert not r[len(w):].tobytes().strip(b"\0"), (what, "rows behind the cut-off", b)
+        blob += r.tobytes()
+    return blob
