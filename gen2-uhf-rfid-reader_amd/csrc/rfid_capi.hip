@@ -1443,6 +1443,35 @@ int rfid_selftest(rfid_ctx *c, int *n_failed) {
   return RFID_OK;
 }
 
+// the gate's step function on caller-given records, in its wave-uniform and its per-lane form (a test entry: the expected
+// values are the caller's)
+int rfid_selftest_gate_fsm(rfid_ctx *c, const rfid_gate_fsm_in *in, int n, rfid_gate_fsm_out *out_wave, rfid_gate_fsm_out *out_lane) {
+  if (!c || n < 0 || (n > 0 && (!in || !out_wave || !out_lane))) return RFID_ERR_INVALID;
+  if (n == 0) return RFID_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  char *d = nullptr;
+  const size_t in_bytes = sizeof(rfid_gate_fsm_in) * (size_t)n, out_bytes = sizeof(rfid_gate_fsm_out) * (size_t)n;
+  HIPCHK(c, hipMalloc((void **)&d, in_bytes + 2 * out_bytes));
+  GateFsmSelfTestArgs a;
+  a.in = reinterpret_cast<const rfid_gate_fsm_in *>(d);
+  a.out_wave = reinterpret_cast<rfid_gate_fsm_out *>(d + in_bytes);
+  a.out_lane = a.out_wave + n;
+  a.n = n;
+  int rc = RFID_OK;
+  auto step = [&](hipError_t e) { if (e != hipSuccess && rc == RFID_OK) { snprintf(c->err, sizeof(c->err), "selftest_gate_fsm: %s", hipGetErrorString(e)); rc = RFID_ERR_HIP; } };
+  step(hipMemcpyAsync(d, in, in_bytes, hipMemcpyHostToDevice, c->stream));
+  step(hipMemsetAsync(d + in_bytes, 0xEE, 2 * out_bytes, c->stream));
+  if (rc == RFID_OK) {
+    hipLaunchKernelGGL(gate_fsm_selftest_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, a);
+    step(hipGetLastError());
+  }
+  step(hipMemcpyAsync(out_wave, a.out_wave, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  step(hipMemcpyAsync(out_lane, a.out_lane, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  step(hipStreamSynchronize(c->stream));
+  (void)hipFree(d);
+  return rc;
+}
+
 // ======================================================================================
 // (2) batched offline path
 // ======================================================================================

@@ -2524,6 +2524,54 @@ RFID_KERNEL(64) void selftest_kernel(SelfTestArgs a) {
   a.shr_out[lane] = wv::shr1(a.x[lane]);
 }
 
+// gate_fsm_step by itself (rfid_selftest_gate_fsm): one step per record from the record's own state, in the two forms
+// the kernels call it in -- wave-uniform arguments on the scalar unit (the consumer wave, ls2_fsm_kernel): a workgroup
+// takes its 64 records one after the other, lane 0 stores; and one record per lane on the vector unit
+// (ls2_fsm_lanes_kernel).  A thin caller: nothing of the step function is restated here.
+struct GateFsmSelfTestArgs {
+  const rfid_gate_fsm_in *in;   // [n]
+  rfid_gate_fsm_out *out_wave;  // [n]
+  rfid_gate_fsm_out *out_lane;  // [n]
+  int n;
+};
+
+RFID_DEVICE void gate_fsm_selftest_one(const int mode, GateRegs &g, const uint64_t below, const uint64_t above, const int pos,
+                                       int nvalid, rfid_gate_fsm_out &o) {
+  uint64_t closedmask, openmask;
+  int open_lane, open_type;
+  gate_fsm_step(mode, g, below, above, pos, nvalid, closedmask, openmask, open_lane, open_type);
+  o.n_samples = g.f_n; o.signal_state = g.f_state; o.num_pulses = g.f_pulses; o.gate_open = g.f_open;
+  o.n_to_ungate = g.f_ung; o.wtype = g.f_type; o.nvalid = nvalid; o.stop = g.stop ? 1 : 0; o.consumed = g.consumed;
+  o.open_lane = open_lane; o.open_type = open_type; o.reserved_ = 0;
+  o.closedmask = closedmask; o.openmask = openmask;
+}
+
+RFID_KERNEL(64) void gate_fsm_selftest_kernel(GateFsmSelfTestArgs a) {
+  const int lane = wv::lane_id();
+  const int base = (int)blockIdx.x * 64;
+  for (int j = 0; j < 64 && base + j < a.n; ++j) {
+    const rfid_gate_fsm_in *r = a.in + base + j;
+    GateRegs g;
+    g.avg_c = 0.0f; g.consumed = 0; g.stop = false;
+    g.f_n = wv::uniform(r->n_samples); g.f_state = wv::uniform(r->signal_state); g.f_pulses = wv::uniform(r->num_pulses);
+    g.f_open = wv::uniform(r->gate_open); g.f_ung = wv::uniform(r->n_to_ungate); g.f_type = wv::uniform(r->wtype);
+    rfid_gate_fsm_out o;
+    gate_fsm_selftest_one(wv::uniform(r->mode), g, wv::uniform(r->below), wv::uniform(r->above), wv::uniform(r->pos),
+                          wv::uniform(r->nvalid), o);
+    if (lane == 0) a.out_wave[base + j] = o;
+  }
+  if (base + lane < a.n) {
+    const rfid_gate_fsm_in r = a.in[base + lane];
+    GateRegs g;
+    g.avg_c = 0.0f; g.consumed = 0; g.stop = false;
+    g.f_n = r.n_samples; g.f_state = r.signal_state; g.f_pulses = r.num_pulses;
+    g.f_open = r.gate_open; g.f_ung = r.n_to_ungate; g.f_type = r.wtype;
+    rfid_gate_fsm_out o;
+    gate_fsm_selftest_one(r.mode, g, r.below, r.above, r.pos, r.nvalid, o);
+    a.out_lane[base + lane] = o;
+  }
+}
+
 // =========================================================================================
 // 6. synthetic replicas (SURVEY.md section 8 d, configs 1/3/5: noise replicas of a base trace made
 //    on the device).  out[s][i] = base[i] + sigma * (N(0,1) + j N(0,1)); the noise of replica r is a

@@ -99,6 +99,14 @@ FINE_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("fl
                        ("pow", "<f4"), ("reserved_", "<i4"), ("seg_re", "<f4", (8,)), ("seg_im", "<f4", (8,)), ("seg_pow", "<f4", (8,))])
 FINE_SEGMENTS, FINE_SEGMENT_BITS = 8, 16
 assert FINE_DTYPE.itemsize == 128
+GATE_FSM_IN_DTYPE = np.dtype([("mode", "<i4"), ("n_samples", "<i4"), ("signal_state", "<i4"), ("num_pulses", "<i4"),
+                              ("gate_open", "<i4"), ("n_to_ungate", "<i4"), ("wtype", "<i4"), ("nvalid", "<i4"), ("pos", "<i4"),
+                              ("reserved_", "<i4"), ("below", "<u8"), ("above", "<u8")])
+GATE_FSM_OUT_DTYPE = np.dtype([("n_samples", "<i4"), ("signal_state", "<i4"), ("num_pulses", "<i4"), ("gate_open", "<i4"),
+                               ("n_to_ungate", "<i4"), ("wtype", "<i4"), ("nvalid", "<i4"), ("stop", "<i4"), ("consumed", "<i4"),
+                               ("open_lane", "<i4"), ("open_type", "<i4"), ("reserved_", "<i4"), ("closedmask", "<u8"),
+                               ("openmask", "<u8")])
+assert GATE_FSM_IN_DTYPE.itemsize == 56 and GATE_FSM_OUT_DTYPE.itemsize == 64
 assert WINDOW_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 48
 assert SCORES_DTYPE.itemsize == 144 and STATS_DTYPE.itemsize == 1056
 
@@ -113,6 +121,7 @@ SIGNATURES = {
     "rfid_last_error": (C.c_char_p, [_vp]),
     "rfid_version": (C.c_char_p, []),
     "rfid_selftest": (_i, [_vp, _ip]),
+    "rfid_selftest_gate_fsm": (_i, [_vp, _vp, _i, _vp, _vp]),
     "rfid_mf_work": (_i, [_vp, _vp, _i, _vp, _i, _ip]),
     "rfid_gate_work": (_i, [_vp, _vp, _i, _vp, _i, _ip, _ip]),
     "rfid_decoder_work": (_i, [_vp, _vp, _i, _vp, _i, _ip, _ip, _vp, _vp]),

@@ -59,6 +59,16 @@ class Context:
         self._chk(self._lib.rfid_selftest(self._h, C.byref(n)))
         return n.value
 
+    def selftest_gate_fsm(self, records) -> Tuple[np.ndarray, np.ndarray]:
+        """rfid_selftest_gate_fsm: one step of the gate's state machine per GATE_FSM_IN_DTYPE record
+        -> (wave-uniform form, per-lane form), GATE_FSM_OUT_DTYPE records.  A test entry: nothing is judged here."""
+        rec = np.ascontiguousarray(records, dtype=capi.GATE_FSM_IN_DTYPE)
+        ow = np.zeros(len(rec), dtype=capi.GATE_FSM_OUT_DTYPE)
+        ol = np.zeros(len(rec), dtype=capi.GATE_FSM_OUT_DTYPE)
+        if len(rec):
+            self._chk(self._lib.rfid_selftest_gate_fsm(self._h, rec.ctypes.data, len(rec), ow.ctypes.data, ol.ctypes.data))
+        return ow, ol
+
     @property
     def stream_handle(self) -> int:
         return int(self._lib.rfid_ctx_stream(self._h) or 0)

@@ -350,6 +350,27 @@ typedef struct rfid_ls_report {
                              * their results): the partial fallback.  0: the rounds sufficed */
 } rfid_ls_report;
 
+/* One 64-sample step of the gate's edge / pulse / window state machine by itself (rfid_selftest_gate_fsm): the state in front
+ * of the step and the two threshold-vote masks (sample i of the step = bit i; disjoint; no bit at or past nvalid) ... */
+typedef struct {
+  int32_t mode;             /* 0 batch (the gate re-arms behind a window), 1 per call (the scan stops where a window closes) */
+  int32_t n_samples, signal_state, num_pulses, gate_open, n_to_ungate, wtype;
+  int32_t nvalid;           /* valid samples of the step, 0 .. 64 */
+  int32_t pos;              /* the step's first sample within the call (what `consumed` counts from) */
+  int32_t reserved_;
+  uint64_t below, above;    /* |x| < thresh, |x| > thresh */
+} rfid_gate_fsm_in;
+/* ... and what the step leaves: the state, which samples were "closed" (they update dc_est) and which lie in a window (the
+ * opening sample is both), the opening (open_lane 0xff: none), nvalid as returned (cut where a per-call scan stops) */
+typedef struct {
+  int32_t n_samples, signal_state, num_pulses, gate_open, n_to_ungate, wtype;
+  int32_t nvalid, stop;
+  int32_t consumed;         /* pos + samples taken when stop is set, else 0 */
+  int32_t open_lane, open_type;
+  int32_t reserved_;
+  uint64_t closedmask, openmask;
+} rfid_gate_fsm_out;
+
 typedef struct rfid_ctx rfid_ctx;
 
 /* ---- lifetime ------------------------------------------------------------------------ */
@@ -369,6 +390,11 @@ RFID_API int rfid_abi_version(void);
 /* device self-test of the wave-level primitives the kernels rely on (DPP wave shift,
  * IEEE division, double sqrt).  0 = all good, >0 = number of failing checks. */
 RFID_API int rfid_selftest(rfid_ctx *ctx, int *n_failed);
+/* test entry: the gate's step function on `n` caller-given records (host memory), each from its own state, in both forms the
+ * kernels call it in: out_wave[k] with wave-uniform arguments (scalar unit), out_lane[k] with one record per lane.  The
+ * caller holds the expected values (tests/gate_ref.py); nothing is judged here. */
+RFID_API int rfid_selftest_gate_fsm(rfid_ctx *ctx, const rfid_gate_fsm_in *in, int n, rfid_gate_fsm_out *out_wave,
+                                    rfid_gate_fsm_out *out_lane);
 
 /* ---- (1) streaming, host buffers: one call per reference work() ----------------------- */
 /* fir_filter_ccc(5,[1]*25): consumes all n_in samples, keeps the filter history and the decimation

@@ -62,10 +62,10 @@ def ragged_batch(synth_mod, B):
     return raw, lens
 
 
-def avg_ampl_pairs_leaving_binade(y):
-    """The oracle's avg_ampl trajectory over its matched-filter output y (gate_impl.cc:130-134: the in-order binary32 sum of
-    (|x| - |x[i-100]|) / 100) -> the pairs of full steps, past the first two, inside which some partial sum has another exponent
-    than the sum the pair starts from: there chain_add_scan_pair cannot apply and the chain is taken."""
+def avg_ampl(y):
+    """The oracle's |x| and avg_ampl after every sample of its matched-filter output y (gate_impl.cc:130-134: the in-order
+    binary32 sum of (|x| - |x[i-100]|) / 100) -> (amp, avg), binary32"""
+    y = np.asarray(y, dtype=np.complex64)
     amp = np.sqrt(y.real.astype(np.float64) ** 2 + y.imag.astype(np.float64) ** 2).astype(np.float32)
     old = np.concatenate([np.zeros(100, np.float32), amp])[: len(amp)]
     d = ((amp - old) / np.float32(100)).astype(np.float32)
@@ -74,6 +74,14 @@ def avg_ampl_pairs_leaving_binade(y):
     for i in range(len(d)):
         acc = np.float32(acc + d[i])
         avg[i] = acc
+    return amp, avg
+
+
+def avg_ampl_pairs_leaving_binade(y):
+    """The oracle's avg_ampl trajectory over its matched-filter output y -> the pairs of full steps, past the first two, inside
+    which some partial sum has another exponent than the sum the pair starts from: there chain_add_scan_pair cannot apply and
+    the chain is taken."""
+    _, avg = avg_ampl(y)
     expo = (avg.view(np.uint32) >> 23) & 0xff
     out = []
     for p in range(2, (len(y) // 64) // 2):

@@ -260,6 +260,18 @@ def selftest(x, num, den, carry):
     return outs
 
 
+def gate_fsm_selftest(records):
+    """gate_fsm_selftest_kernel on capi.GATE_FSM_IN_DTYPE records -> (wave-uniform form, per-lane form), GATE_FSM_OUT_DTYPE"""
+    rec = np.ascontiguousarray(records, dtype=capi.GATE_FSM_IN_DTYPE)
+    ow = np.zeros(len(rec), dtype=capi.GATE_FSM_OUT_DTYPE)
+    ol = np.zeros(len(rec), dtype=capi.GATE_FSM_OUT_DTYPE)
+    rc = lib().emu_gate_fsm_selftest(C.c_void_p(rec.ctypes.data), len(rec), C.c_void_p(ow.ctypes.data), C.c_void_p(ol.ctypes.data))
+    if rc == EMU_DEADLOCK:
+        _raise_deadlock(lib(), "gate_fsm_selftest")
+    assert rc == 0, rc
+    return ow, ol
+
+
 def chain_scan(x, carry):
     """-> (chain, scan, clean): the exact 63-deep chain, chain_add_scan (or its fallback), and whether the scan applied."""
     x = np.ascontiguousarray(x, dtype=np.float32)

@@ -698,6 +698,16 @@ int emu_selftest(const float *x, const float *num, const float *den, float carry
   return run.rc(0);
 }
 
+// gate_fsm_step on caller-given records: gate_fsm_selftest_kernel as rfid_selftest_gate_fsm launches it
+int emu_gate_fsm_selftest(const rfid_gate_fsm_in *in, int n, rfid_gate_fsm_out *out_wave, rfid_gate_fsm_out *out_lane) {
+  EmuRun run;
+  if (n <= 0) return 0;
+  GateFsmSelfTestArgs a;
+  a.in = in; a.out_wave = out_wave; a.out_lane = out_lane; a.n = n;
+  emu::launch(emu::Idx3{(unsigned)((n + 63) / 64), 1, 1}, emu::Idx3{64, 1, 1}, [&]() { gate_fsm_selftest_kernel(a); });
+  return run.rc(0);
+}
+
 // in-order sum: the integer-scan form against the chain; scan_out[64] = 1 when the scan was provably exact
 int emu_chain_scan(const float *x, float carry, float *chain_out, float *scan_out) {
   EmuRun run;
