@@ -1472,6 +1472,58 @@ int rfid_selftest_gate_fsm(rfid_ctx *c, const rfid_gate_fsm_in *in, int n, rfid_
   return rc;
 }
 
+// stream_stats_kernel by itself on a caller-given result table, with a workgroup shape and an input form of the caller's choice
+// (a test entry: the expected values are the caller's).  The summaries are made on the device by stats_summary() and lie in an
+// array of their own sized as rfid_batch_plan sizes d_sum, so a row's alignment is what a plan of this wmax gives it.
+int rfid_selftest_stats(rfid_ctx *c, const rfid_decode_result *res, const int32_t *wcount, int n_streams, int wmax, int waves,
+                        int from_summaries, int max_slot_number, int max_num_queries, int number_unique_tags, rfid_stream_stats *out) {
+  if (!c || !res || !wcount || !out || n_streams <= 0 || wmax <= 0 || waves < 1 || waves > STATS_MAX_WAVES || max_slot_number < 1)
+    return RFID_ERR_INVALID;
+  if ((int64_t)n_streams * wmax > 0x7fffffffLL) return RFID_ERR_UNSUPPORTED;
+  for (int s = 0; s < n_streams; ++s)
+    if (wcount[s] < 0 || wcount[s] > wmax) return RFID_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)n_streams * (size_t)wmax;
+  const size_t res_bytes = sizeof(rfid_decode_result) * n, wc_bytes = sizeof(int) * (size_t)n_streams,
+               out_bytes = sizeof(rfid_stream_stats) * (size_t)n_streams, sum_bytes = sizeof(int) * (n + 4);
+  rfid_decode_result *d_res = nullptr;
+  int *d_wc = nullptr, *d_sum = nullptr;
+  rfid_stream_stats *d_out = nullptr;
+  int rc = RFID_OK;
+  auto step = [&](hipError_t e) { if (e != hipSuccess && rc == RFID_OK) { snprintf(c->err, sizeof(c->err), "selftest_stats: %s", hipGetErrorString(e)); rc = RFID_ERR_HIP; } };
+  step(hipMalloc((void **)&d_res, res_bytes));
+  step(hipMalloc((void **)&d_wc, wc_bytes));
+  step(hipMalloc((void **)&d_out, out_bytes));
+  if (from_summaries) step(hipMalloc((void **)&d_sum, sum_bytes));
+  if (rc == RFID_OK) {
+    step(hipMemcpyAsync(d_res, res, res_bytes, hipMemcpyHostToDevice, c->stream));
+    step(hipMemcpyAsync(d_wc, wcount, wc_bytes, hipMemcpyHostToDevice, c->stream));
+    step(hipMemcpyAsync(d_out, out, out_bytes, hipMemcpyHostToDevice, c->stream));
+    if (d_sum) step(hipMemsetAsync(d_sum, 0xFF, sum_bytes, c->stream));     // (the four words behind the table: reads of tag 255)
+  }
+  if (rc == RFID_OK && d_sum) {
+    StatsSummaryArgs sa;
+    sa.res = d_res; sa.sum = d_sum; sa.n = (int64_t)n;
+    hipLaunchKernelGGL(stats_summary_selftest_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, sa);
+    step(hipGetLastError());
+  }
+  if (rc == RFID_OK) {
+    StatsArgs a;
+    a.res = d_res; a.wcount = d_wc; a.wmax = wmax; a.n_streams = n_streams;
+    a.max_slot_number = max_slot_number; a.max_num_queries = max_num_queries; a.number_unique_tags = number_unique_tags;
+    a.out = d_out; a.sum = d_sum;
+    hipLaunchKernelGGL(stream_stats_kernel, dim3((unsigned)n_streams), dim3(64 * (unsigned)waves), 0, c->stream, a);
+    step(hipGetLastError());
+    step(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  }
+  step(hipStreamSynchronize(c->stream));
+  if (d_res) (void)hipFree(d_res);
+  if (d_wc) (void)hipFree(d_wc);
+  if (d_out) (void)hipFree(d_out);
+  if (d_sum) (void)hipFree(d_sum);
+  return rc;
+}
+
 // ======================================================================================
 // (2) batched offline path
 // ======================================================================================

@@ -2492,6 +2492,18 @@ RFID_KERNEL(64 * STATS_MAX_WAVES) void stream_stats_kernel(StatsArgs a) {
   }
 }
 
+// the one-word summaries of a caller-given result table, as the decoders leave them (rfid_selftest_stats: the statistics
+// kernel by itself on its second input form)
+struct StatsSummaryArgs {
+  const rfid_decode_result *res;  // [n]
+  int *sum;                       // [n]
+  int64_t n;
+};
+RFID_KERNEL(256) void stats_summary_selftest_kernel(StatsSummaryArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + (int64_t)threadIdx.x;
+  if (i < a.n) a.sum[i] = stats_summary(a.res[i]);
+}
+
 // =========================================================================================
 // 5. self-test of the primitives the exactness argument rests on
 // =========================================================================================

@@ -122,6 +122,7 @@ SIGNATURES = {
     "rfid_version": (C.c_char_p, []),
     "rfid_selftest": (_i, [_vp, _ip]),
     "rfid_selftest_gate_fsm": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "rfid_selftest_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "rfid_mf_work": (_i, [_vp, _vp, _i, _vp, _i, _ip]),
     "rfid_gate_work": (_i, [_vp, _vp, _i, _vp, _i, _ip, _ip]),
     "rfid_decoder_work": (_i, [_vp, _vp, _i, _vp, _i, _ip, _ip, _vp, _vp]),

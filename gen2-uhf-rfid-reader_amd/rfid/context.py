@@ -69,6 +69,23 @@ class Context:
             self._chk(self._lib.rfid_selftest_gate_fsm(self._h, rec.ctypes.data, len(rec), ow.ctypes.data, ol.ctypes.data))
         return ow, ol
 
+    def selftest_stats(self, results, wcount, waves: int, from_summaries: bool, max_slot_number: int, max_num_queries: int,
+                       number_unique_tags: int, out=None) -> np.ndarray:
+        """rfid_selftest_stats: the statistics kernel by itself on a [n_streams][wmax] table of RESULT_DTYPE records, `waves`
+        wavefronts per trace, from the records or from their one-word summaries.  out: STATS_DTYPE rows the device copy starts
+        from (default zeros; rows behind n_streams are not passed) -> the rows after the launch.  A test entry: nothing is
+        judged here."""
+        res = np.ascontiguousarray(results, dtype=capi.RESULT_DTYPE)
+        wc = np.ascontiguousarray(wcount, dtype=np.int32)
+        n_streams, wmax = res.shape
+        assert len(wc) == n_streams
+        st = np.zeros(n_streams, dtype=capi.STATS_DTYPE) if out is None else np.ascontiguousarray(out, dtype=capi.STATS_DTYPE).copy()
+        assert len(st) >= n_streams
+        self._chk(self._lib.rfid_selftest_stats(self._h, res.ctypes.data, wc.ctypes.data, n_streams, wmax, int(waves),
+                                                1 if from_summaries else 0, int(max_slot_number), int(max_num_queries),
+                                                int(number_unique_tags), st.ctypes.data))
+        return st
+
     @property
     def stream_handle(self) -> int:
         return int(self._lib.rfid_ctx_stream(self._h) or 0)

@@ -395,6 +395,15 @@ RFID_API int rfid_selftest(rfid_ctx *ctx, int *n_failed);
  * caller holds the expected values (tests/gate_ref.py); nothing is judged here. */
 RFID_API int rfid_selftest_gate_fsm(rfid_ctx *ctx, const rfid_gate_fsm_in *in, int n, rfid_gate_fsm_out *out_wave,
                                     rfid_gate_fsm_out *out_lane);
+/* test entry: the per-trace statistics kernel by itself on a caller-given result table res[n_streams][wmax] (host memory;
+ * wcount[s] <= wmax records of row s count), one workgroup of `waves` (1 .. 16) wavefronts per trace -- the batch path launches
+ * 1, or 16 for wmax > 2048.  from_summaries != 0: the kernel reads the results' one-word summaries, made on the device as the
+ * decoders make them, from an array sized as a plan's (n_streams * wmax + 4 words), instead of the records.  max_slot_number
+ * (>= 1) is 2^fixed_q.  out[n_streams] is copied to the device before the launch and back after it.  The caller holds the
+ * expected values (tests/stats_ref.py); nothing is judged here. */
+RFID_API int rfid_selftest_stats(rfid_ctx *ctx, const rfid_decode_result *res, const int32_t *wcount, int n_streams, int wmax,
+                                 int waves, int from_summaries, int max_slot_number, int max_num_queries,
+                                 int number_unique_tags, rfid_stream_stats *out);
 
 /* ---- (1) streaming, host buffers: one call per reference work() ----------------------- */
 /* fir_filter_ccc(5,[1]*25): consumes all n_in samples, keeps the filter history and the decimation

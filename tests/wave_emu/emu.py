@@ -272,6 +272,26 @@ def gate_fsm_selftest(records):
     return ow, ol
 
 
+def stats_selftest(results, wcount, waves, from_summaries, max_slot_number, max_num_queries, number_unique_tags, out=None):
+    """stream_stats_kernel as rfid_selftest_stats launches it: a [n_streams][wmax] table of capi.RESULT_DTYPE records, `waves`
+    wavefronts per trace, from the records or from their one-word summaries.  out: STATS_DTYPE rows the kernel writes into
+    (a copy; it may hold rows behind n_streams, which the kernel must leave alone) -> the rows after the launch."""
+    res = np.ascontiguousarray(results, dtype=capi.RESULT_DTYPE)
+    wc = np.ascontiguousarray(wcount, dtype=np.int32)
+    n_streams, wmax = res.shape
+    assert len(wc) == n_streams
+    st = np.zeros(n_streams, dtype=capi.STATS_DTYPE) if out is None else np.ascontiguousarray(out, dtype=capi.STATS_DTYPE).copy()
+    assert len(st) >= n_streams
+    rc = lib().emu_stats_selftest(C.c_void_p(res.ctypes.data), C.c_void_p(wc.ctypes.data), n_streams, wmax, int(waves),
+                                  1 if from_summaries else 0, int(max_slot_number), int(max_num_queries), int(number_unique_tags),
+                                  C.c_void_p(st.ctypes.data))
+    if rc == EMU_DEADLOCK:
+        _raise_deadlock(lib(), "stats_selftest")
+    assert rc != -2, "stream_stats_kernel: a 16-byte load on an address that is no multiple of 16"
+    assert rc == 0, rc
+    return st
+
+
 def chain_scan(x, carry):
     """-> (chain, scan, clean): the exact 63-deep chain, chain_add_scan (or its fallback), and whether the scan applied."""
     x = np.ascontiguousarray(x, dtype=np.float32)

@@ -708,6 +708,37 @@ int emu_gate_fsm_selftest(const rfid_gate_fsm_in *in, int n, rfid_gate_fsm_out *
   return run.rc(0);
 }
 
+// stream_stats_kernel on a caller-given result table, as rfid_selftest_stats launches it: `waves` wavefronts per trace, from the
+// records or from their summaries (stats_summary_selftest_kernel; a fresh 256-byte aligned [n_streams * wmax + 4] array, as a
+// plan's d_sum, the four words behind the table preset to reads of tag 255).  The kernel writes the caller's `out` itself.
+// -2: the kernel issued a 16-byte load on an address that is no multiple of 16 (the device form reads an int4).
+int emu_stats_selftest(const rfid_decode_result *res, const int *wcount, int n_streams, int wmax, int waves, int from_summaries,
+                       int max_slot_number, int max_num_queries, int number_unique_tags, rfid_stream_stats *out) {
+  EmuRun run;
+  if (n_streams <= 0 || wmax <= 0 || waves < 1 || waves > STATS_MAX_WAVES || max_slot_number < 1) return -1;
+  for (int s = 0; s < n_streams; ++s)
+    if (wcount[s] < 0 || wcount[s] > wmax) return -1;
+  const size_t n = (size_t)n_streams * (size_t)wmax;
+  int *sum = nullptr;
+  if (from_summaries) {
+    void *p = nullptr;
+    if (posix_memalign(&p, 256, sizeof(int) * (n + 4)) != 0) return -1;
+    sum = (int *)p;
+    memset(sum, 0xFF, sizeof(int) * (n + 4));
+    StatsSummaryArgs ss;
+    ss.res = res; ss.sum = sum; ss.n = (int64_t)n;
+    emu::launch(emu::Idx3{(unsigned)((n + 255) / 256), 1, 1}, emu::Idx3{256, 1, 1}, [&]() { stats_summary_selftest_kernel(ss); });
+  }
+  StatsArgs sa;
+  sa.res = res; sa.wcount = wcount; sa.wmax = wmax; sa.n_streams = n_streams;
+  sa.max_slot_number = max_slot_number; sa.max_num_queries = max_num_queries; sa.number_unique_tags = number_unique_tags;
+  sa.out = out; sa.sum = sum;
+  emu::g_misaligned16 = 0;
+  emu::launch(emu::Idx3{(unsigned)n_streams, 1, 1}, emu::Idx3{64 * (unsigned)waves, 1, 1}, [&]() { stream_stats_kernel(sa); });
+  free(sum);
+  return run.rc(emu::g_misaligned16 ? -2 : 0);      // (-2: a 16-byte load of the kernel was not 16-byte aligned)
+}
+
 // in-order sum: the integer-scan form against the chain; scan_out[64] = 1 when the scan was provably exact
 int emu_chain_scan(const float *x, float carry, float *chain_out, float *scan_out) {
   EmuRun run;

@@ -66,6 +66,7 @@ extern thread_local Block *g_blk;
 extern thread_local Fiber *g_cur;
 extern thread_local Idx3 g_block_idx, g_grid_dim, g_block_dim;
 extern thread_local ucontext_t g_sched;
+inline long g_misaligned16 = 0;   // wv::load4_i32 calls on an address that is no multiple of 16 (a count for tests; not exact under the concurrent schedules)
 
 void yield();
 void launch(Idx3 grid, Idx3 block, const std::function<void()> &body, const char *name = "kernel");
@@ -250,7 +251,12 @@ static inline void pk_add(float2 &acc, const float2 q) {
 static inline void set_priority_high() {}
 template <int P> static inline void set_priority() {}
 static inline void backoff() { emu::g_cur->grid_calls++; emu::g_cur->at = "backoff"; emu::yield(); }   // (counts as progress: a spin of its own)
-static inline void load4_i32(const int *p, int &a, int &b, int &c, int &d) { a = p[0]; b = p[1]; c = p[2]; d = p[3]; }
+// (the device form reads an int4: the address must be a multiple of 16.  Here any address works, so the loads that are not
+// are counted, for the entries that check the count: emu_stats_selftest)
+static inline void load4_i32(const int *p, int &a, int &b, int &c, int &d) {
+  if (((uintptr_t)p & 15u) != 0u) emu::g_misaligned16++;
+  a = p[0]; b = p[1]; c = p[2]; d = p[3];
+}
 static inline int atomic_add(int *p, int v) { int o = *p; *p = o + v; return o; }
 static inline int atomic_min(int *p, int v) { int o = *p; if (v < o) *p = v; return o; }
 static inline int atomic_max(int *p, int v) { int o = *p; if (v > o) *p = v; return o; }
