@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdarg>
 #include <ctime>
 #include <pthread.h>
 #include <cstdio>
@@ -21,6 +22,7 @@
 
 #include "rfid_host_math.h"
 #include "rfid_kernels.hpp"
+#include "rfid_stage.hpp"
 #include "rfid_inventory.hpp"
 #include "rfid_tracks.hpp"
 #include "rfid_quality.hpp"
@@ -316,50 +318,36 @@ struct rfid_ctx {
     int64_t *d_off = nullptr;         // [B_plan x max_tags + 1]
     int *d_base = nullptr, *d_head = nullptr;
   } trk;
-  // ---- quality stage (rfid_batch_plan_quality): lives and dies with the tracks workspace ----
-  struct Quality : Stage {
-    rfid_read_quality *d_table = nullptr;   // [B_plan][rows]
-    rfid_read_quality *d_packed = nullptr;  // [trk.cap]: aligned with the tracks
-    int *d_nrows = nullptr;           // [B_plan]: EPC windows before the cut-off
-    int rows = 0;                     // ceil(wmax / 2)
+  // ---- the five window-table stages: one [B_plan][rows] table of fixed-size records each (csrc/rfid_stage.hpp) ----
+  struct Table : Stage {
+    void *d_table = nullptr;          // [B_plan][rows] records of the stage's type
+    template <typename R> R *table() const { return static_cast<R *>(d_table); }
+    int *d_nrows = nullptr;           // [B_plan]: rows before the cut-off
+    int rows = 0;                     // per trace: wmax (the row of a window is its seq), or ceil(wmax / 2) (of an EPC window: seq >> 1)
     int n_streams = 0;                // traces it covered
+  };
+  // quality (rfid_batch_plan_quality): lives and dies with the tracks workspace
+  struct Quality : Table {
+    rfid_read_quality *d_packed = nullptr;  // [trk.cap]: aligned with the tracks
   } qual;
-  // ---- repair stage (rfid_batch_plan_repair): lives and dies with the inventory workspace; a side branch behind the inventory ----
-  struct Repair : Stage {
-    rfid_repair *d_table = nullptr;   // [B_plan][rows]
+  // repair (rfid_batch_plan_repair): lives and dies with the inventory workspace; a side branch behind the inventory
+  struct Repair : Table {
     rfid_repair *d_packed = nullptr;  // [B_plan x rows]: the repaired rows, ordered by (stream, seq)
-    int *d_nrows = nullptr;           // [B_plan]: EPC windows before the cut-off
     int *d_counts = nullptr, *d_off = nullptr;   // [B_plan][blocks]: repaired rows of a block of REP_ROWS rows / of the blocks before it
     int *d_head = nullptr;            // [0] repaired rows in all
-    int rows = 0, blocks = 0;         // ceil(wmax / 2), ceil(rows / REP_ROWS)
-    int n_streams = 0;                // traces it covered
+    int blocks = 0;                   // ceil(rows / REP_ROWS)
   } rep;
-  DevBuf rep_one;                     // rfid_repair_window: the window, its result, the record
-  // ---- slots stage (rfid_batch_plan_slots): lives and dies with the plan; needs the pass's statistics only ----
-  struct Slots : Stage {
-    rfid_window_moments *d_table = nullptr;   // [B_plan][wmax]: the row of a window is its seq
-    int *d_nrows = nullptr;           // [B_plan]: windows before the cut-off
-    int rows = 0;                     // wmax
-    int n_streams = 0;                // traces it covered
-  } slt;
-  DevBuf mom_one;                     // rfid_window_moments_of: the windows, their records
-  // ---- commands stage (rfid_batch_plan_commands): lives and dies with the plan; needs the pass's statistics only ----
-  struct Commands : Stage {
-    rfid_command *d_table = nullptr;  // [B_plan][wmax]: the row of a window is its seq
-    int *d_nrows = nullptr;           // [B_plan]: windows before the cut-off
-    int rows = 0;                     // wmax
-    int n_streams = 0;                // traces it covered
-  } cmd;
-  DevBuf cmd_one;                     // rfid_commands_of: the spans, their levels, their records
-  // ---- fine stage (rfid_batch_plan_fine): lives and dies with the tracks workspace ----
-  struct Fine : Stage {
-    rfid_read_fine *d_table = nullptr;      // [B_plan][rows]
+  // slots, commands (rfid_batch_plan_slots / _commands): live and die with the plan; need the pass's statistics only
+  struct Slots : Table {} slt;
+  struct Commands : Table {} cmd;
+  // fine (rfid_batch_plan_fine): lives and dies with the tracks workspace
+  struct Fine : Table {
     rfid_read_fine *d_packed = nullptr;     // [trk.cap]: aligned with the tracks
-    int *d_nrows = nullptr;           // [B_plan]: EPC windows before the cut-off
-    int rows = 0;                     // ceil(wmax / 2)
-    int n_streams = 0;                // traces it covered
   } fin;
-  DevBuf fin_one;                     // rfid_fine_window: the window, its result, the record
+  // What the per-call forms (rfid_repair_window, rfid_window_moments_of, rfid_commands_of, rfid_fine_window) upload, compute on
+  // and download from.  One buffer for the four: each synchronises c->stream before it returns, so no two of them ever have
+  // work in flight on it, and grow() may free and reallocate it.
+  DevBuf one;
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
   // (rfid_batch_stats ran behind the last decode), the inventory was enqueued behind those statistics, the tracks behind
   // that inventory.  A stage is current only while every stage before it is: one ordered level, moved by mark_current and
@@ -390,6 +378,13 @@ int fail(rfid_ctx *c, int code, const char *what, hipError_t e = hipSuccess) {
     else
       snprintf(c->err, sizeof(c->err), "%s", what);
   }
+  return code;
+}
+__attribute__((format(printf, 3, 4))) int failf(rfid_ctx *c, int code, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(c->err, sizeof(c->err), fmt, ap);
+  va_end(ap);
   return code;
 }
 
@@ -556,35 +551,12 @@ int stage_fetch_head(rfid_ctx *c, const char *fn, const int *d_reads_head, int64
   return RFID_OK;
 }
 
-// One trace's rows of a stage's table (quality, repair: one record per EPC window; slots, commands: one per window -- `what`; `rows` of
-// them per trace).  *n: those before the cut-off (d_nrows).  RFID_ERR_CAPACITY under `fn`'s name when `cap` is smaller than
-// that; else up to `cap` rows are copied.
-int stage_fetch_rows(rfid_ctx *c, const char *fn, const int *d_nrows, const void *table, size_t record_bytes, int rows, int n_streams,
-                     int stream, void *out, int64_t cap, int64_t *n, const char *what = "EPC windows") {
-  if (stream < 0 || stream >= n_streams) return RFID_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
-  int nrows = 0;
-  HIPCHK(c, hipMemcpyAsync(&nrows, d_nrows + stream, sizeof(nrows), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  *n = nrows;
-  if (nrows > cap) {
-    snprintf(c->err, sizeof(c->err), "%s: cap is smaller than the number of %s", fn, what);
-    return RFID_ERR_CAPACITY;
-  }
-  const int64_t take = (cap < rows) ? cap : rows;          // (the zeroed rows behind the cut-off too, as far as there is room)
-  if (take > 0) {
-    HIPCHK(c, hipMemcpyAsync(out, (const char *)table + (size_t)stream * (size_t)rows * record_bytes, record_bytes * (size_t)take, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return RFID_OK;
-}
-
 // ---- launch geometry of the kernels that take one workgroup per trace (statistics, inventory, tracks) ----
 // one wave per trace; sixteen when a trace can hold thousands of windows (few long traces)
 static_assert(STATS_MAX_WAVES == INV_MAX_WAVES, "one rule for the three kernels");
 bool wide_traces(const rfid_ctx *c) { return c->wmax > 2048; }
 dim3 trace_block(const rfid_ctx *c) { return dim3(wide_traces(c) ? 64 * INV_MAX_WAVES : 64); }
-// the one workgroup of an offsets scan over n traces (scan_share / scan_partials, csrc/rfid_inventory.hpp)
+// the one workgroup of an offsets scan over n traces (scan_share / scan_partials, csrc/rfid_stage.hpp)
 dim3 scan_block(int n) { return dim3((unsigned)((n >= INV_SCAN_THREADS) ? INV_SCAN_THREADS : ((n + 63) & ~63))); }
 // a persistent grid: one single-wave workgroup per item, at most `most` of them (and one for nothing)
 dim3 persistent_grid(int64_t items, int64_t most) { return dim3((unsigned)(items < most ? (items > 0 ? items : 1) : most)); }
@@ -703,42 +675,22 @@ int set_tails_on_stream2(rfid_ctx *c) {
   return RFID_OK;
 }
 
-void free_quality(rfid_ctx *c) {
-  stage_free(c->qual);
-  c->qual.rows = 0;
-}
-
-void free_fine(rfid_ctx *c) {
-  stage_free(c->fin);
-  c->fin.rows = 0;
+void table_free(rfid_ctx::Table &t) {
+  stage_free(t);
+  t.rows = 0;
 }
 
 void free_tracks(rfid_ctx *c) {
-  free_quality(c);                     // (sized by this workspace, and reading it)
-  free_fine(c);                        // (likewise)
+  table_free(c->qual);                 // (sized by this workspace, and reading it)
+  table_free(c->fin);                  // (likewise)
   invalidate_from(c, rfid_ctx::CUR_TRACKS);
   stage_free(c->trk);
   c->trk.cap = 0;
 }
 
-void free_repair(rfid_ctx *c) {
-  stage_free(c->rep);
-  c->rep.rows = 0; c->rep.blocks = 0;
-}
-
-void free_slots(rfid_ctx *c) {
-  stage_free(c->slt);
-  c->slt.rows = 0;
-}
-
-void free_commands(rfid_ctx *c) {
-  stage_free(c->cmd);
-  c->cmd.rows = 0;
-}
-
 void free_inventory(rfid_ctx *c) {
   free_tracks(c);                      // (sized by this workspace, and reading it)
-  free_repair(c);                      // (reading it)
+  table_free(c->rep);                  // (reading it)
   invalidate_from(c, rfid_ctx::CUR_INVENTORY);
   stage_free(c->inv);
   c->inv.max_tags = 0;
@@ -746,8 +698,8 @@ void free_inventory(rfid_ctx *c) {
 
 void free_plan(rfid_ctx *c) {
   free_inventory(c);
-  free_slots(c);
-  free_commands(c);
+  table_free(c->slt);
+  table_free(c->cmd);
   invalidate_from(c, rfid_ctx::CUR_STATS);
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
@@ -775,6 +727,141 @@ int join_tails(rfid_ctx *c) {
       if (hipStreamWaitEvent(c->stream, c->ev_tail_done[i], 0) != hipSuccess) return RFID_ERR_HIP;
       c->tail_recorded[i] = false;
     }
+  return RFID_OK;
+}
+
+// ---- the five window-table stages (quality, repair, slots, commands, fine): what their plan, enqueue and get functions share ----
+// A stage's description: what its checks ask for and how its messages name it.
+struct TableStage {
+  const char *name;      // as in rfid_batch_<name>
+  bool inv, trk;         // the workspaces that must exist beside the plan's: the inventory's, the tracks'
+  int level;             // how current (rfid_ctx::Current) the last pass must be: the stage it is enqueued behind
+  bool inv_traces;       // its traces are those the inventory covered (c->inv.n_streams), not c->B
+  const char *rows;      // what a row of its table is
+};
+constexpr TableStage ST_QUALITY = {"quality", true, true, rfid_ctx::CUR_TRACKS, true, "EPC windows"};
+constexpr TableStage ST_REPAIR = {"repair", true, false, rfid_ctx::CUR_INVENTORY, true, "EPC windows"};
+constexpr TableStage ST_SLOTS = {"slots", false, false, rfid_ctx::CUR_STATS, false, "windows"};
+constexpr TableStage ST_COMMANDS = {"commands", false, false, rfid_ctx::CUR_STATS, false, "windows"};
+constexpr TableStage ST_FINE = {"fine", true, true, rfid_ctx::CUR_TRACKS, true, "EPC windows"};
+
+bool table_needs_met(const rfid_ctx *c, const TableStage &d) { return (!d.inv || c->inv.blk) && (!d.trk || c->trk.blk); }
+
+// rfid_batch_plan_<name>: the checks, then the workspace anew -- `pieces` in one allocation (stage_alloc), `rows` per trace
+int table_plan(rfid_ctx *c, rfid_ctx::Table &t, const TableStage &d, int rows, std::initializer_list<StagePiece> pieces) {
+  if (!c->B_plan || !table_needs_met(c, d))
+    return failf(c, RFID_ERR_STATE, "rfid_batch_plan_%s: no plan%s", d.name,
+                 d.trk ? " with a tracks workspace (rfid_batch_plan_tracks)" : (d.inv ? " with an inventory workspace (rfid_batch_plan_inventory)" : " (rfid_batch_plan)"));
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  table_free(t);
+  char what[64];
+  snprintf(what, sizeof(what), "rfid_batch_plan_%s: workspace allocation", d.name);
+  const int r = stage_alloc(c, t, what, pieces);
+  if (r) return r;
+  t.rows = rows;
+  return RFID_OK;
+}
+
+// rfid_batch_<name>, up to its launches: the checks, the main stream behind the last pass, *n traces, what the pass left in `pass`,
+// the stage's first event
+int table_begin(rfid_ctx *c, rfid_ctx::Table &t, const TableStage &d, int *n, StagePass *pass) {
+  if (!c->B || !table_needs_met(c, d) || !t.blk)
+    return failf(c, RFID_ERR_STATE, "rfid_batch_%s: no plan with a %s workspace (rfid_batch_plan_%s)", d.name, d.name, d.name);
+  if (d.level == rfid_ctx::CUR_STATS) {
+    if (c->current < d.level) return failf(c, RFID_ERR_STATE, "rfid_batch_%s: no pass with statistics yet", d.name);
+  } else {
+    const bool tracks = d.level == rfid_ctx::CUR_TRACKS;
+    if (!(tracks ? c->trk.enqueued : c->inv.enqueued) || c->current < d.level)
+      return failf(c, RFID_ERR_STATE, "rfid_batch_%s: no rfid_batch_%s behind the last pass", d.name, tracks ? "tracks" : "inventory");
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  // as rfid_batch_inventory: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
+  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
+  { int rj = join_tails(c); if (rj) return rj; }
+  *n = d.inv_traces ? c->inv.n_streams : c->B;
+  pass->y = c->y(); pass->y_stride = c->y_stride; pass->wtab = c->cur.d_wtab; pass->res = c->cur.d_res;
+  pass->wcount = c->cur.d_wcount; pass->stats = c->cur.d_stats; pass->wmax = c->wmax; pass->n_streams = *n;
+  return stage_record(c, t, 0);
+}
+
+// ... and behind them: the second event, the pass's y has been read again, what the table now covers
+int table_end(rfid_ctx *c, rfid_ctx::Table &t, int n) {
+  { int r = stage_record(c, t, 1); if (r) return r; }
+  { int r = y_read_again(c); if (r) return r; }
+  t.enqueued = true;
+  t.n_streams = n;
+  return RFID_OK;
+}
+
+// rfid_batch_get_window_* (`fn`): one trace's rows of the table.  *n: those before the cut-off (d_nrows).  RFID_ERR_CAPACITY
+// when `cap` is smaller than that; else up to `cap` rows are copied.
+int table_get_rows(rfid_ctx *c, const rfid_ctx::Table &t, const TableStage &d, const char *fn, size_t record_bytes, int stream, void *out,
+                   int64_t cap, int64_t *n) {
+  if (!n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
+  if (!t.blk || !t.enqueued) return failf(c, RFID_ERR_STATE, "%s: no rfid_batch_%s behind this plan", fn, d.name);
+  if (stream < 0 || stream >= t.n_streams) return RFID_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  int nrows = 0;
+  HIPCHK(c, hipMemcpyAsync(&nrows, t.d_nrows + stream, sizeof(nrows), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  *n = nrows;
+  if (nrows > cap) return failf(c, RFID_ERR_CAPACITY, "%s: cap is smaller than the number of %s", fn, d.rows);
+  const int64_t take = (cap < t.rows) ? cap : t.rows;      // (the zeroed rows behind the cut-off too, as far as there is room)
+  if (take > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, (const char *)t.d_table + (size_t)stream * (size_t)t.rows * record_bytes, record_bytes * (size_t)take, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return RFID_OK;
+}
+
+// rfid_batch_get_<name>: the table's records of the CRC-verified reads (d_packed), aligned with the tracks
+int table_get_aligned(rfid_ctx *c, const rfid_ctx::Table &t, const TableStage &d, const void *d_packed, size_t record_bytes, void *out,
+                      int64_t cap, int64_t *n) {
+  if (!n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
+  char fn[48];
+  snprintf(fn, sizeof(fn), "rfid_batch_get_%s", d.name);
+  if (!c->inv.blk || !c->trk.blk || !t.blk || !t.enqueued) return failf(c, RFID_ERR_STATE, "%s: no rfid_batch_%s behind this plan", fn, d.name);
+  HIPCHK(c, hipSetDevice(c->device));
+  int n_entries = 0;
+  { int r = stage_fetch_head(c, fn, c->trk.d_head, cap, n, &n_entries); if (r) return r; }
+  if (*n > 0) {
+    HIPCHK(c, hipMemcpyAsync(out, d_packed, record_bytes * (size_t)*n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  return RFID_OK;
+}
+
+// table_gather_kernel<words> behind a table kernel: its arguments, and a word per thread up to eight workgroups per compute unit
+TableGatherArgs gather_args(const rfid_ctx *c, const rfid_ctx::Table &t, void *d_packed, int n) {
+  TableGatherArgs g;
+  g.reads = c->trk.d_reads; g.head = c->trk.d_head; g.cap = c->trk.cap; g.table = t.table<const int>(); g.n_streams = n; g.rows = t.rows;
+  g.out = (int *)d_packed;
+  return g;
+}
+dim3 gather_grid(const rfid_ctx *c, int words) {
+  const int64_t most = (int64_t)c->n_cus * 8;
+  int64_t blocks = (c->trk.cap * words + TABLE_GATHER_THREADS - 1) / TABLE_GATHER_THREADS;
+  if (blocks > most) blocks = most;
+  if (blocks < 1) blocks = 1;
+  return dim3((unsigned)blocks);
+}
+
+// rfid_repair_window / rfid_fine_window (`fn`): one EPC window and its result up (c->one), `launch` on them, the record down
+template <typename R, typename Launch>
+int one_window(rfid_ctx *c, const char *fn, const rfid_cf32 *gated, const rfid_decode_result *res, R *out, Launch launch) {
+  if (!c || !gated || !res || !out) return RFID_ERR_INVALID;
+  if (res->type != RFID_DECODE_EPC) return failf(c, RFID_ERR_INVALID, "%s: not the result of an EPC window", fn);
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_w = up256(sizeof(float2) * (size_t)EPC_WIN), sz_r = up256(sizeof(rfid_decode_result));
+  { int r = grow(c, c->one, sz_w + sz_r + sizeof(R)); if (r) return r; }
+  char *b = (char *)c->one.p;
+  HIPCHK(c, hipMemcpyAsync(b, gated, sizeof(float2) * (size_t)EPC_WIN, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res), hipMemcpyHostToDevice, c->stream));
+  launch((const float2 *)b, (const rfid_decode_result *)(b + sz_w), (R *)(b + sz_w + sz_r));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
 }
 
@@ -1246,7 +1333,7 @@ int rfid_ctx_destroy(rfid_ctx *c) {
   la_free(c);
   sio_free(c);
   free_plan(c);
-  void *ptrs[] = {c->d_small, c->s_in.p, c->s_out.p, c->synth_tab.p, c->ls2_ws.p, c->ls2_ws_alt.p, c->rep_one.p, c->mom_one.p, c->cmd_one.p, c->fin_one.p};
+  void *ptrs[] = {c->d_small, c->s_in.p, c->s_out.p, c->synth_tab.p, c->ls2_ws.p, c->ls2_ws_alt.p, c->one.p};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   if (c->ls2_host) (void)hipHostFree(c->ls2_host);
@@ -1895,77 +1982,40 @@ int rfid_batch_tracks_ms(rfid_ctx *c, float *ms) {
 // ---- quality stage: per-read SNR and decision margin, behind the tracks of a pass (csrc/rfid_quality.hpp) ----
 int rfid_batch_plan_quality(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
-  if (!c->B_plan || !c->inv.blk || !c->trk.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_quality: no plan with a tracks workspace (rfid_batch_plan_tracks)");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   rfid_ctx::Quality &q = c->qual;
-  free_quality(c);
   // EPC windows are every other window: ceil(wmax / 2) rows per trace, as many packed records as the tracks have reads
   const int rows = (c->wmax + 1) / 2;
-  const int r = stage_alloc(c, q, "rfid_batch_plan_quality: workspace allocation",
-                            {{(void **)&q.d_table, sizeof(rfid_read_quality) * (size_t)rows * (size_t)c->B_plan},
-                             {(void **)&q.d_packed, sizeof(rfid_read_quality) * (size_t)c->trk.cap},
-                             {(void **)&q.d_nrows, sizeof(int) * (size_t)c->B_plan}});
-  if (r) return r;
-  q.rows = rows;
-  return RFID_OK;
+  return table_plan(c, q, ST_QUALITY, rows,
+                    {{&q.d_table, sizeof(rfid_read_quality) * (size_t)rows * (size_t)c->B_plan},
+                     {(void **)&q.d_packed, sizeof(rfid_read_quality) * (size_t)c->trk.cap},
+                     {(void **)&q.d_nrows, sizeof(int) * (size_t)c->B_plan}});
 }
 
 int rfid_batch_quality(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
-  rfid_ctx::Tracks &t = c->trk;
   rfid_ctx::Quality &q = c->qual;
-  if (!c->B || !c->inv.blk || !t.blk || !q.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_quality: no plan with a quality workspace (rfid_batch_plan_quality)");
-  if (!t.enqueued || c->current < rfid_ctx::CUR_TRACKS) return fail(c, RFID_ERR_STATE, "rfid_batch_quality: no rfid_batch_tracks behind the last pass");
-  HIPCHK(c, hipSetDevice(c->device));
-  // as rfid_batch_inventory: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
-  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
-  { int rj = join_tails(c); if (rj) return rj; }
-  const int n = c->inv.n_streams;     // the traces the inventory and the tracks covered
+  int n = 0;                          // the traces the inventory and the tracks covered
   QualArgs a;
-  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->cur.d_wtab; a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats;
-  a.wmax = c->wmax; a.n_streams = n; a.rows = q.rows; a.table = q.d_table; a.nrows = q.d_nrows;
-  QualGatherArgs g;
-  g.reads = t.d_reads; g.head = t.d_head; g.cap = t.cap; g.table = q.d_table; g.n_streams = n; g.rows = q.rows; g.out = q.d_packed;
-  { int r = stage_record(c, q, 0); if (r) return r; }
+  { int r = table_begin(c, q, ST_QUALITY, &n, &a.p); if (r) return r; }
+  a.rows = q.rows; a.table = q.table<rfid_read_quality>(); a.nrows = q.d_nrows;
+  const TableGatherArgs g = gather_args(c, q, q.d_packed, n);
   // single-wave workgroups, each walking packs of eight rows (12.6 KB of LDS each)
   const int64_t items = (int64_t)n * ((q.rows + QUAL_PACK - 1) / QUAL_PACK);
   hipLaunchKernelGGL(quality_kernel, persistent_grid(items, (int64_t)c->n_cus * QUAL_WGS_PER_CU), dim3(64), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
-  const int64_t words = t.cap * QUAL_WORDS, gmost = (int64_t)c->n_cus * 8;
-  int64_t gblocks = (words + QUAL_GATHER_THREADS - 1) / QUAL_GATHER_THREADS;
-  if (gblocks > gmost) gblocks = gmost;
-  if (gblocks < 1) gblocks = 1;
-  hipLaunchKernelGGL(quality_gather_kernel, dim3((unsigned)gblocks), dim3(QUAL_GATHER_THREADS), 0, c->stream, g);
+  hipLaunchKernelGGL(table_gather_kernel<QUAL_WORDS>, gather_grid(c, QUAL_WORDS), dim3(TABLE_GATHER_THREADS), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
-  { int r = stage_record(c, q, 1); if (r) return r; }
-  { int r = y_read_again(c); if (r) return r; }
-  q.enqueued = true;
-  q.n_streams = n;
-  return RFID_OK;
+  return table_end(c, q, n);
 }
 
 int rfid_batch_get_quality(rfid_ctx *c, rfid_read_quality *out, int64_t cap, int64_t *n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
-  rfid_ctx::Inventory &v = c->inv;
-  rfid_ctx::Tracks &t = c->trk;
-  rfid_ctx::Quality &q = c->qual;
-  if (!v.blk || !t.blk || !q.blk || !q.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_quality: no rfid_batch_quality behind this plan");
-  HIPCHK(c, hipSetDevice(c->device));
-  int n_entries = 0;
-  { int r = stage_fetch_head(c, "rfid_batch_get_quality", t.d_head, cap, n, &n_entries); if (r) return r; }
-  if (*n > 0) {
-    HIPCHK(c, hipMemcpyAsync(out, q.d_packed, sizeof(rfid_read_quality) * (size_t)*n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return RFID_OK;
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_aligned(c, c->qual, ST_QUALITY, c->qual.d_packed, sizeof(*out), out, cap, n);
 }
 
 int rfid_batch_get_window_quality(rfid_ctx *c, int stream, rfid_read_quality *out, int64_t cap, int64_t *n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
-  rfid_ctx::Quality &q = c->qual;
-  if (!q.blk || !q.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_quality: no rfid_batch_quality behind this plan");
-  return stage_fetch_rows(c, "rfid_batch_get_window_quality", q.d_nrows, q.d_table, sizeof(rfid_read_quality), q.rows, q.n_streams, stream, out, cap, n);
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->qual, ST_QUALITY, "rfid_batch_get_window_quality", sizeof(*out), stream, out, cap, n);
 }
 
 int rfid_batch_quality_ms(rfid_ctx *c, float *ms) {
@@ -1976,42 +2026,30 @@ int rfid_batch_quality_ms(rfid_ctx *c, float *ms) {
 // ---- repair stage: CRC-failed EPC frames recovered from their weakest decisions, behind the inventory of a pass (csrc/rfid_repair.hpp) ----
 int rfid_batch_plan_repair(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
-  if (!c->B_plan || !c->inv.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_repair: no plan with an inventory workspace (rfid_batch_plan_inventory)");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   rfid_ctx::Repair &p = c->rep;
-  free_repair(c);
   // EPC windows are every other window: ceil(wmax / 2) rows per trace, at most as many repaired ones
   const int rows = (c->wmax + 1) / 2, blocks = (rows + REP_ROWS - 1) / REP_ROWS;
   const size_t sz_t = sizeof(rfid_repair) * (size_t)rows * (size_t)c->B_plan, sz_b = sizeof(int) * (size_t)blocks * (size_t)c->B_plan;
-  const int r = stage_alloc(c, p, "rfid_batch_plan_repair: workspace allocation",
-                            {{(void **)&p.d_table, sz_t}, {(void **)&p.d_packed, sz_t}, {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan},
-                             {(void **)&p.d_counts, sz_b}, {(void **)&p.d_off, sz_b}, {(void **)&p.d_head, sizeof(int)}});
-  if (r) return r;
-  p.rows = rows; p.blocks = blocks;
-  return RFID_OK;
+  const int r = table_plan(c, p, ST_REPAIR, rows,
+                           {{&p.d_table, sz_t}, {(void **)&p.d_packed, sz_t}, {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan},
+                            {(void **)&p.d_counts, sz_b}, {(void **)&p.d_off, sz_b}, {(void **)&p.d_head, sizeof(int)}});
+  if (!r) p.blocks = blocks;
+  return r;
 }
 
 int rfid_batch_repair(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
   rfid_ctx::Inventory &v = c->inv;
   rfid_ctx::Repair &p = c->rep;
-  if (!c->B || !v.blk || !p.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_repair: no plan with a repair workspace (rfid_batch_plan_repair)");
-  if (!v.enqueued || c->current < rfid_ctx::CUR_INVENTORY) return fail(c, RFID_ERR_STATE, "rfid_batch_repair: no rfid_batch_inventory behind the last pass");
-  HIPCHK(c, hipSetDevice(c->device));
-  // as rfid_batch_quality: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
-  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
-  { int rj = join_tails(c); if (rj) return rj; }
-  const int n = v.n_streams;          // the traces the inventory covered
+  int n = 0;                          // the traces the inventory covered
   RepArgs a;
-  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->cur.d_wtab; a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats;
-  a.wmax = c->wmax; a.n_streams = n; a.rows = p.rows; a.blocks = p.blocks;
+  { int r = table_begin(c, p, ST_REPAIR, &n, &a.p); if (r) return r; }
+  a.rows = p.rows; a.blocks = p.blocks;
   a.ent = v.d_ent; a.ent_counts = v.d_counts; a.ent_over = v.d_over; a.max_tags = v.max_tags;
-  a.table = p.d_table; a.nrows = p.d_nrows; a.counts = p.d_counts;
+  a.table = p.table<rfid_repair>(); a.nrows = p.d_nrows; a.counts = p.d_counts;
   RepPackArgs g;
-  g.table = p.d_table; g.counts = p.d_counts; g.n_streams = n; g.rows = p.rows; g.blocks = p.blocks;
+  g.table = a.table; g.counts = p.d_counts; g.n_streams = n; g.rows = p.rows; g.blocks = p.blocks;
   g.offsets = p.d_off; g.head = p.d_head; g.packed = p.d_packed; g.cap = (int64_t)p.rows * c->B_plan;
-  { int r = stage_record(c, p, 0); if (r) return r; }
   // single-wave workgroups, each walking blocks of 64 rows (no LDS)
   const int64_t items = (int64_t)n * p.blocks;
   const dim3 grid = persistent_grid(items, (int64_t)c->n_cus * REP_WGS_PER_CU);
@@ -2021,11 +2059,7 @@ int rfid_batch_repair(rfid_ctx *c) {
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(repair_pack_kernel, grid, dim3(64), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
-  { int r = stage_record(c, p, 1); if (r) return r; }
-  { int r = y_read_again(c); if (r) return r; }
-  p.enqueued = true;
-  p.n_streams = n;
-  return RFID_OK;
+  return table_end(c, p, n);
 }
 
 int rfid_batch_get_repairs(rfid_ctx *c, rfid_repair *out, int64_t cap, int64_t *n) {
@@ -2046,10 +2080,8 @@ int rfid_batch_get_repairs(rfid_ctx *c, rfid_repair *out, int64_t cap, int64_t *
 }
 
 int rfid_batch_get_window_repairs(rfid_ctx *c, int stream, rfid_repair *out, int64_t cap, int64_t *n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
-  rfid_ctx::Repair &p = c->rep;
-  if (!p.blk || !p.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_repairs: no rfid_batch_repair behind this plan");
-  return stage_fetch_rows(c, "rfid_batch_get_window_repairs", p.d_nrows, p.d_table, sizeof(rfid_repair), p.rows, p.n_streams, stream, out, cap, n);
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->rep, ST_REPAIR, "rfid_batch_get_window_repairs", sizeof(*out), stream, out, cap, n);
 }
 
 int rfid_batch_repair_ms(rfid_ctx *c, float *ms) {
@@ -2059,69 +2091,37 @@ int rfid_batch_repair_ms(rfid_ctx *c, float *ms) {
 
 // the per-call form: one window in host memory through the batch kernel's device function (one launch, synchronising)
 int rfid_repair_window(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_result *res, rfid_repair *out) {
-  if (!c || !gated || !res || !out) return RFID_ERR_INVALID;
-  if (res->type != RFID_DECODE_EPC) return fail(c, RFID_ERR_INVALID, "rfid_repair_window: not the result of an EPC window");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t sz_w = up256(sizeof(float2) * (size_t)EPC_WIN), sz_r = up256(sizeof(rfid_decode_result));
-  { int r = grow(c, c->rep_one, sz_w + sz_r + sizeof(rfid_repair)); if (r) return r; }
-  char *b = (char *)c->rep_one.p;
-  HIPCHK(c, hipMemcpyAsync(b, gated, sizeof(float2) * (size_t)EPC_WIN, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(repair_one_kernel, dim3(1), dim3(64), 0, c->stream, (const float2 *)b, (const rfid_decode_result *)(b + sz_w),
-                     (rfid_repair *)(b + sz_w + sz_r));
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return RFID_OK;
+  return one_window(c, "rfid_repair_window", gated, res, out, [c](const float2 *g, const rfid_decode_result *r, rfid_repair *o) {
+    hipLaunchKernelGGL(repair_one_kernel, dim3(1), dim3(64), 0, c->stream, g, r, o);
+  });
 }
 
 // ---- slots stage: the second-order moments of every window, behind the statistics of a pass (csrc/rfid_slots.hpp) ----
 int rfid_batch_plan_slots(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
-  if (!c->B_plan) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_slots: no plan (rfid_batch_plan)");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   rfid_ctx::Slots &p = c->slt;
-  free_slots(c);
-  const int r = stage_alloc(c, p, "rfid_batch_plan_slots: workspace allocation",
-                            {{(void **)&p.d_table, sizeof(rfid_window_moments) * (size_t)c->wmax * (size_t)c->B_plan},
-                             {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan}});
-  if (r) return r;
-  p.rows = c->wmax;
-  return RFID_OK;
+  return table_plan(c, p, ST_SLOTS, c->wmax,
+                    {{&p.d_table, sizeof(rfid_window_moments) * (size_t)c->wmax * (size_t)c->B_plan},
+                     {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan}});
 }
 
 int rfid_batch_slots(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
   rfid_ctx::Slots &p = c->slt;
-  if (!c->B || !p.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_slots: no plan with a slots workspace (rfid_batch_plan_slots)");
-  if (c->current < rfid_ctx::CUR_STATS) return fail(c, RFID_ERR_STATE, "rfid_batch_slots: no pass with statistics yet");
-  HIPCHK(c, hipSetDevice(c->device));
-  // as rfid_batch_quality: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
-  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
-  { int rj = join_tails(c); if (rj) return rj; }
-  const int n = c->B;
+  int n = 0;
   MomArgs a;
-  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->cur.d_wtab; a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats;
-  a.wmax = c->wmax; a.n_streams = n; a.table = p.d_table; a.nrows = p.d_nrows;
-  { int r = stage_record(c, p, 0); if (r) return r; }
+  { int r = table_begin(c, p, ST_SLOTS, &n, &a.p); if (r) return r; }
+  a.table = p.table<rfid_window_moments>(); a.nrows = p.d_nrows;
   // single-wave workgroups, each walking packs of eight rows (15.7 KB of LDS each)
   const int64_t items = (int64_t)n * ((p.rows + MOM_PACK - 1) / MOM_PACK);
   hipLaunchKernelGGL(moments_kernel, persistent_grid(items, (int64_t)c->n_cus * MOM_WGS_PER_CU), dim3(64), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
-  { int r = stage_record(c, p, 1); if (r) return r; }
-  { int r = y_read_again(c); if (r) return r; }
-  p.enqueued = true;
-  p.n_streams = n;
-  return RFID_OK;
+  return table_end(c, p, n);
 }
 
 int rfid_batch_get_window_moments(rfid_ctx *c, int stream, rfid_window_moments *out, int64_t cap, int64_t *n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
-  rfid_ctx::Slots &p = c->slt;
-  if (!p.blk || !p.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_moments: no rfid_batch_slots behind this plan");
-  return stage_fetch_rows(c, "rfid_batch_get_window_moments", p.d_nrows, p.d_table, sizeof(rfid_window_moments), p.rows, p.n_streams, stream, out, cap, n,
-                          "windows");
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->slt, ST_SLOTS, "rfid_batch_get_window_moments", sizeof(*out), stream, out, cap, n);
 }
 
 int rfid_batch_slots_ms(rfid_ctx *c, float *ms) {
@@ -2135,8 +2135,8 @@ int rfid_window_moments_of(rfid_ctx *c, const rfid_cf32 *gated, int n_windows, r
   if (n_windows == 0) return RFID_OK;
   HIPCHK(c, hipSetDevice(c->device));
   const size_t sz_in = up256(sizeof(float2) * (size_t)MOM_N * (size_t)n_windows), sz_out = sizeof(rfid_window_moments) * (size_t)n_windows;
-  { int r = grow(c, c->mom_one, sz_in + sz_out); if (r) return r; }
-  char *b = (char *)c->mom_one.p;
+  { int r = grow(c, c->one, sz_in + sz_out); if (r) return r; }
+  char *b = (char *)c->one.p;
   HIPCHK(c, hipMemcpyAsync(b, gated, sizeof(float2) * (size_t)MOM_N * (size_t)n_windows, hipMemcpyHostToDevice, c->stream));
   const int64_t packs = ((int64_t)n_windows + MOM_PACK - 1) / MOM_PACK;
   hipLaunchKernelGGL(moments_of_kernel, persistent_grid(packs, (int64_t)c->n_cus * MOM_WGS_PER_CU), dim3(64), 0, c->stream,
@@ -2150,33 +2150,19 @@ int rfid_window_moments_of(rfid_ctx *c, const rfid_cf32 *gated, int n_windows, r
 // ---- commands stage: the reader's PIE command in front of every window, behind the statistics of a pass (csrc/rfid_commands.hpp) ----
 int rfid_batch_plan_commands(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
-  if (!c->B_plan) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_commands: no plan (rfid_batch_plan)");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   rfid_ctx::Commands &p = c->cmd;
-  free_commands(c);
-  const int r = stage_alloc(c, p, "rfid_batch_plan_commands: workspace allocation",
-                            {{(void **)&p.d_table, sizeof(rfid_command) * (size_t)c->wmax * (size_t)c->B_plan},
-                             {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan}});
-  if (r) return r;
-  p.rows = c->wmax;
-  return RFID_OK;
+  return table_plan(c, p, ST_COMMANDS, c->wmax,
+                    {{&p.d_table, sizeof(rfid_command) * (size_t)c->wmax * (size_t)c->B_plan},
+                     {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan}});
 }
 
 int rfid_batch_commands(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
   rfid_ctx::Commands &p = c->cmd;
-  if (!c->B || !p.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_commands: no plan with a commands workspace (rfid_batch_plan_commands)");
-  if (c->current < rfid_ctx::CUR_STATS) return fail(c, RFID_ERR_STATE, "rfid_batch_commands: no pass with statistics yet");
-  HIPCHK(c, hipSetDevice(c->device));
-  // as rfid_batch_slots: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
-  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
-  { int rj = join_tails(c); if (rj) return rj; }
-  const int n = c->B;
+  int n = 0;
   CmdArgs a;
-  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->cur.d_wtab; a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats;
-  a.wmax = c->wmax; a.n_streams = n; a.table = p.d_table; a.nrows = p.d_nrows;
-  { int r = stage_record(c, p, 0); if (r) return r; }
+  { int r = table_begin(c, p, ST_COMMANDS, &n, &a.p); if (r) return r; }
+  a.table = p.table<rfid_command>(); a.nrows = p.d_nrows;
   // single-wave workgroups, each walking blocks of rows (1 KB of LDS each): one row per block while the launch has a wave for
   // every row (a block's windows are worked on one after the other), up to sixteen in large batches (where most blocks lie behind
   // the cut-off and a block's window records come in one round trip)
@@ -2186,19 +2172,12 @@ int rfid_batch_commands(rfid_ctx *c) {
   const int64_t items = (int64_t)n * ((p.rows + a.rows_per - 1) / a.rows_per);
   hipLaunchKernelGGL(commands_kernel, persistent_grid(items, most), dim3(64), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
-  { int r = stage_record(c, p, 1); if (r) return r; }
-  { int r = y_read_again(c); if (r) return r; }
-  p.enqueued = true;
-  p.n_streams = n;
-  return RFID_OK;
+  return table_end(c, p, n);
 }
 
 int rfid_batch_get_window_commands(rfid_ctx *c, int stream, rfid_command *out, int64_t cap, int64_t *n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
-  rfid_ctx::Commands &p = c->cmd;
-  if (!p.blk || !p.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_commands: no rfid_batch_commands behind this plan");
-  return stage_fetch_rows(c, "rfid_batch_get_window_commands", p.d_nrows, p.d_table, sizeof(rfid_command), p.rows, p.n_streams, stream, out, cap, n,
-                          "windows");
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->cmd, ST_COMMANDS, "rfid_batch_get_window_commands", sizeof(*out), stream, out, cap, n);
 }
 
 int rfid_batch_commands_ms(rfid_ctx *c, float *ms) {
@@ -2213,8 +2192,8 @@ int rfid_commands_of(rfid_ctx *c, const rfid_cf32 *spans, const rfid_cf32 *level
   HIPCHK(c, hipSetDevice(c->device));
   const size_t sz_in = up256(sizeof(float2) * (size_t)CMD_SPAN * (size_t)n), sz_lv = up256(sizeof(float2) * (size_t)n),
                sz_out = sizeof(rfid_command) * (size_t)n;
-  { int r = grow(c, c->cmd_one, sz_in + sz_lv + sz_out); if (r) return r; }
-  char *b = (char *)c->cmd_one.p;
+  { int r = grow(c, c->one, sz_in + sz_lv + sz_out); if (r) return r; }
+  char *b = (char *)c->one.p;
   HIPCHK(c, hipMemcpyAsync(b, spans, sizeof(float2) * (size_t)CMD_SPAN * (size_t)n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(b + sz_in, levels, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
   // (the copies around it are what a call costs: two workgroups per compute unit will do)
@@ -2229,78 +2208,41 @@ int rfid_commands_of(rfid_ctx *c, const rfid_cf32 *spans, const rfid_cf32 *level
 // ---- fine stage: the data-aided channel estimate of every EPC window, behind the tracks of a pass (csrc/rfid_fine.hpp) ----
 int rfid_batch_plan_fine(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
-  if (!c->B_plan || !c->inv.blk || !c->trk.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_plan_fine: no plan with a tracks workspace (rfid_batch_plan_tracks)");
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
   rfid_ctx::Fine &f = c->fin;
-  free_fine(c);
   // EPC windows are every other window: ceil(wmax / 2) rows per trace, as many packed records as the tracks have reads
   const int rows = (c->wmax + 1) / 2;
-  const int r = stage_alloc(c, f, "rfid_batch_plan_fine: workspace allocation",
-                            {{(void **)&f.d_table, sizeof(rfid_read_fine) * (size_t)rows * (size_t)c->B_plan},
-                             {(void **)&f.d_packed, sizeof(rfid_read_fine) * (size_t)c->trk.cap},
-                             {(void **)&f.d_nrows, sizeof(int) * (size_t)c->B_plan}});
-  if (r) return r;
-  f.rows = rows;
-  return RFID_OK;
+  return table_plan(c, f, ST_FINE, rows,
+                    {{&f.d_table, sizeof(rfid_read_fine) * (size_t)rows * (size_t)c->B_plan},
+                     {(void **)&f.d_packed, sizeof(rfid_read_fine) * (size_t)c->trk.cap},
+                     {(void **)&f.d_nrows, sizeof(int) * (size_t)c->B_plan}});
 }
 
 int rfid_batch_fine(rfid_ctx *c) {
   if (!c) return RFID_ERR_INVALID;
-  rfid_ctx::Tracks &t = c->trk;
   rfid_ctx::Fine &f = c->fin;
-  if (!c->B || !c->inv.blk || !t.blk || !f.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_fine: no plan with a fine workspace (rfid_batch_plan_fine)");
-  if (!t.enqueued || c->current < rfid_ctx::CUR_TRACKS) return fail(c, RFID_ERR_STATE, "rfid_batch_fine: no rfid_batch_tracks behind the last pass");
-  HIPCHK(c, hipSetDevice(c->device));
-  // as rfid_batch_quality: c->d_* (the matched filter's output among them) name the last pass's result set; its tails ran on
-  // the second stream when two sets alternate, and the next pass's front end follows on the main stream, behind this
-  { int rj = join_tails(c); if (rj) return rj; }
-  const int n = c->inv.n_streams;     // the traces the inventory and the tracks covered
+  int n = 0;                          // the traces the inventory and the tracks covered
   FineArgs a;
-  a.y = c->y(); a.y_stride = c->y_stride; a.wtab = c->cur.d_wtab; a.res = c->cur.d_res; a.wcount = c->cur.d_wcount; a.stats = c->cur.d_stats;
-  a.wmax = c->wmax; a.n_streams = n; a.rows = f.rows; a.table = f.d_table; a.nrows = f.d_nrows;
-  FineGatherArgs g;
-  g.reads = t.d_reads; g.head = t.d_head; g.cap = t.cap; g.table = f.d_table; g.n_streams = n; g.rows = f.rows; g.out = f.d_packed;
-  { int r = stage_record(c, f, 0); if (r) return r; }
+  { int r = table_begin(c, f, ST_FINE, &n, &a.p); if (r) return r; }
+  a.rows = f.rows; a.table = f.table<rfid_read_fine>(); a.nrows = f.d_nrows;
+  const TableGatherArgs g = gather_args(c, f, f.d_packed, n);
   // single-wave workgroups, each walking packs of eight rows (13.8 KB of LDS each)
   const int64_t items = (int64_t)n * ((f.rows + FINE_PACK - 1) / FINE_PACK);
   const int64_t most = c->knobs.fine_wgs ? (int64_t)c->knobs.fine_wgs : (int64_t)c->n_cus * FINE_WGS_PER_CU;
   hipLaunchKernelGGL(fine_kernel, persistent_grid(items, most), dim3(64), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
-  const int64_t words = t.cap * FINE_WORDS, gmost = (int64_t)c->n_cus * 8;
-  int64_t gblocks = (words + FINE_GATHER_THREADS - 1) / FINE_GATHER_THREADS;
-  if (gblocks > gmost) gblocks = gmost;
-  if (gblocks < 1) gblocks = 1;
-  hipLaunchKernelGGL(fine_gather_kernel, dim3((unsigned)gblocks), dim3(FINE_GATHER_THREADS), 0, c->stream, g);
+  hipLaunchKernelGGL(table_gather_kernel<FINE_WORDS>, gather_grid(c, FINE_WORDS), dim3(TABLE_GATHER_THREADS), 0, c->stream, g);
   HIPCHK(c, hipGetLastError());
-  { int r = stage_record(c, f, 1); if (r) return r; }
-  { int r = y_read_again(c); if (r) return r; }
-  f.enqueued = true;
-  f.n_streams = n;
-  return RFID_OK;
+  return table_end(c, f, n);
 }
 
 int rfid_batch_get_fine(rfid_ctx *c, rfid_read_fine *out, int64_t cap, int64_t *n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
-  rfid_ctx::Inventory &v = c->inv;
-  rfid_ctx::Tracks &t = c->trk;
-  rfid_ctx::Fine &f = c->fin;
-  if (!v.blk || !t.blk || !f.blk || !f.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_fine: no rfid_batch_fine behind this plan");
-  HIPCHK(c, hipSetDevice(c->device));
-  int n_entries = 0;
-  { int r = stage_fetch_head(c, "rfid_batch_get_fine", t.d_head, cap, n, &n_entries); if (r) return r; }
-  if (*n > 0) {
-    HIPCHK(c, hipMemcpyAsync(out, f.d_packed, sizeof(rfid_read_fine) * (size_t)*n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-  }
-  return RFID_OK;
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_aligned(c, c->fin, ST_FINE, c->fin.d_packed, sizeof(*out), out, cap, n);
 }
 
 int rfid_batch_get_window_fine(rfid_ctx *c, int stream, rfid_read_fine *out, int64_t cap, int64_t *n) {
-  if (!c || !n || cap < 0 || (cap > 0 && !out)) return RFID_ERR_INVALID;
-  rfid_ctx::Fine &f = c->fin;
-  if (!f.blk || !f.enqueued) return fail(c, RFID_ERR_STATE, "rfid_batch_get_window_fine: no rfid_batch_fine behind this plan");
-  return stage_fetch_rows(c, "rfid_batch_get_window_fine", f.d_nrows, f.d_table, sizeof(rfid_read_fine), f.rows, f.n_streams, stream, out, cap, n);
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->fin, ST_FINE, "rfid_batch_get_window_fine", sizeof(*out), stream, out, cap, n);
 }
 
 int rfid_batch_fine_ms(rfid_ctx *c, float *ms) {
@@ -2310,20 +2252,9 @@ int rfid_batch_fine_ms(rfid_ctx *c, float *ms) {
 
 // the per-call form: one window in host memory through the batch kernel's device functions (one launch, synchronising)
 int rfid_fine_window(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_result *res, rfid_read_fine *out) {
-  if (!c || !gated || !res || !out) return RFID_ERR_INVALID;
-  if (res->type != RFID_DECODE_EPC) return fail(c, RFID_ERR_INVALID, "rfid_fine_window: not the result of an EPC window");
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t sz_w = up256(sizeof(float2) * (size_t)EPC_WIN), sz_r = up256(sizeof(rfid_decode_result));
-  { int r = grow(c, c->fin_one, sz_w + sz_r + sizeof(rfid_read_fine)); if (r) return r; }
-  char *b = (char *)c->fin_one.p;
-  HIPCHK(c, hipMemcpyAsync(b, gated, sizeof(float2) * (size_t)EPC_WIN, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(fine_one_kernel, dim3(1), dim3(64), 0, c->stream, (const float2 *)b, (const rfid_decode_result *)(b + sz_w),
-                     (rfid_read_fine *)(b + sz_w + sz_r));
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return RFID_OK;
+  return one_window(c, "rfid_fine_window", gated, res, out, [c](const float2 *g, const rfid_decode_result *r, rfid_read_fine *o) {
+    hipLaunchKernelGGL(fine_one_kernel, dim3(1), dim3(64), 0, c->stream, g, r, o);
+  });
 }
 
 }  // extern "C"

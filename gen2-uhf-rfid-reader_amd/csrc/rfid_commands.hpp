@@ -31,7 +31,7 @@
 // commands_of_kernel is the per-call twin: the same device functions over spans a caller holds.
 // Only primitives both device environments offer.
 #pragma once
-#include "rfid_inventory.hpp"
+#include "rfid_stage.hpp"
 
 namespace rfidk {
 
@@ -175,13 +175,7 @@ RFID_DEVICE void cmd_block(int *edges, int *rec, const float2 *base, int64_t row
 }
 
 struct CmdArgs {
-  const float2 *y;                  // the matched filter's output of the pass
-  int64_t y_stride;
-  const rfid_window *wtab;          // [n_streams][wmax]
-  const rfid_decode_result *res;    // [n_streams][wmax]
-  const int *wcount;                // [n_streams]
-  const rfid_stream_stats *stats;   // [n_streams]: n_windows_used of the same pass
-  int wmax, n_streams;
+  StagePass p;                      // what the pass left (rfid_stage.hpp)
   rfid_command *table;              // [n_streams][wmax]: the row of a window is its seq
   int *nrows;                       // [n_streams]: windows before the cut-off (n_windows_used)
   int rows_per;                     // rows per wave and step, 1..CMD_ROWS (the host's choice: 1 while the launch has a wave per row)
@@ -192,16 +186,16 @@ RFID_KERNEL(64) void commands_kernel(CmdArgs a) {
   RFID_SHARED int rec[CMD_BLOCK_WORDS];
   const int lane = wv::lane_id();
   const int R = a.rows_per;
-  const int blocks_per = (a.wmax + R - 1) / R;
-  const int64_t n_items = (int64_t)a.n_streams * blocks_per;
+  const int blocks_per = (a.p.wmax + R - 1) / R;
+  const int64_t n_items = (int64_t)a.p.n_streams * blocks_per;
   int *table_w = reinterpret_cast<int *>(a.table);
   for (int64_t it = (int64_t)blockIdx.x; it < n_items; it += (int64_t)gridDim.x) {
     const int s = (int)(it / blocks_per);
     const int r0 = (int)(it - (int64_t)s * blocks_per) * R;
-    const int nw = stage_windows(a.wcount, a.stats, a.wmax, s);
+    const int nw = stage_windows(a.p.wcount, a.p.stats, a.p.wmax, s);
     if (r0 == 0 && lane == 0) a.nrows[s] = nw;
-    const int rows = (a.wmax - r0 < R) ? (a.wmax - r0) : R;   // (the table's rows of this block)
-    int *out = table_w + ((int64_t)s * a.wmax + r0) * CMD_WORDS;
+    const int rows = (a.p.wmax - r0 < R) ? (a.p.wmax - r0) : R;   // (the table's rows of this block)
+    int *out = table_w + ((int64_t)s * a.p.wmax + r0) * CMD_WORDS;
     if (r0 >= nw) {                        // behind the cut-off
 #pragma unroll
       for (int k = lane; k < CMD_BLOCK_WORDS; k += 64)
@@ -212,13 +206,13 @@ RFID_KERNEL(64) void commands_kernel(CmdArgs a) {
     int a_l = 0, rn_l = 0;
     float dr_l = 0.0f, di_l = 0.0f;
     if (lane < n_on) {
-      const int64_t k = (int64_t)s * a.wmax + r0 + lane;
-      const rfid_window wd = a.wtab[k];
+      const int64_t k = (int64_t)s * a.p.wmax + r0 + lane;
+      const rfid_window wd = a.p.wtab[k];
       a_l = wd.start; dr_l = wd.dc_re; di_l = wd.dc_im;
       // the RN16 the window before decoded (results are read as words, as stage_fetch reads them: bits[0] is word 5)
-      if ((r0 + lane) & 1) rn_l = reinterpret_cast<const int *>(a.res + (k - 1))[5];
+      if ((r0 + lane) & 1) rn_l = reinterpret_cast<const int *>(a.p.res + (k - 1))[5];
     }
-    cmd_block<true>(edges, rec, a.y + (int64_t)s * a.y_stride, a.y_stride, a_l, dr_l, di_l, rn_l, s, r0, n_on, lane);
+    cmd_block<true>(edges, rec, a.p.y + (int64_t)s * a.p.y_stride, a.p.y_stride, a_l, dr_l, di_l, rn_l, s, r0, n_on, lane);
 #pragma unroll
     for (int k = lane; k < CMD_BLOCK_WORDS; k += 64)
       if (k < rows * CMD_WORDS) out[k] = rec[k];

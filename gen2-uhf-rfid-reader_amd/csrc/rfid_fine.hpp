@@ -10,7 +10,7 @@
 // The definition (include/rfid_mi355x.h, rfid_read_fine) is in binary32, one rounding per operation, every sum in order from
 // 0.0f: a record is a function of the input alone.  The kernel's shape is the quality stage's (csrc/rfid_quality.hpp):
 //   gather  a wave takes FINE_PACK = 8 EPC windows of one trace at a time (a persistent grid over (trace, pack of rows)); the
-//           quality stage's gather, two j per lane -- j = lane and lane + 64 -- the gathers of all eight windows in flight together.
+//           decoder's gather (epc_gather), two j per lane -- j = lane and lane + 64 -- the gathers of all eight windows in flight together.
 //   signs   the four words of frame bits are the same in every lane; the parity of bits 0..j is a masked population count.
 //   park    g dx, g dy and dx^2 + dy^2 go to LDS by (window, segment, component), 17 words apart: the 64 walkers -- one per
 //           (window, segment) -- start 51 words apart, in 64 different banks, and walk 16 terms of three rows each.
@@ -19,11 +19,11 @@
 // The cut-off is the inventory's and the tracks' (stage_windows).  Rows behind a trace's cut-off are zeroed, so the table's bytes
 // repeat from pass to pass.  Single-wave workgroups, nothing shared between them, no atomics: nothing depends on the order in
 // which they run.
-// fine_gather_kernel then copies the records of the CRC-verified reads into one array aligned with the tracks; fine_one_kernel
-// runs the same device functions on one window a caller holds.
+// table_gather_kernel<FINE_WORDS> (rfid_stage.hpp) then copies the records of the CRC-verified reads into one array aligned with
+// the tracks; fine_one_kernel runs the same device functions on one window a caller holds.
 // Only primitives both device environments offer.
 #pragma once
-#include "rfid_quality.hpp"
+#include "rfid_stage.hpp"
 
 namespace rfidk {
 
@@ -41,13 +41,7 @@ static_assert(FINE_SEGS * FINE_SEG_BITS == 128 && ((3 * FINE_ROW) & 1) == 1, "wa
 constexpr int FINE_W_STREAM = 0, FINE_W_SEQ = 1, FINE_W_START = 2, FINE_W_FLAGS = 3, FINE_W_SUM = 4, FINE_W_RESERVED = 7, FINE_W_SEG = 8;
 
 struct FineArgs {
-  const float2 *y;                  // the matched filter's output of the pass
-  int64_t y_stride;
-  const rfid_window *wtab;          // [n_streams][wmax]
-  const rfid_decode_result *res;    // [n_streams][wmax]
-  const int *wcount;                // [n_streams]
-  const rfid_stream_stats *stats;   // [n_streams]: n_windows_used of the same pass
-  int wmax, n_streams;
+  StagePass p;                      // what the pass left (rfid_stage.hpp)
   int rows;                         // ceil(wmax / 2): EPC windows have odd seq, the row of one is seq >> 1
   rfid_read_fine *table;            // [n_streams][rows]
   int *nrows;                       // [n_streams]: EPC windows before the cut-off (n_windows_used / 2)
@@ -72,17 +66,6 @@ RFID_DEVICE void fine_fetch(const rfid_decode_result *rs, FineWin &w) {
   w.b01 = (uint64_t)(uint32_t)b0 | ((uint64_t)(uint32_t)b1 << 32);
   w.b23 = (uint64_t)(uint32_t)b2 | ((uint64_t)(uint32_t)b3 << 32);
   w.crc_ok = crc_ok;
-}
-
-// the decoder's own gather (tag_decoder_impl.cc:171-190) of j = lane and lane + 64, as quality_kernel forms it: indices held
-// inside the window (not reached: they end at 1356)
-RFID_DEVICE void fine_gather(const FineWin &w, int lane, float2 &pa, float2 &qa, float2 &pb, float2 &qb) {
-  const float T = w.T, T2 = 2.0f * T, fidx = w.fidx;
-  const int j0 = lane, j1 = lane + 64;
-  pa = w.src[qual_clamp(wv::f2i((float)j0 * T2 + fidx))];
-  qa = w.src[qual_clamp(wv::f2i(((float)(j0 * 2) * T + T) + fidx))];
-  pb = w.src[qual_clamp(wv::f2i((float)j1 * T2 + fidx))];
-  qb = w.src[qual_clamp(wv::f2i(((float)(j1 * 2) * T + T) + fidx))];
 }
 
 // where term i of (window u, segment k, component c) lies
@@ -134,12 +117,12 @@ RFID_KERNEL(64) void fine_kernel(FineArgs a) {
   RFID_SHARED int rec[FINE_PACK * FINE_WORDS];
   const int lane = wv::lane_id();
   const int packs_per = (a.rows + FINE_PACK - 1) / FINE_PACK;
-  const int64_t n_items = (int64_t)a.n_streams * packs_per;
+  const int64_t n_items = (int64_t)a.p.n_streams * packs_per;
   int *table_w = reinterpret_cast<int *>(a.table);
   for (int64_t it = (int64_t)blockIdx.x; it < n_items; it += (int64_t)gridDim.x) {
     const int s = (int)(it / packs_per);
     const int r0 = (int)(it - (int64_t)s * packs_per) * FINE_PACK;
-    const int nw = stage_windows(a.wcount, a.stats, a.wmax, s);
+    const int nw = stage_windows(a.p.wcount, a.p.stats, a.p.wmax, s);
     const int nrows = nw >> 1;             // seq = 2 row + 1 < nw
     if (r0 == 0 && lane == 0) a.nrows[s] = nrows;
     int *out = table_w + ((int64_t)s * a.rows + r0) * FINE_WORDS + lane;     // (store q: 64 q words further on, rows r0 + 2 q, + 1)
@@ -155,15 +138,15 @@ RFID_KERNEL(64) void fine_kernel(FineArgs a) {
 #pragma unroll
     for (int u = 0; u < FINE_PACK; ++u) {
       const int row = (r0 + u < nrows) ? (r0 + u) : r0;      // (a row behind the cut-off: the pack's first, its terms unused)
-      const int64_t k = (int64_t)s * a.wmax + (2 * row + 1);
-      const rfid_window wd = a.wtab[k];
-      fine_fetch(a.res + k, w[u]);
-      w[u].src = a.y + (int64_t)s * a.y_stride + wd.start;
+      const int64_t k = (int64_t)s * a.p.wmax + (2 * row + 1);
+      const rfid_window wd = a.p.wtab[k];
+      fine_fetch(a.p.res + k, w[u]);
+      w[u].src = a.p.y + (int64_t)s * a.p.y_stride + wd.start;
       w[u].dcr = wd.dc_re; w[u].dci = wd.dc_im;
       w[u].start = wd.start;
     }
 #pragma unroll
-    for (int u = 0; u < FINE_PACK; ++u) fine_gather(w[u], lane, pa[u], qa[u], pb[u], qb[u]);
+    for (int u = 0; u < FINE_PACK; ++u) epc_gather(w[u].src, w[u].T, w[u].fidx, lane, pa[u], qa[u], pb[u], qb[u]);
 #pragma unroll
     for (int u = 0; u < FINE_PACK; ++u) {
       fine_park(term, u, w[u], pa[u], qa[u], pb[u], qb[u], lane);
@@ -185,34 +168,6 @@ RFID_KERNEL(64) void fine_kernel(FineArgs a) {
   }
 }
 
-// ---- the records of the CRC-verified reads, aligned with the tracks: fine[i] belongs to reads[i] ------------------------------
-struct FineGatherArgs {
-  const rfid_tag_read *reads;       // the tracks of the same pass
-  const int *head;                  // [0] reads in all
-  int64_t cap;
-  const rfid_read_fine *table;      // [n_streams][rows]
-  int n_streams, rows;
-  rfid_read_fine *out;              // [cap]
-};
-
-constexpr int FINE_GATHER_THREADS = 256;
-
-RFID_KERNEL(FINE_GATHER_THREADS) void fine_gather_kernel(FineGatherArgs a) {
-  int64_t total = a.head[0];
-  if (total > a.cap) total = a.cap;
-  const int *table_w = reinterpret_cast<const int *>(a.table);
-  int *out_w = reinterpret_cast<int *>(a.out);
-  const int64_t n = total * FINE_WORDS, step = (int64_t)gridDim.x * FINE_GATHER_THREADS;
-  for (int64_t t = (int64_t)blockIdx.x * FINE_GATHER_THREADS + (int64_t)threadIdx.x; t < n; t += step) {   // a word per thread
-    const int64_t i = t / FINE_WORDS;
-    const int word = (int)(t - i * FINE_WORDS);
-    const int s = a.reads[i].stream, row = a.reads[i].seq >> 1;
-    int v = 0;
-    if (s >= 0 && s < a.n_streams && row >= 0 && row < a.rows) v = table_w[((int64_t)s * a.rows + row) * FINE_WORDS + word];
-    out_w[t] = v;
-  }
-}
-
 // ---- one caller-supplied window (rfid_fine_window): the same gather, signs and sums, one wave -----------------------------------
 RFID_KERNEL(64) void fine_one_kernel(const float2 *gated, const rfid_decode_result *res, rfid_read_fine *out) {
   RFID_SHARED float term[FINE_SEGS * 3 * FINE_ROW];
@@ -222,7 +177,7 @@ RFID_KERNEL(64) void fine_one_kernel(const float2 *gated, const rfid_decode_resu
   fine_fetch(res, w);
   w.src = gated; w.dcr = 0.0f; w.dci = 0.0f; w.start = 0;      // (DC-free already)
   float2 pa, qa, pb, qb;
-  fine_gather(w, lane, pa, qa, pb, qb);
+  epc_gather(w.src, w.T, w.fidx, lane, pa, qa, pb, qb);
   fine_park(term, 0, w, pa, qa, pb, qb, lane);
   if (lane < FINE_W_SEG) rec[lane] = (lane == FINE_W_FLAGS) ? (w.crc_ok & 1) : 0;
   wv::wave_sync();

@@ -27,12 +27,11 @@
 // Counts, last read and the largest |h|^2 are accumulated by the reads that resolve in a round and thrown away if the
 // round turns out not to be the last; the strongest read's seq needs the maximum first and takes one more walk.
 //
-// Also here, because the tracks and the quality stage (rfid_tracks.hpp, rfid_quality.hpp, which include this file) decide
-// the same things: stage_windows (which windows of a trace count in a pass), stage_fetch (how a result record is read and
-// which records are reads), inv_hash / inv_walk (how a frame is looked up in the table) and scan_share / scan_partials
-// (the one-workgroup offsets scan).  How a table is BUILT is not shared: reads claim slots here, entries in the tracks.
+// Also here, because the tracks stage (rfid_tracks.hpp, which includes this file) decides the same thing: inv_hash / inv_walk
+// (how a frame is looked up in the table).  How a table is BUILT is not shared: reads claim slots here, entries in the tracks.
+// What all stages share -- stage_windows, stage_fetch, scan_share / scan_partials -- is in rfid_stage.hpp.
 #pragma once
-#include "rfid_kernels.hpp"
+#include "rfid_stage.hpp"
 
 namespace rfidk {
 
@@ -51,43 +50,6 @@ struct InvArgs {
 constexpr int INV_EMPTY = 0x7fffffff;
 constexpr int INV_MAX_WAVES = 16;
 constexpr int INV_UNROLL = 4;       // 64-window batches of loads in flight per wave
-
-// the windows of trace s that count in this pass: those the gate opened, before the TERMINATED cut-off (shared by the
-// inventory, tracks and quality kernels)
-RFID_DEVICE int stage_windows(const int *wcount, const rfid_stream_stats *stats, int wmax, int s) {
-  int nw = wcount[s];
-  const int used = stats[s].n_windows_used;
-  if (used < nw) nw = used;
-  if (nw > wmax) nw = wmax;
-  return (nw < 0) ? 0 : nw;
-}
-
-// one result record as the stages read it (shared by the inventory and the tracks kernels)
-struct StageRead {
-  uint32_t f[4];
-  int h_re, h_im, T, index;   // (bit patterns)
-  bool on;                    // an EPC window with a verified CRC
-};
-
-RFID_DEVICE StageRead stage_fetch(const rfid_decode_result *rs, int k, int k_end) {
-  StageRead q;
-  q.f[0] = q.f[1] = q.f[2] = q.f[3] = 0u; q.h_re = q.h_im = q.T = q.index = 0; q.on = false;
-  if (k < k_end) {
-    // the whole 48-byte record in three 16-byte loads, none of them waiting for another (rows are 16-byte aligned)
-    static_assert(sizeof(rfid_decode_result) == 48, "rfid_decode_result is read as 12 words");
-    const int *p = reinterpret_cast<const int *>(rs + k);
-    int w[12];
-    wv::load4_i32(p, w[0], w[1], w[2], w[3]);        // type, index, h_re, h_im
-    wv::load4_i32(p + 4, w[4], w[5], w[6], w[7]);    // T, bits[0..2]
-    wv::load4_i32(p + 8, w[8], w[9], w[10], w[11]);  // bits[3], n_bits, crc_ok, tag_id
-    if (w[0] == RFID_DECODE_EPC && w[10] == 1) {
-      q.on = true;
-      q.f[0] = (uint32_t)w[5]; q.f[1] = (uint32_t)w[6]; q.f[2] = (uint32_t)w[7]; q.f[3] = (uint32_t)w[8];
-      q.index = w[1]; q.h_re = w[2]; q.h_im = w[3]; q.T = w[4];
-    }
-  }
-  return q;
-}
 
 // int pattern of h_re*h_re + h_im*h_im (non-negative: ordered like the float)
 RFID_DEVICE int inv_norm(const StageRead &q) {
@@ -233,34 +195,6 @@ struct InvPackArgs {
   int *head;                    // [0] entries in all, [1] the first trace that overflowed (INV_EMPTY: none)
   rfid_tag_entry *packed;       // [sum of counts]
 };
-
-// The one-workgroup offsets scan over per-trace amounts (inventory_offsets_kernel, tracks_offsets_kernel): every thread
-// sums the amounts of a contiguous share of the traces, thread 0 scans the partial sums serially (INV_SCAN_THREADS at
-// most), every thread then walks its share again from the base it is handed.
-constexpr int INV_SCAN_THREADS = 1024;
-
-struct ScanShare { int b0, b1; };     // this thread's traces: [b0, b1)
-RFID_DEVICE ScanShare scan_share(int n_streams, int tid, int nthr) {
-  const int per = (n_streams + nthr - 1) / nthr;
-  ScanShare sh;
-  sh.b0 = tid * per;
-  sh.b1 = (sh.b0 + per < n_streams) ? (sh.b0 + per) : n_streams;
-  return sh;
-}
-
-// `sum`: what this thread's share holds.  -> what the shares of the threads before it hold; `total` (thread 0 only):
-// what all hold.  Two workgroup barriers: what the threads wrote to LDS before the call is visible behind it.
-RFID_DEVICE int scan_partials(int *part, int tid, int nthr, int sum, int &total) {
-  part[tid] = sum;
-  wv::block_sync();
-  if (tid == 0) {
-    int run = 0;
-    for (int t = 0; t < nthr; ++t) { const int v = part[t]; part[t] = run; run += v; }
-    total = run;
-  }
-  wv::block_sync();
-  return part[tid];
-}
 
 RFID_KERNEL(INV_SCAN_THREADS) void inventory_offsets_kernel(InvPackArgs a) {
   RFID_SHARED int part[INV_SCAN_THREADS];

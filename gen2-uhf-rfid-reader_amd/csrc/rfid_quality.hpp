@@ -20,10 +20,11 @@
 // The cut-off is the inventory's and the tracks' (stage_windows).  Rows behind a trace's cut-off are zeroed, so the table's
 // bytes repeat from pass to pass.  Single-wave workgroups, nothing shared between them, no atomics: nothing depends on the
 // order in which they run.
-// quality_gather_kernel then copies the records of the CRC-verified reads into one array aligned with the tracks.
+// table_gather_kernel<QUAL_WORDS> (rfid_stage.hpp) then copies the records of the CRC-verified reads into one array aligned
+// with the tracks.
 // Only primitives both device environments offer.
 #pragma once
-#include "rfid_tracks.hpp"
+#include "rfid_stage.hpp"
 
 namespace rfidk {
 
@@ -35,13 +36,7 @@ static_assert(sizeof(rfid_read_quality) == 32 && QUAL_PACK * QUAL_WORDS == 64, "
 static_assert(QUAL_PACK * 3 <= 32, "one bank per walker");
 
 struct QualArgs {
-  const float2 *y;                  // the matched filter's output of the pass
-  int64_t y_stride;
-  const rfid_window *wtab;          // [n_streams][wmax]
-  const rfid_decode_result *res;    // [n_streams][wmax]
-  const int *wcount;                // [n_streams]
-  const rfid_stream_stats *stats;   // [n_streams]: n_windows_used of the same pass
-  int wmax, n_streams;
+  StagePass p;                      // what the pass left (rfid_stage.hpp)
   int rows;                         // ceil(wmax / 2): EPC windows have odd seq, the row of one is seq >> 1
   rfid_read_quality *table;         // [n_streams][rows]
   int *nrows;                       // [n_streams]: EPC windows before the cut-off (n_windows_used / 2)
@@ -53,19 +48,17 @@ struct QualWin {     // what a window's gathers need (the same in every lane)
   int crc_ok;
 };
 
-RFID_DEVICE int qual_clamp(int i) { return (i < 0) ? 0 : ((i > EPC_WIN - 1) ? (EPC_WIN - 1) : i); }
-
 RFID_KERNEL(64) void quality_kernel(QualArgs a) {
   RFID_SHARED float term[QUAL_PACK * 3 * QUAL_TERM_STRIDE];
   RFID_SHARED int rec[QUAL_PACK * QUAL_WORDS];
   const int lane = wv::lane_id();
   const int packs_per = (a.rows + QUAL_PACK - 1) / QUAL_PACK;
-  const int64_t n_items = (int64_t)a.n_streams * packs_per;
+  const int64_t n_items = (int64_t)a.p.n_streams * packs_per;
   int *table_w = reinterpret_cast<int *>(a.table);
   for (int64_t it = (int64_t)blockIdx.x; it < n_items; it += (int64_t)gridDim.x) {
     const int s = (int)(it / packs_per);
     const int r0 = (int)(it - (int64_t)s * packs_per) * QUAL_PACK;
-    const int nw = stage_windows(a.wcount, a.stats, a.wmax, s);
+    const int nw = stage_windows(a.p.wcount, a.p.stats, a.p.wmax, s);
     const int nrows = nw >> 1;             // seq = 2 row + 1 < nw
     if (r0 == 0 && lane == 0) a.nrows[s] = nrows;
     const int my_row = r0 + (lane >> 3);   // (the record this lane stores a word of)
@@ -80,28 +73,20 @@ RFID_KERNEL(64) void quality_kernel(QualArgs a) {
 #pragma unroll
     for (int u = 0; u < QUAL_PACK; ++u) {
       const int row = (r0 + u < nrows) ? (r0 + u) : r0;      // (a row behind the cut-off: the pack's first, its terms unused)
-      const int64_t k = (int64_t)s * a.wmax + (2 * row + 1);
-      const rfid_window wd = a.wtab[k];
-      const int *p = reinterpret_cast<const int *>(a.res + k);
+      const int64_t k = (int64_t)s * a.p.wmax + (2 * row + 1);
+      const rfid_window wd = a.p.wtab[k];
+      const int *p = reinterpret_cast<const int *>(a.p.res + k);
       int t0, t1, t2, t3, t4, d0, d1, d2;
       wv::load4_i32(p, t0, t1, t2, t3);                      // type, index, h_re, h_im
       wv::load4_i32(p + 4, t4, d0, d1, d2);                  // T, bits[0..2]
       w[u].crc_ok = p[10];
-      w[u].src = a.y + (int64_t)s * a.y_stride + wd.start;
+      w[u].src = a.p.y + (int64_t)s * a.p.y_stride + wd.start;
       w[u].dcr = wd.dc_re; w[u].dci = wd.dc_im;
       w[u].h_re = wv::u2f((uint32_t)t2); w[u].h_im = wv::u2f((uint32_t)t3); w[u].T = wv::u2f((uint32_t)t4);
       w[u].fidx = (float)t1;
     }
 #pragma unroll
-    for (int u = 0; u < QUAL_PACK; ++u) {
-      // the decoder's own gather (tag_decoder_impl.cc:171-190), indices held inside the window (not reached: they end at 1356)
-      const float T = w[u].T, T2 = 2.0f * T, fidx = w[u].fidx;
-      const int j0 = lane, j1 = lane + 64;
-      pa[u] = w[u].src[qual_clamp(wv::f2i((float)j0 * T2 + fidx))];
-      qa[u] = w[u].src[qual_clamp(wv::f2i(((float)(j0 * 2) * T + T) + fidx))];
-      pb[u] = w[u].src[qual_clamp(wv::f2i((float)j1 * T2 + fidx))];
-      qb[u] = w[u].src[qual_clamp(wv::f2i(((float)(j1 * 2) * T + T) + fidx))];
-    }
+    for (int u = 0; u < QUAL_PACK; ++u) epc_gather(w[u].src, w[u].T, w[u].fidx, lane, pa[u], qa[u], pb[u], qb[u]);
     // ---- terms, minimum ----
 #pragma unroll
     for (int u = 0; u < QUAL_PACK; ++u) {
@@ -144,34 +129,6 @@ RFID_KERNEL(64) void quality_kernel(QualArgs a) {
     wv::wave_sync();
     if (my_row < a.rows) *out = rec[lane];
     wv::wave_sync();   // (the next pack overwrites both areas)
-  }
-}
-
-// ---- the records of the CRC-verified reads, aligned with the tracks: quality[i] belongs to reads[i] ---------------------
-struct QualGatherArgs {
-  const rfid_tag_read *reads;       // the tracks of the same pass
-  const int *head;                  // [0] reads in all
-  int64_t cap;
-  const rfid_read_quality *table;   // [n_streams][rows]
-  int n_streams, rows;
-  rfid_read_quality *out;           // [cap]
-};
-
-constexpr int QUAL_GATHER_THREADS = 256;
-
-RFID_KERNEL(QUAL_GATHER_THREADS) void quality_gather_kernel(QualGatherArgs a) {
-  int64_t total = a.head[0];
-  if (total > a.cap) total = a.cap;
-  const int *table_w = reinterpret_cast<const int *>(a.table);
-  int *out_w = reinterpret_cast<int *>(a.out);
-  const int64_t n = total * QUAL_WORDS, step = (int64_t)gridDim.x * QUAL_GATHER_THREADS;
-  for (int64_t t = (int64_t)blockIdx.x * QUAL_GATHER_THREADS + (int64_t)threadIdx.x; t < n; t += step) {   // a word per thread
-    const int64_t i = t / QUAL_WORDS;
-    const int word = (int)(t - i * QUAL_WORDS);
-    const int s = a.reads[i].stream, row = a.reads[i].seq >> 1;
-    int v = 0;
-    if (s >= 0 && s < a.n_streams && row >= 0 && row < a.rows) v = table_w[((int64_t)s * a.rows + row) * QUAL_WORDS + word];
-    out_w[t] = v;
   }
 }
 

@@ -34,7 +34,7 @@
 //                   ballot: ordered by (stream, seq), every place computed.
 // Nothing is shared between workgroups, no atomics.  Only primitives both device environments offer.
 #pragma once
-#include "rfid_quality.hpp"
+#include "rfid_stage.hpp"
 
 namespace rfidk {
 
@@ -155,15 +155,13 @@ RFID_DEVICE RepairFound repair_search(const RepairCols &t, float a0, float a1, u
   return r;
 }
 
-// |r_j| of j = lane and lane + 64 of one window: the decoder's own gather and decision value, as quality_kernel forms them
+// |r_j| of j = lane and lane + 64 of one window: the decoder's own gather (epc_gather) and the decision value as quality_kernel
+// forms it
 RFID_DEVICE void repair_gather(const float2 *src, float dcr, float dci, float h_re, float h_im, float T, float fidx, int lane,
                                float &a0, float &a1) {
-  const float T2 = 2.0f * T, nhim = -h_im;
-  const int j0 = lane, j1 = lane + 64;
-  const float2 pa = src[qual_clamp(wv::f2i((float)j0 * T2 + fidx))];
-  const float2 qa = src[qual_clamp(wv::f2i(((float)(j0 * 2) * T + T) + fidx))];
-  const float2 pb = src[qual_clamp(wv::f2i((float)j1 * T2 + fidx))];
-  const float2 qb = src[qual_clamp(wv::f2i(((float)(j1 * 2) * T + T) + fidx))];
+  const float nhim = -h_im;
+  float2 pa, qa, pb, qb;
+  epc_gather(src, T, fidx, lane, pa, qa, pb, qb);
   const float dx0 = (pa.x - dcr) - (qa.x - dcr), dy0 = (pa.y - dci) - (qa.y - dci);
   const float dx1 = (pb.x - dcr) - (qb.x - dcr), dy1 = (pb.y - dci) - (qb.y - dci);
   a0 = __builtin_fabsf(dx0 * h_re - dy0 * nhim);
@@ -215,13 +213,7 @@ RFID_DEVICE RepairFound repair_search_win(const RepairCols &t, const RepairWin &
 }
 
 struct RepArgs {
-  const float2 *y;                  // the matched filter's output of the pass
-  int64_t y_stride;
-  const rfid_window *wtab;          // [n_streams][wmax]
-  const rfid_decode_result *res;    // [n_streams][wmax]
-  const int *wcount;                // [n_streams]
-  const rfid_stream_stats *stats;   // [n_streams]: n_windows_used of the same pass
-  int wmax, n_streams;
+  StagePass p;                      // what the pass left (rfid_stage.hpp)
   int rows;                         // ceil(wmax / 2): the row of an EPC window is seq >> 1
   int blocks;                       // ceil(rows / REP_ROWS)
   const rfid_tag_entry *ent;        // [n_streams][max_tags]: the inventory of the same pass
@@ -236,11 +228,11 @@ struct RepArgs {
 RFID_KERNEL(64) void repair_kernel(RepArgs a) {
   const int lane = wv::lane_id();
   const RepairCols cols = repair_cols(lane);
-  const int64_t n_items = (int64_t)a.n_streams * a.blocks;
+  const int64_t n_items = (int64_t)a.p.n_streams * a.blocks;
   for (int64_t it = (int64_t)blockIdx.x; it < n_items; it += (int64_t)gridDim.x) {
     const int s = (int)(it / a.blocks);
     const int r0 = (int)(it - (int64_t)s * a.blocks) * REP_ROWS;
-    const int nw = stage_windows(a.wcount, a.stats, a.wmax, s);
+    const int nw = stage_windows(a.p.wcount, a.p.stats, a.p.wmax, s);
     const int nrows = nw >> 1;             // seq = 2 row + 1 < nw
     if (r0 == 0 && lane == 0) a.nrows[s] = nrows;
     const int my_row = r0 + lane;
@@ -256,7 +248,7 @@ RFID_KERNEL(64) void repair_kernel(RepArgs a) {
       RepairWin w;
       w.start = w.dcr = w.dci = w.type = w.index = w.h_re = w.h_im = w.T = w.crc_ok = 0;
       w.b[0] = w.b[1] = w.b[2] = w.b[3] = 0;
-      if (on) w = repair_fetch(a.wtab + ((int64_t)s * a.wmax + k), a.res + ((int64_t)s * a.wmax + k));
+      if (on) w = repair_fetch(a.p.wtab + ((int64_t)s * a.p.wmax + k), a.p.res + ((int64_t)s * a.p.wmax + k));
       const bool ok = w.type == RFID_DECODE_EPC && w.crc_ok == 1;      // (a read, as stage_fetch has it)
       const int over = a.ent_over[s] ? 2 : 0;
       const int E = over ? 0 : a.ent_counts[s];
@@ -270,7 +262,7 @@ RFID_KERNEL(64) void repair_kernel(RepArgs a) {
         rec.flips = -1; rec.entry = -1;
       }
       // ---- the failed rows of the block, one after the other; the gathers of the next one are in flight during a search ----
-      const float2 *y = a.y + (int64_t)s * a.y_stride;
+      const float2 *y = a.p.y + (int64_t)s * a.p.y_stride;
       uint64_t todo = wv::ballot(on && !ok);
       RepairWin u = w;
       float a0 = 0.0f, a1 = 0.0f;

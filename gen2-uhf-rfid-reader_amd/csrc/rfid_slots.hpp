@@ -23,7 +23,7 @@
 // moments_of_kernel is the per-call twin: the same device function over gated samples a caller holds (dc = 0).
 // Only primitives both device environments offer.
 #pragma once
-#include "rfid_inventory.hpp"
+#include "rfid_stage.hpp"
 
 namespace rfidk {
 
@@ -86,13 +86,7 @@ RFID_DEVICE void moments_pack(float2 *xy, int *rec, const MomWin (&w)[MOM_PACK],
 }
 
 struct MomArgs {
-  const float2 *y;                  // the matched filter's output of the pass
-  int64_t y_stride;
-  const rfid_window *wtab;          // [n_streams][wmax]
-  const rfid_decode_result *res;    // [n_streams][wmax]
-  const int *wcount;                // [n_streams]
-  const rfid_stream_stats *stats;   // [n_streams]: n_windows_used of the same pass
-  int wmax, n_streams;
+  StagePass p;                      // what the pass left (rfid_stage.hpp)
   rfid_window_moments *table;       // [n_streams][wmax]: the row of a window is its seq
   int *nrows;                       // [n_streams]: windows before the cut-off (n_windows_used)
 };
@@ -101,35 +95,35 @@ RFID_KERNEL(64) void moments_kernel(MomArgs a) {
   RFID_SHARED float2 xy[MOM_PACK * MOM_STRIDE];
   RFID_SHARED int rec[MOM_PACK * MOM_WORDS];
   const int lane = wv::lane_id();
-  const int packs_per = (a.wmax + MOM_PACK - 1) / MOM_PACK;
-  const int64_t n_items = (int64_t)a.n_streams * packs_per;
+  const int packs_per = (a.p.wmax + MOM_PACK - 1) / MOM_PACK;
+  const int64_t n_items = (int64_t)a.p.n_streams * packs_per;
   int *table_w = reinterpret_cast<int *>(a.table);
   for (int64_t it = (int64_t)blockIdx.x; it < n_items; it += (int64_t)gridDim.x) {
     const int s = (int)(it / packs_per);
     const int r0 = (int)(it - (int64_t)s * packs_per) * MOM_PACK;
-    const int nw = stage_windows(a.wcount, a.stats, a.wmax, s);
+    const int nw = stage_windows(a.p.wcount, a.p.stats, a.p.wmax, s);
     if (r0 == 0 && lane == 0) a.nrows[s] = nw;
     const int my_row = r0 + (lane >> 3);   // (the record this lane stores a word of)
-    int *out = table_w + ((int64_t)s * a.wmax + my_row) * MOM_WORDS + (lane & 7);
+    int *out = table_w + ((int64_t)s * a.p.wmax + my_row) * MOM_WORDS + (lane & 7);
     if (r0 >= nw) {                        // behind the cut-off
-      if (my_row < a.wmax) *out = 0;
+      if (my_row < a.p.wmax) *out = 0;
       continue;
     }
     MomWin w[MOM_PACK];
 #pragma unroll
     for (int u = 0; u < MOM_PACK; ++u) {
       const int row = (r0 + u < nw) ? (r0 + u) : r0;         // (a row behind the cut-off: the pack's first, its sums unused)
-      const int64_t k = (int64_t)s * a.wmax + row;
-      const rfid_window wd = a.wtab[k];
-      const int crc_ok = reinterpret_cast<const int *>(a.res + k)[10];
-      w[u].src = a.y + (int64_t)s * a.y_stride + wd.start;
+      const int64_t k = (int64_t)s * a.p.wmax + row;
+      const rfid_window wd = a.p.wtab[k];
+      const int crc_ok = reinterpret_cast<const int *>(a.p.res + k)[10];
+      w[u].src = a.p.y + (int64_t)s * a.p.y_stride + wd.start;
       w[u].dcr = wd.dc_re; w[u].dci = wd.dc_im;
       w[u].stream = s; w[u].seq = row;
       w[u].flags = (row & 1) ? (2 | (crc_ok & 1)) : 0;       // (type = seq & 1)
     }
     const int n_on = (nw - r0 < MOM_PACK) ? (nw - r0) : MOM_PACK;
     moments_pack(xy, rec, w, n_on, lane);
-    if (my_row < a.wmax) *out = rec[lane];
+    if (my_row < a.p.wmax) *out = rec[lane];
     wv::wave_sync();   // (the next pack overwrites both areas)
   }
 }

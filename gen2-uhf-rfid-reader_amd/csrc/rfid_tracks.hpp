@@ -20,7 +20,7 @@
 //   pass 2  every wave walks its range in batches of 64 windows, in order.  Inside a batch the lanes that hold the same
 //           entry are found with ballot; a lane's rank is the number of lower lanes among them, the lowest of them
 //           moves the cursor on by their number (an LDS atomic whose old value readlane hands to the others).
-// Which windows count (stage_windows) and how a result record is read (stage_fetch) are the inventory's too.
+// Which windows count (stage_windows) and how a result record is read (stage_fetch) are every stage's (rfid_stage.hpp).
 // Only primitives both device environments offer, workgroup barriers only, nothing shared between workgroups.
 #pragma once
 #include "rfid_inventory.hpp"

@@ -337,6 +337,23 @@ class Context:
         self._chk(get_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
+    def _window_rows(self, get, dtype, stream: int, extra: int) -> np.ndarray:
+        """One trace's rows of a window-table stage (rfid_batch_get_window_*): those before the cut-off plus up to `extra`
+        of the zeroed ones behind them."""
+        return self._sized_fetch(get, dtype, head=(int(stream),), extra=max(int(extra), 0))
+
+    def _one_window(self, call, dtype, gated, result) -> np.ndarray:
+        """The per-call form of an EPC-window stage (rfid_repair_window, rfid_fine_window): one window's gated samples and
+        its result record in, one record of `dtype` out."""
+        gated = np.ascontiguousarray(gated, dtype=np.complex64)
+        if len(gated) != 1370:
+            raise ValueError("an EPC window has 1370 samples")
+        res = np.zeros(1, dtype=capi.RESULT_DTYPE)
+        res[0] = result
+        out = np.zeros(1, dtype=dtype)
+        self._chk(call(self._h, gated.ctypes.data, res.ctypes.data, out.ctypes.data))
+        return out[0]
+
     def batch_plan_inventory(self, max_tags: int) -> None:
         """Reserves the inventory workspace of the current plan: up to max_tags distinct EPC frames per trace."""
         self._chk(self._lib.rfid_batch_plan_inventory(self._h, int(max_tags)))
@@ -414,8 +431,7 @@ class Context:
         """Debug tap (synchronises): the records of EVERY EPC window of one trace before the cut-off, in seq order, failed
         ones included (n_windows_used // 2 of them), of the last batch_quality_enqueue.  extra > 0: up to that many of the
         table's rows behind them as well (zeroed by the stage)."""
-        return self._sized_fetch(self._lib.rfid_batch_get_window_quality, capi.QUALITY_DTYPE, head=(int(stream),),
-                                 extra=max(int(extra), 0))
+        return self._window_rows(self._lib.rfid_batch_get_window_quality, capi.QUALITY_DTYPE, stream, extra)
 
     def batch_quality_ms(self) -> float:
         return self._stage_ms(self._lib.rfid_batch_quality_ms)
@@ -445,8 +461,7 @@ class Context:
         """One trace's row of the repair table (synchronises): the record of EVERY EPC window before the cut-off, in seq
         order (n_windows_used // 2 of them), of the last batch_repair_enqueue.  extra > 0: up to that many of the table's
         rows behind them as well (zeroed by the stage)."""
-        return self._sized_fetch(self._lib.rfid_batch_get_window_repairs, capi.REPAIR_DTYPE, head=(int(stream),),
-                                 extra=max(int(extra), 0))
+        return self._window_rows(self._lib.rfid_batch_get_window_repairs, capi.REPAIR_DTYPE, stream, extra)
 
     def batch_repair_ms(self) -> float:
         return self._stage_ms(self._lib.rfid_batch_repair_ms)
@@ -454,14 +469,7 @@ class Context:
     def repair_window(self, gated, result) -> np.ndarray:
         """The repair search for ONE EPC window in host memory (rfid_repair_window): gated = its 1370 gated, DC-free
         samples, result = its capi.RESULT_DTYPE record (what decoder_work returned).  -> one capi.REPAIR_DTYPE record."""
-        gated = np.ascontiguousarray(gated, dtype=np.complex64)
-        if len(gated) != 1370:
-            raise ValueError("an EPC window has 1370 samples")
-        res = np.zeros(1, dtype=capi.RESULT_DTYPE)
-        res[0] = result
-        out = np.zeros(1, dtype=capi.REPAIR_DTYPE)
-        self._chk(self._lib.rfid_repair_window(self._h, gated.ctypes.data, res.ctypes.data, out.ctypes.data))
-        return out[0]
+        return self._one_window(self._lib.rfid_repair_window, capi.REPAIR_DTYPE, gated, result)
 
     def batch_plan_slots(self) -> None:
         """Reserves the slots workspace of the current plan (a new plan drops it; it needs none of the other workspaces)."""
@@ -477,8 +485,7 @@ class Context:
         cut-off, RN16 and EPC alike, in seq order (n_windows_used of them), of the last batch_slots_enqueue.  extra > 0: up
         to that many of the table's rows behind them as well (zeroed by the stage).  rfid.batch.classify_slots turns a row
         into one record per slot."""
-        return self._sized_fetch(self._lib.rfid_batch_get_window_moments, capi.MOMENTS_DTYPE, head=(int(stream),),
-                                 extra=max(int(extra), 0))
+        return self._window_rows(self._lib.rfid_batch_get_window_moments, capi.MOMENTS_DTYPE, stream, extra)
 
     def batch_slots_ms(self) -> float:
         return self._stage_ms(self._lib.rfid_batch_slots_ms)
@@ -510,8 +517,7 @@ class Context:
         cut-off, RN16 and EPC alike, in seq order (n_windows_used of them), of the last batch_commands_enqueue.  extra > 0: up
         to that many of the table's rows behind them as well (zeroed by the stage).  rfid.batch.command_fields turns a row
         into names, Q, RN16 and timings."""
-        return self._sized_fetch(self._lib.rfid_batch_get_window_commands, capi.COMMAND_DTYPE, head=(int(stream),),
-                                 extra=max(int(extra), 0))
+        return self._window_rows(self._lib.rfid_batch_get_window_commands, capi.COMMAND_DTYPE, stream, extra)
 
     def batch_commands_ms(self) -> float:
         return self._stage_ms(self._lib.rfid_batch_commands_ms)
@@ -555,8 +561,7 @@ class Context:
         """One trace's row of the fine table (synchronises): the record of EVERY EPC window before the cut-off, in seq order,
         failed ones included (n_windows_used // 2 of them; flags bit 0 tells them apart), of the last batch_fine_enqueue.
         extra > 0: up to that many of the table's rows behind them as well (zeroed by the stage)."""
-        return self._sized_fetch(self._lib.rfid_batch_get_window_fine, capi.FINE_DTYPE, head=(int(stream),),
-                                 extra=max(int(extra), 0))
+        return self._window_rows(self._lib.rfid_batch_get_window_fine, capi.FINE_DTYPE, stream, extra)
 
     def batch_fine_ms(self) -> float:
         return self._stage_ms(self._lib.rfid_batch_fine_ms)
@@ -565,14 +570,7 @@ class Context:
         """The same sums for ONE EPC window in host memory (rfid_fine_window): gated = its 1370 gated, DC-free samples,
         result = its capi.RESULT_DTYPE record (what decoder_work returned, or that record with bits the caller has
         corrected).  -> one capi.FINE_DTYPE record, stream = seq = start = 0."""
-        gated = np.ascontiguousarray(gated, dtype=np.complex64)
-        if len(gated) != 1370:
-            raise ValueError("an EPC window has 1370 samples")
-        res = np.zeros(1, dtype=capi.RESULT_DTYPE)
-        res[0] = result
-        out = np.zeros(1, dtype=capi.FINE_DTYPE)
-        self._chk(self._lib.rfid_fine_window(self._h, gated.ctypes.data, res.ctypes.data, out.ctypes.data))
-        return out[0]
+        return self._one_window(self._lib.rfid_fine_window, capi.FINE_DTYPE, gated, result)
 
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1

@@ -73,6 +73,46 @@ def check_crafted_windows(ctx, oracle_mod, rfid):
         ctx.fine_window(w[:250], res)
 
 
+def check_per_call_forms_share_one_buffer(rfid, oracle_mod, synth_mod):
+    """The four per-call forms upload to, compute on and download from ONE device buffer of the context, which grows as a call
+    needs: in one context without a plan -- repair_window, window_moments of 9 windows (two packs; grows the buffer), fine_window,
+    commands_of 17 spans (two blocks; grows it again), window_moments of 1 window, repair_window on the first input again.  Every
+    result equals, byte for byte, what the same call returns in a context of its own; the second repair equals the first."""
+    import commands_cases
+    frames = rotated_frames(oracle_mod)
+    # a frame the decoder got right, handed in with one bit changed and its CRC marked as failed: the search has a frame to repair
+    name, w, d, phi = frames[4]
+    bits = d["bits"][:128].copy()
+    bits[40] ^= 1
+    res = repair_ref.result_of_dump(d)
+    res["bits"] = repair_ref.inv.pack_frames(bits[None, :])[0]
+    res["crc_ok"] = 0
+    nine = np.stack([f[1][:240] for f in frames[:9]])
+    spans, levels, names = commands_cases.crafted_spans(synth_mod)
+    w2, d2 = frames[7][1], frames[7][2]
+    calls = [
+        ("repair", lambda c: c.repair_window(w, res)),
+        ("moments of 9", lambda c: c.window_moments(nine)),
+        ("fine", lambda c: c.fine_window(w2, repair_ref.result_of_dump(d2))),
+        ("commands of 17", lambda c: c.commands_of(spans[:17], levels[:17])),
+        ("moments of 1", lambda c: c.window_moments(nine[3:4])),
+        ("repair again", lambda c: c.repair_window(w, res)),
+    ]
+    ctx = rfid.Context(device=0)
+    try:
+        got = [f(ctx).tobytes() for _, f in calls]
+    finally:
+        ctx.close()
+    for (what, f), g in zip(calls, got):
+        fresh = rfid.Context(device=0)
+        try:
+            assert f(fresh).tobytes() == g, what
+        finally:
+            fresh.close()
+    assert got[5] == got[0] and got[0].strip(b"\0") and got[2].strip(b"\0")
+    assert len(got[1]) == 9 * 32 and len(got[3]) == 17 * 48 and got[1][3 * 32 + 8:4 * 32] == got[4][8:]     # (behind stream, seq)
+
+
 def check_rows(ctx, want, what="", extra=3, stats=True):
     """the packed records against want[0], every trace's row against want[1] (and `extra` zero rows behind it) -> all the bytes.
     stats: the context's statistics are still those of the pass the stage ran behind"""

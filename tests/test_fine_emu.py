@@ -364,6 +364,13 @@ def test_crafted_windows_through_fine_window(oracle_mod):
         ctx.close()
 
 
+def test_per_call_forms_share_one_buffer(oracle_mod, synth_mod):
+    """repair_window, window_moments, fine_window and commands_of interleaved in one context, the buffer growing twice: every
+    result is what a context of its own returns"""
+    import rfid
+    cases.check_per_call_forms_share_one_buffer(rfid, oracle_mod, synth_mod)
+
+
 def test_the_estimate_is_at_least_twice_as_steady_as_h_est(oracle_mod, synth_mod):
     """60 rounds, one tag, h = 0.10 e^{j 2.1}, sigma = 0.03: over the CRC-verified reads the phase of the data-aided h (fine_fields of
     the library's records) scatters at most half as much about the truth, 25 complex64(h), as the decoder's h_est does.  Theory: h_est

@@ -133,6 +133,13 @@ def test_crafted_windows_through_fine_window(oracle_mod):
         ctx.close()
 
 
+def test_per_call_forms_share_one_buffer(oracle_mod, synth_mod):
+    """repair_window, window_moments, fine_window and commands_of interleaved in one context, the buffer growing twice: every
+    result is what a context of its own returns"""
+    import rfid
+    cases.check_per_call_forms_share_one_buffer(rfid, oracle_mod, synth_mod)
+
+
 @pytest.fixture(scope="module")
 def small(oracle_mod, synth_mod):
     """the four traces of tests/test_fine_emu.py: 16, 12, 8 and 12 EPC windows"""

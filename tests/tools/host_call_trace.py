@@ -76,15 +76,36 @@ def _all_stages(mode):
         ctx.batch_plan_tracks()
         ctx.batch_plan_quality()
         ctx.batch_plan_repair()
+        ctx.batch_plan_slots()
+        ctx.batch_plan_commands()
+        ctx.batch_plan_fine()
         for _ in range(2):
             _passes(ctx, data, 1)
             ctx.batch_inventory()
             ctx.batch_tracks()
             ctx.batch_quality()
             ctx.batch_repair()
-            assert len(ctx.batch_window_quality(1)) > 0 and len(ctx.batch_window_repairs(1)) > 0
+            ctx.batch_slots_enqueue()
+            ctx.batch_commands_enqueue()
+            ctx.batch_fine()
+            assert len(ctx.batch_window_quality(1)) > 0 and len(ctx.batch_window_repairs(1)) > 0 and len(ctx.batch_window_fine(1)) > 0
+            assert len(ctx.batch_window_moments(1)) > 0 and len(ctx.batch_window_commands(1)) > 0
         _finish(ctx, (2 if mode else 1, False))
     return run
+
+
+def _per_call_forms(ctx):
+    """the four calls that work on windows a caller holds, interleaved: what they allocate, copy and launch (the values do not matter)"""
+    import numpy as np
+    from rfid import capi
+    win = np.zeros(1370, dtype=np.complex64)
+    res = np.zeros(1, dtype=capi.RESULT_DTYPE)[0]
+    res["type"] = 1
+    for n_mom, n_cmd in ((9, 17), (1, 3)):
+        ctx.repair_window(win, res)
+        ctx.window_moments(np.zeros((n_mom, 240), dtype=np.complex64))
+        ctx.fine_window(win, res)
+        ctx.commands_of(np.ones((n_cmd, 704), dtype=np.complex64), np.ones(n_cmd, dtype=np.complex64))
 
 
 def _second_set(ctx):
@@ -108,6 +129,7 @@ SCENARIOS = {
     "all_stages_mode0": _all_stages(0),
     "all_stages_mode2": _all_stages(2),
     "second_set": _second_set,
+    "per_call_forms": _per_call_forms,
 }
 
 
