@@ -1,6 +1,6 @@
-"""What tests/test_commands_emu.py (the kernels on the wave emulator) and tests/test_gpu_commands.py (on the device) share: the inputs
-of the commands stage's cases, cut and laid out by the ORACLE alone, and the checks that are the same on both sides.  Expected records
-come from tests/commands_ref.py; what every window's command must BE comes from the synthesiser's slot table."""
+"""What the commands stage's cases (tests/commands_suite.py, on both sides; tests/test_commands_emu.py and tests/test_gpu_commands.py,
+on one) are built from: their inputs, cut and laid out by the ORACLE alone, and the checks that are the same wherever the records come
+from.  Expected records come from tests/commands_ref.py; what every window's command must BE comes from the synthesiser's slot table."""
 import ctypes as C
 
 import numpy as np
@@ -8,6 +8,7 @@ import numpy as np
 import commands_ref as ref
 import slots_cases
 import slots_ref
+from stage_backend import lay_out
 
 SIGMA = slots_cases.SIGMA
 SPAN = ref.SPAN
@@ -90,7 +91,7 @@ def clipped_batches(oracle_mod, synth_mod, start=660):
     dark[-4000:] = 0
     out = []
     for order in ((cut, full), (full, cut), (dark, cut)):
-        host, lens, L, stride = slots_cases.lay_out(list(order), odd_stride=False)
+        host, lens, L, stride = lay_out(list(order))
         assert L == len(full)
         refs, want = oracle_of(oracle_mod, host, lens, 2)
         k = 0 if order[0] is cut else 1

@@ -1,24 +1,14 @@
-"""What tests/test_slots_emu.py (the kernels on the wave emulator) and tests/test_gpu_slots.py (on the device) share: the inputs of
-the slots stage's cases, cut and laid out by the ORACLE alone, and the checks that are the same on both sides.  Expected records come
-from tests/slots_ref.py."""
+"""What the slots stage's cases (tests/slots_suite.py, on both sides; tests/test_slots_emu.py and tests/test_gpu_slots.py, on one) are
+built from: their inputs, cut and laid out by the ORACLE alone, and the checks that are the same wherever the records come from.
+Expected records come from tests/slots_ref.py."""
 import ctypes as C
 
 import numpy as np
 
 import slots_ref as ref
+from stage_backend import lay_out
 
 SIGMA = 0.01
-
-
-def lay_out(ts, odd_stride=True):
-    """traces -> (host [n][stride], lens, L, stride); an odd row stride unless told otherwise"""
-    L = max(map(len, ts))
-    stride = ((L + 2) | 1) if odd_stride else ((L + 1) & ~1)
-    host = np.zeros((len(ts), stride), dtype=np.complex64)
-    lens = np.array([len(t) for t in ts], dtype=np.int64)
-    for i, t in enumerate(ts):
-        host[i, : len(t)] = t
-    return host, lens, L, stride
 
 
 def cut_behind(oracle_mod, x, fixed_q, keep):
@@ -41,7 +31,7 @@ def ragged_batch(oracle_mod, synth_mod):
     cut behind their windows 93, 30 and 7 (no count a multiple of 8, two of them odd: a last RN16 without its EPC), odd row stride"""
     ts = [ref.shape_trace(synth_mod, ref.SHAPES[0], SIGMA).samples, ref.shape_trace(synth_mod, ref.SHAPES[4], SIGMA).samples,
           synth_mod.make_trace(n_rounds=1, fixed_q=2, tag_ids=(1, 2, 3, 4), seed=5, sigma=SIGMA).samples]
-    host, lens, L, stride = lay_out(ts)
+    host, lens, L, stride = lay_out(ts, odd_stride=True)
     for b, keep in enumerate((93, 30, 7)):
         lens[b] = cut_behind(oracle_mod, ts[b], 2, keep)
     refs, want = oracle_of(oracle_mod, host, lens, 2)
@@ -146,3 +136,38 @@ def check_classification(rb, rows, truth_slots, shape):
         assert (int(g["cls"]), int(g["answered"])) == t, (shape, k, g, t, truth_slots[k])
         assert int(g["seq"]) == 2 * k
     return got
+
+
+def five_shapes(backend, oracle_mod, synth_mod):
+    """the five shapes at sigma = 0.01, each through a pass of its own context; the records are the oracle's
+    -> per shape (trace, records)"""
+    import rfid
+    out = []
+    for shape in ref.SHAPES:
+        t = ref.shape_trace(synth_mod, shape, SIGMA)
+        host, lens, L, stride = lay_out([t.samples])
+        dev = backend.put(host, lens)
+        ctx = rfid.Context(device=0, fixed_q=shape[0])
+        try:
+            ctx.batch_set_long_stream(0)
+            ctx.batch_plan(1, L)
+            ctx.batch_plan_slots()
+            backend.run_pass(ctx, dev, L, stride)
+            ctx.batch_slots_enqueue()
+            rows = ctx.batch_window_moments(0)
+        finally:
+            ctx.close()
+        o = oracle_mod.run_trace(t.samples, oracle_mod.config(fixed_q=shape[0]))
+        ref.assert_equal(rows, ref.expected(o, oracle_mod.fir(t.samples)), shape)
+        out.append((t, rows))
+    return out
+
+
+def check_five_shapes(rb, classified):
+    """classify_slots == SlotTruth for EVERY slot of every shape of five_shapes() (no slot may be left out) and == the restatement
+    of slots_ref; Schoute's estimate on the five-tag shape is 4.82 per round, the suggested Q 2"""
+    for shape, (t, rows) in zip(ref.SHAPES, classified):
+        got = check_classification(rb, rows, t.slots, shape)
+        assert len(got) == shape[2] << shape[0]
+    est = rb.estimate_population(rb.classify_slots(classified[0][1])["cls"], 12)
+    assert "%.2f" % est == "4.82" and rb.suggest_q(est) == 2

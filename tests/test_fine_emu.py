@@ -18,7 +18,8 @@ import fine_ref as ref
 import slots_cases
 import tracks_ref as tref
 import emu_lib
-from emu_lib import pack as _pack, run_pass as _pass
+from emu_lib import run_pass as _pass
+from stage_backend import lay_out
 
 TAGS = (0x27, 0x27, 0x31)
 SEEDS = ((104, 4), (112, 3), (120, 2), (128, 3))       # (seed, inventory rounds) per trace
@@ -40,7 +41,7 @@ def _oracle(oracle_mod, host, lens, fixed_q=2, **cfg):
 @pytest.fixture(scope="module")
 def batch(oracle_mod, synth_mod):
     ts = [synth_mod.make_trace(n_rounds=n, fixed_q=2, tag_ids=TAGS, seed=seed, sigma=0.02, t1_jitter_raw=3).samples for seed, n in SEEDS]
-    host, lens, L, stride = _pack(ts)
+    host, lens, L, stride = lay_out(ts, shorten=777)
     refs, ys = _oracle(oracle_mod, host, lens)
     packed, rows = ref.expected_batch(refs, ys)
     # the input does what the case is about, by the oracle alone: row counts that fill two packs, one and a half, and one; failed
@@ -166,7 +167,7 @@ def test_a_corrupted_frame_has_its_record_and_says_so(oracle_mod, synth_mod):
     there, decision-directed, with flags = 0, and absent from the packed array; five rows: less than a pack"""
     import rfid
     x = synth_mod.make_trace(n_rounds=5, fixed_q=0, tag_ids=(0x27,), seed=7, sigma=0.02, corrupt_rounds=(3,)).samples
-    host, lens, L, stride = _pack([x], shorten=0)
+    host, lens, L, stride = lay_out([x])
     o = oracle_mod.run_trace(host[0, : lens[0]], oracle_mod.config(fixed_q=0))
     packed, rows = ref.expected(o, oracle_mod.fir(host[0, : lens[0]]), 0)
     assert len(rows) == 5 and rows["flags"].tolist() == [1, 1, 0, 1, 1] and packed["seq"].tolist() == [1, 3, 7, 9]
@@ -381,7 +382,7 @@ def test_the_estimate_is_at_least_twice_as_steady_as_h_est(oracle_mod, synth_mod
     from rfid import batch as rb
     h_true = 0.10 * np.exp(2.1j)
     x = synth_mod.make_trace(n_rounds=60, fixed_q=0, tag_ids=(0x27,), seed=3, sigma=0.03, h=h_true).samples
-    host, lens, L, stride = _pack([x], shorten=0)
+    host, lens, L, stride = lay_out([x])
     o = oracle_mod.run_trace(host[0, : lens[0]], oracle_mod.config(fixed_q=0))
     packed, rows = ref.expected(o, oracle_mod.fir(host[0, : lens[0]]), 0)
     assert len(packed) == 60

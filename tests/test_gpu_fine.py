@@ -9,6 +9,8 @@ import sys
 import numpy as np
 import pytest
 
+import stage_backend
+from stage_backend import lay_out
 import fine_cases as cases
 import fine_ref as ref
 import tracks_ref as tref
@@ -23,18 +25,9 @@ TAGS6 = (0x27, 0x27, 0x31, 0x31, 0x4C, 0x5A)
 TAGS3 = (0x27, 0x27, 0x31)
 
 
-def _upload(traces):
-    import torch
-    L = max(map(len, traces))
-    stride = (L + 1) & ~1
-    host = np.zeros((len(traces), stride), dtype=np.complex64)
-    lens = np.array([len(t) for t in traces], dtype=np.int64)
-    for i, t in enumerate(traces):
-        host[i, : len(t)] = t
-    dev = torch.from_numpy(host.view(np.float32)).to("cuda:0")
-    dlens = torch.from_numpy(lens).to("cuda:0")
-    torch.cuda.synchronize()
-    return host, lens, L, stride, dev, dlens
+@pytest.fixture(scope="module")
+def backend():
+    return stage_backend.Device()
 
 
 def _oracle(oracle_mod, host, lens, fixed_q, **cfg):
@@ -67,12 +60,13 @@ def _check(ctx, want, what=""):
 
 
 @pytest.mark.parametrize("mode", [0, 2], ids=["fused-front-end", "long-stream"])
-def test_ragged_batch_of_eight_traces(oracle_mod, synth_mod, mode):
+def test_ragged_batch_of_eight_traces(backend, oracle_mod, synth_mod, mode):
     """14 .. 7 rounds, FIXED_Q = 3, six tags, sigma = 0.03; eight traces of different lengths.  The pass three times: byte-identical
     records, packed and per trace; reads and failed windows alike against the oracle."""
     import rfid
     ts = [synth_mod.make_trace(n_rounds=14 - k, fixed_q=3, tag_ids=TAGS6, seed=900 + k, sigma=0.03, t1_jitter_raw=3).samples for k in range(8)]
-    host, lens, L, stride, dev, dlens = _upload(ts)
+    host, lens, L, stride = lay_out(ts)
+    dev = backend.put(host, lens)
     refs, ys = _oracle(oracle_mod, host, lens, 3)
     want = ref.expected_batch(refs, ys)
     for b, r in enumerate(want[1]):
@@ -84,7 +78,7 @@ def test_ragged_batch_of_eight_traces(oracle_mod, synth_mod, mode):
         _plan(ctx, 8, L, 16)
         blobs = []
         for rep in range(3):
-            ctx.batch_process_ptr(dev.data_ptr(), stride, L, dlens.data_ptr())
+            backend.run_pass(ctx, dev, L, stride)
             blobs.append(_check(ctx, want, (mode, rep)))
         assert blobs[0] == blobs[1] == blobs[2]
         print("fine of 8 traces: %.4f ms, %d reads, %d EPC windows; decode %.4f ms" %
@@ -94,14 +88,16 @@ def test_ragged_batch_of_eight_traces(oracle_mod, synth_mod, mode):
 
 
 @pytest.mark.parametrize("overlap", [1, 2], ids=["one-result-set", "two-result-sets"])
-def test_64_traces_two_passes_back_to_back(oracle_mod, synth_mod, overlap):
+def test_64_traces_two_passes_back_to_back(backend, oracle_mod, synth_mod, overlap):
     """64 traces of three rounds (FIXED_Q = 1), and the same traces in the opposite order as a second batch.  With two result sets
     alternating (RFID_OVERLAP=2) the records of every pass are that pass's -- also when the next pass, over other samples, is
     enqueued before they are fetched."""
     import rfid
     ts = [synth_mod.make_trace(n_rounds=3, fixed_q=1, tag_ids=TAGS3, seed=500 + k, sigma=0.02, t1_jitter_raw=3).samples for k in range(64)]
-    host, lens, L, stride, dev, dlens = _upload(ts)
-    _, _, L2, stride2, dev2, dlens2 = _upload(ts[::-1])
+    host, lens, L, stride = lay_out(ts)
+    dev = backend.put(host, lens)
+    host2, lens2, L2, stride2 = lay_out(ts[::-1])
+    dev2 = backend.put(host2, lens2)
     assert (L2, stride2) == (L, stride)
     refs, ys = _oracle(oracle_mod, host, lens, 1)
     want = ref.expected_batch(refs, ys)
@@ -112,9 +108,9 @@ def test_64_traces_two_passes_back_to_back(oracle_mod, synth_mod, overlap):
         ctx.set_knob("overlap", overlap)
         _plan(ctx, 64, L, 8)
         for rep in range(2):
-            ctx.batch_process_ptr(dev.data_ptr(), stride, L, dlens.data_ptr())
+            backend.run_pass(ctx, dev, L, stride)
             _enqueue(ctx)
-            ctx.batch_process_ptr(dev2.data_ptr(), stride, L, dlens2.data_ptr())      # (the next pass, before anything is fetched)
+            backend.run_pass(ctx, dev2, L, stride)      # (the next pass, before anything is fetched)
             first = cases.check_rows(ctx, want, (overlap, rep, "first"), stats=False)
             second = _check(ctx, want2, (overlap, rep, "second"))
             assert first != second
@@ -141,18 +137,19 @@ def test_per_call_forms_share_one_buffer(oracle_mod, synth_mod):
 
 
 @pytest.fixture(scope="module")
-def small(oracle_mod, synth_mod):
+def small(backend, oracle_mod, synth_mod):
     """the four traces of tests/test_fine_emu.py: 16, 12, 8 and 12 EPC windows"""
     ts = [synth_mod.make_trace(n_rounds=n, fixed_q=2, tag_ids=TAGS3, seed=seed, sigma=0.02, t1_jitter_raw=3).samples
           for seed, n in ((104, 4), (112, 3), (120, 2), (128, 3))]
-    return _upload(ts)
+    host, lens, L, stride = lay_out(ts)
+    return host, lens, L, stride, backend.put(host, lens)
 
 
-def test_windows_behind_the_cut_off(oracle_mod, small):
+def test_windows_behind_the_cut_off(backend, oracle_mod, small):
     """MAX_NUM_QUERIES = 7 reached inside the traces: seven EPC windows each -- a pack that is cut off inside -- behind a pass of the
     same context's twin without the limit; the rows behind the cut-off are zero and the packed array holds no read from there"""
     import rfid
-    host, lens, L, stride, dev, dlens = small
+    host, lens, L, stride, dev = small
     refs, ys = _oracle(oracle_mod, host, lens, 2, max_num_queries=7)
     want = ref.expected_batch(refs, ys)
     full = ref.expected_batch(*_oracle(oracle_mod, host, lens, 2))
@@ -161,7 +158,7 @@ def test_windows_behind_the_cut_off(oracle_mod, small):
         ctx = rfid.Context(device=0, fixed_q=2, max_num_queries=mq)
         try:
             _plan(ctx, 4, L, 8)
-            ctx.batch_process_ptr(dev.data_ptr(), stride, L, dlens.data_ptr())
+            backend.run_pass(ctx, dev, L, stride)
             _check(ctx, w, mq)
             for b in range(4):
                 many = ctx.batch_window_fine(b, extra=10_000)
@@ -171,18 +168,18 @@ def test_windows_behind_the_cut_off(oracle_mod, small):
 
 
 @pytest.mark.parametrize("wgs", [0, 3])
-def test_a_later_trace_whose_rows_cross_a_pack_boundary(oracle_mod, small, wgs):
+def test_a_later_trace_whose_rows_cross_a_pack_boundary(backend, oracle_mod, small, wgs):
     """Traces 1 and 3 of the batch have twelve EPC windows: a pack and a half.  With the launch's default grid and with three
     workgroups for everything (the knob fine_wgs: every workgroup walks many packs, of several traces)"""
     import rfid
-    host, lens, L, stride, dev, dlens = small
+    host, lens, L, stride, dev = small
     want = ref.expected_batch(*_oracle(oracle_mod, host, lens, 2))
     assert len(want[1][1]) == 12 and len(want[1][3]) == 12
     ctx = rfid.Context(device=0, fixed_q=2, max_num_queries=BIG)
     try:
         _plan(ctx, 4, L, 8)
         ctx.set_knob("fine_wgs", wgs)
-        ctx.batch_process_ptr(dev.data_ptr(), stride, L, dlens.data_ptr())
+        backend.run_pass(ctx, dev, L, stride)
         _check(ctx, want, wgs)
     finally:
         ctx.close()

@@ -8,6 +8,8 @@ import sys
 import numpy as np
 import pytest
 
+import stage_backend
+from stage_backend import lay_out
 import inventory_ref as ref
 
 pytestmark = pytest.mark.gpu
@@ -19,27 +21,19 @@ BIG = (1 << 31) - 2
 TAGS6 = (0x27, 0x27, 0x31, 0x31, 0x4C, 0x5A)
 
 
-def _upload(traces):
-    import torch
-    L = max(map(len, traces))
-    stride = (L + 1) & ~1
-    host = np.zeros((len(traces), stride), dtype=np.complex64)
-    lens = np.array([len(t) for t in traces], dtype=np.int64)
-    for i, t in enumerate(traces):
-        host[i, : len(t)] = t
-    dev = torch.from_numpy(host.view(np.float32)).to("cuda:0")
-    dlens = torch.from_numpy(lens).to("cuda:0")
-    torch.cuda.synchronize()
-    return host, lens, L, stride, dev, dlens
+@pytest.fixture(scope="module")
+def backend():
+    return stage_backend.Device()
 
 
 @pytest.mark.parametrize("mode", [0, 2], ids=["fused-front-end", "long-stream"])
-def test_ragged_batch_of_eight_traces(oracle_mod, synth_mod, mode):
+def test_ragged_batch_of_eight_traces(backend, oracle_mod, synth_mod, mode):
     """40 rounds, FIXED_Q = 3, six tags of which two pairs end in the same byte, sigma = 0.03; eight traces of different lengths.
     The pass three times: byte-identical entry arrays.  Then the same pass through a 16-slot table (six frames: probes collide)."""
     import rfid
     ts = [synth_mod.make_trace(n_rounds=40 - 3 * k, fixed_q=3, tag_ids=TAGS6, seed=900 + k, sigma=0.03, t1_jitter_raw=3).samples for k in range(8)]
-    host, lens, L, stride, dev, dlens = _upload(ts)
+    host, lens, L, stride = lay_out(ts)
+    dev = backend.put(host, lens)
     refs = [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=3, max_num_queries=BIG)) for b in range(8)]
     want, want_counts = ref.expected_batch([o.dumps for o in refs])
     # the input does what the case is about, by the oracle alone
@@ -54,7 +48,7 @@ def test_ragged_batch_of_eight_traces(oracle_mod, synth_mod, mode):
         ctx.batch_plan_inventory(16)
         blobs = []
         for rep in range(3):
-            ctx.batch_process_ptr(dev.data_ptr(), stride, L, dlens.data_ptr())
+            backend.run_pass(ctx, dev, L, stride)
             ent, counts = ctx.batch_inventory()
             st = ctx.batch_stats()
             ref.assert_equal(ent, counts, want, want_counts, (mode, rep))

@@ -9,6 +9,8 @@ import sys
 import numpy as np
 import pytest
 
+import stage_backend
+from stage_backend import lay_out
 import quality_ref as ref
 import tracks_ref as tref
 
@@ -21,18 +23,9 @@ BIG = (1 << 31) - 2
 TAGS6 = (0x27, 0x27, 0x31, 0x31, 0x4C, 0x5A)
 
 
-def _upload(traces):
-    import torch
-    L = max(map(len, traces))
-    stride = (L + 1) & ~1
-    host = np.zeros((len(traces), stride), dtype=np.complex64)
-    lens = np.array([len(t) for t in traces], dtype=np.int64)
-    for i, t in enumerate(traces):
-        host[i, : len(t)] = t
-    dev = torch.from_numpy(host.view(np.float32)).to("cuda:0")
-    dlens = torch.from_numpy(lens).to("cuda:0")
-    torch.cuda.synchronize()
-    return host, lens, L, stride, dev, dlens
+@pytest.fixture(scope="module")
+def backend():
+    return stage_backend.Device()
 
 
 def _plan(ctx, n, L, max_tags):
@@ -50,12 +43,13 @@ def _stages(ctx):
 
 
 @pytest.mark.parametrize("mode", [0, 2], ids=["fused-front-end", "long-stream"])
-def test_ragged_batch_of_eight_traces(oracle_mod, synth_mod, mode):
+def test_ragged_batch_of_eight_traces(backend, oracle_mod, synth_mod, mode):
     """40 rounds, FIXED_Q = 3, six tags, sigma = 0.03; eight traces of different lengths.  The pass three times: byte-identical
     records, packed and per trace; reads and failed windows alike against the oracle."""
     import rfid
     ts = [synth_mod.make_trace(n_rounds=40 - 3 * k, fixed_q=3, tag_ids=TAGS6, seed=900 + k, sigma=0.03, t1_jitter_raw=3).samples for k in range(8)]
-    host, lens, L, stride, dev, dlens = _upload(ts)
+    host, lens, L, stride = lay_out(ts)
+    dev = backend.put(host, lens)
     refs = [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=3, max_num_queries=BIG)) for b in range(8)]
     ys = [oracle_mod.fir(host[b, : lens[b]]) for b in range(8)]
     packed, rows = ref.expected_batch(refs, ys)
@@ -69,7 +63,7 @@ def test_ragged_batch_of_eight_traces(oracle_mod, synth_mod, mode):
         _plan(ctx, 8, L, 16)
         blobs = []
         for rep in range(3):
-            ctx.batch_process_ptr(dev.data_ptr(), stride, L, dlens.data_ptr())
+            backend.run_pass(ctx, dev, L, stride)
             reads, q = _stages(ctx)
             ref.assert_equal(q, packed, (mode, rep))
             assert np.array_equal(q["stream"], reads["stream"]) and np.array_equal(q["seq"], reads["seq"])

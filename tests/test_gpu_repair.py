@@ -10,6 +10,8 @@ import sys
 import numpy as np
 import pytest
 
+import stage_backend
+from stage_backend import lay_out
 import repair_ref as ref
 import repair_windows as rw
 
@@ -20,18 +22,9 @@ BIG = (1 << 31) - 2
 EDGE = dict(fixed_q=0, tag_ids=(0x27,), seed=1, n_rounds=24, sigma=0.02, t1_jitter_raw=3, h=0.016 * np.exp(2.1j))
 
 
-def _upload(traces):
-    import torch
-    L = max(map(len, traces))
-    stride = (L + 1) & ~1
-    host = np.zeros((len(traces), stride), dtype=np.complex64)
-    lens = np.array([len(t) for t in traces], dtype=np.int64)
-    for i, t in enumerate(traces):
-        host[i, : len(t)] = t
-    dev = torch.from_numpy(host.view(np.float32)).to("cuda:0")
-    dlens = torch.from_numpy(lens).to("cuda:0")
-    torch.cuda.synchronize()
-    return host, lens, L, stride, dev, dlens
+@pytest.fixture(scope="module")
+def backend():
+    return stage_backend.Device()
 
 
 def _eight(synth_mod):
@@ -48,11 +41,12 @@ def _plan(ctx, n, L, max_tags):
 
 
 @pytest.mark.parametrize("mode", [0, 2], ids=["fused-front-end", "long-stream"])
-def test_ragged_batch_of_eight_traces(oracle_mod, synth_mod, mode):
+def test_ragged_batch_of_eight_traces(backend, oracle_mod, synth_mod, mode):
     """The edge trace, the lost tag, the mixed slots and five more seeds at A = 0.016, eight traces of different lengths.  The pass
     three times: byte-identical records, packed and per trace, against the reference."""
     import rfid
-    host, lens, L, stride, dev, dlens = _upload(_eight(synth_mod))
+    host, lens, L, stride = lay_out(_eight(synth_mod))
+    dev = backend.put(host, lens)
     refs = [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=2, max_num_queries=BIG)) for b in range(8)]
     ys = [oracle_mod.fir(host[b, : lens[b]]) for b in range(8)]
     packed, rows = ref.expected_batch(oracle_mod, refs, ys)
@@ -65,7 +59,7 @@ def test_ragged_batch_of_eight_traces(oracle_mod, synth_mod, mode):
         _plan(ctx, 8, L, 8)
         blobs = []
         for rep in range(3):
-            ctx.batch_process_ptr(dev.data_ptr(), stride, L, dlens.data_ptr())
+            backend.run_pass(ctx, dev, L, stride)
             ctx.batch_inventory_enqueue()
             got = ctx.batch_repair()
             ref.assert_equal(got, packed, (mode, rep))

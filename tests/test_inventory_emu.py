@@ -14,6 +14,7 @@ import pytest
 import inventory_ref as ref
 import emu_lib
 from emu_lib import oracle_runs as _oracle, run_pass as _pass
+from stage_backend import lay_out
 
 TAGS = (0x27, 0x27, 0x31)
 SEEDS = ((104, 4), (112, 3))       # (seed, inventory rounds) per trace
@@ -28,14 +29,7 @@ def emulated_library():
 def _batch(synth_mod, **kw):
     ts = [synth_mod.make_trace(n_rounds=n, fixed_q=2, tag_ids=TAGS, seed=seed, sigma=0.02, t1_jitter_raw=3, **kw).samples
           for seed, n in SEEDS]
-    L = max(map(len, ts))
-    stride = (L + 1) & ~1
-    host = np.zeros((len(ts), stride), dtype=np.complex64)
-    lens = np.array([len(t) for t in ts], dtype=np.int64)
-    lens[0] -= 777            # (ragged also where the longest trace is concerned)
-    for i, t in enumerate(ts):
-        host[i, : len(t)] = t
-    return host, lens, L, stride
+    return lay_out(ts, shorten=777)            # (ragged also where the longest trace is concerned)
 
 
 @pytest.fixture(scope="module")

@@ -14,7 +14,8 @@ import pytest
 import quality_ref as ref
 import tracks_ref as tref
 import emu_lib
-from emu_lib import pack as _pack, run_pass as _pass
+from emu_lib import run_pass as _pass
+from stage_backend import lay_out
 
 TAGS = (0x27, 0x27, 0x31)
 SEEDS = ((104, 4), (112, 3))       # (seed, inventory rounds) per trace
@@ -36,7 +37,7 @@ def _oracle(oracle_mod, host, lens, **cfg):
 @pytest.fixture(scope="module")
 def batch(oracle_mod, synth_mod):
     ts = [synth_mod.make_trace(n_rounds=n, fixed_q=2, tag_ids=TAGS, seed=seed, sigma=0.02, t1_jitter_raw=3).samples for seed, n in SEEDS]
-    host, lens, L, stride = _pack(ts)
+    host, lens, L, stride = lay_out(ts, shorten=777)
     refs, ys = _oracle(oracle_mod, host, lens)
     packed, rows = ref.expected_batch(refs, ys)
     # the input does what the case is about, by the oracle alone: every trace holds failed EPC windows next to its reads, and the
@@ -153,7 +154,7 @@ def test_a_corrupted_frame_fails_its_crc_with_the_snr_of_a_read(oracle_mod, synt
     import rfid
     from rfid import batch as rb
     x = synth_mod.make_trace(n_rounds=5, fixed_q=0, tag_ids=(0x27,), seed=7, sigma=0.02, corrupt_rounds=(3,)).samples
-    host, lens, L, stride = _pack([x], shorten=0)
+    host, lens, L, stride = lay_out([x])
     o = oracle_mod.run_trace(host[0, : lens[0]], oracle_mod.config(fixed_q=0))
     packed, rows = ref.expected(o, oracle_mod.fir(host[0, : lens[0]]), 0)
     failed = np.flatnonzero(rows["flags"] == 0)

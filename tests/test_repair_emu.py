@@ -17,6 +17,7 @@ import repair_windows as rw
 import tracks_ref as tref
 import emu_lib
 from emu_lib import run_pass as _pass
+from stage_backend import lay_out
 
 TRACES = dict(      # name -> (A, make_trace arguments)
     edge=(0.016, dict(fixed_q=0, tag_ids=(0x27,), seed=1, n_rounds=24)),
@@ -36,11 +37,6 @@ def make(synth_mod, name):
     return synth_mod.make_trace(sigma=0.02, t1_jitter_raw=3, h=A * np.exp(2.1j), **kw).samples
 
 
-def _pack(ts):
-    """traces -> (host array [n][stride], lengths, longest length, stride); nothing is cut short"""
-    return emu_lib.pack(ts, shorten=0)
-
-
 def _oracle(oracle_mod, host, lens, fixed_q, **cfg):
     refs = [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=fixed_q, **cfg)) for b in range(len(lens))]
     ys = [oracle_mod.fir(host[b, : lens[b]]) for b in range(len(lens))]
@@ -52,7 +48,7 @@ def single(oracle_mod, synth_mod):
     """name -> (host, lens, L, stride, fixed_q, oracle result, (packed, [rows]), y) of the three traces, each on its own"""
     out = {}
     for name, (A, kw) in TRACES.items():
-        host, lens, L, stride = _pack([make(synth_mod, name)])
+        host, lens, L, stride = lay_out([make(synth_mod, name)])
         refs, ys = _oracle(oracle_mod, host, lens, kw["fixed_q"])
         out[name] = (host, lens, L, stride, kw["fixed_q"], refs[0], ref.expected_batch(oracle_mod, refs, ys), ys[0])
     return out
@@ -133,7 +129,7 @@ def batch(oracle_mod, synth_mod):
     """the three traces and a pure-carrier trace in the middle as one ragged batch, FIXED_Q = 2 for all of them"""
     ts = [make(synth_mod, "mixed"), make(synth_mod, "edge"), None, make(synth_mod, "lost")]
     ts[2] = np.full(len(ts[0]) // 2, np.complex64(0.8 + 0.1j))
-    host, lens, L, stride = _pack(ts)
+    host, lens, L, stride = lay_out(ts)
     refs, ys = _oracle(oracle_mod, host, lens, 2)
     want = ref.expected_batch(oracle_mod, refs, ys)
     assert [len(r) for r in want[1]] == [32, 24, 0, 3] and [int((r["n_flips"] > 0).sum()) for r in want[1]] == [6, 14, 0, 3]
@@ -217,7 +213,7 @@ def test_no_false_comfort_a_frame_sent_wrong_stays_unrepaired(oracle_mod, synth_
     reversing a decision toggles.  By the reference the window stays unrepaired, and the stage says the same"""
     import rfid
     x = synth_mod.make_trace(n_rounds=5, fixed_q=0, tag_ids=(0x27,), seed=7, sigma=0.02, corrupt_rounds=(3,)).samples
-    host, lens, L, stride = _pack([x])
+    host, lens, L, stride = lay_out([x])
     refs, ys = _oracle(oracle_mod, host, lens, 0)
     want = ref.expected_batch(oracle_mod, refs, ys)
     rows = want[1][0]

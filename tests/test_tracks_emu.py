@@ -15,7 +15,8 @@ import pytest
 import inventory_ref as iref
 import tracks_ref as ref
 import emu_lib
-from emu_lib import pack as _pack, oracle_runs as _oracle, run_pass as _pass
+from emu_lib import oracle_runs as _oracle, run_pass as _pass
+from stage_backend import lay_out
 
 TAGS = (0x27, 0x27, 0x31)
 SEEDS = ((104, 4), (112, 3))       # (seed, inventory rounds) per trace
@@ -39,7 +40,7 @@ def _seqs_by_entry(reads, off):
 
 @pytest.fixture(scope="module")
 def batch(oracle_mod, synth_mod):
-    host, lens, L, stride = _pack(_traces(synth_mod))
+    host, lens, L, stride = lay_out(_traces(synth_mod), shorten=777)
     refs = _oracle(oracle_mod, host, lens)
     ent, counts, reads, off = ref.expected_batch(refs)
     # the input does what the case is about, by the oracle alone: the tags interleave in time, one of them is read four times
@@ -161,7 +162,7 @@ def test_a_trace_without_a_verified_read_has_an_empty_range(oracle_mod, synth_mo
     import rfid
     ts = _traces(synth_mod)
     ts.insert(1, np.full(len(ts[0]) // 2, 0.8 + 0.1j, dtype=np.complex64))
-    host, lens, L, stride = _pack(ts)
+    host, lens, L, stride = lay_out(ts, shorten=777)
     refs = [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=2)) for b in range(3)]
     want = ref.expected_batch(refs)
     ent, counts, reads, off = want
@@ -191,7 +192,7 @@ def test_sixteen_waves_share_a_trace(oracle_mod, synth_mod):
     their prefix decide every place."""
     import rfid
     x = synth_mod.make_trace(n_rounds=20, fixed_q=2, tag_ids=TAGS, seed=131, sigma=0.02, t1_jitter_raw=3).samples
-    host, lens, L, stride = _pack([x], shorten=0)
+    host, lens, L, stride = lay_out([x])
     refs = _oracle(oracle_mod, host, lens)
     want = ref.expected_batch(refs)
     ent, counts, reads, off = want

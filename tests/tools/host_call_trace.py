@@ -23,9 +23,9 @@ for p in (ROOT, os.path.join(ROOT, "gen2-uhf-rfid-reader_amd"), os.path.join(ROO
 
 
 def _two_ragged():
-    import emu_lib
+    from stage_backend import lay_out
     from rfid import synth
-    return emu_lib.pack([synth.make_trace(n_rounds=4, seed=11, sigma=0.01).samples, synth.make_trace(n_rounds=3, seed=12, sigma=0.01).samples])
+    return lay_out([synth.make_trace(n_rounds=4, seed=11, sigma=0.01).samples, synth.make_trace(n_rounds=3, seed=12, sigma=0.01).samples], shorten=777)
 
 
 def _passes(ctx, data, n, want_scores=False):
@@ -109,9 +109,9 @@ def _per_call_forms(ctx):
 
 
 def _second_set(ctx):
-    import emu_lib
+    from stage_backend import lay_out
     from rfid import synth
-    data = emu_lib.pack([synth.make_trace(n_rounds=1, seed=100 + i, sigma=0.01).samples for i in range(64)], shorten=7)
+    data = lay_out([synth.make_trace(n_rounds=1, seed=100 + i, sigma=0.01).samples for i in range(64)], shorten=7)
     ctx.set_knob("long_stream", 0)
     ctx.set_knob("overlap", 2)
     ctx.batch_plan(64, data[2])
