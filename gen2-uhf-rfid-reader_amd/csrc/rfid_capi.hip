@@ -30,6 +30,7 @@
 #include "rfid_slots.hpp"
 #include "rfid_commands.hpp"
 #include "rfid_fine.hpp"
+#include "rfid_retune.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
 // the launch list of the long-stream front end, on the stream named by the enclosing scope's `ls2_stream`
@@ -82,6 +83,7 @@ struct RfidKnobs {
   int inventory_slots = 0; // RFID_INVENTORY_SLOTS   2..1024 (a power of two): table slots per trace of the inventory stage, read by rfid_batch_plan_inventory (0: the next power of two >= 2 x max_tags_per_trace).  A small table makes frames collide: the stage's later rounds
   int commands_rows = 0;   // RFID_COMMANDS_ROWS     1..16: rows per wave and step of the commands stage (0: one while the launch has a wave per row, then the next powers of two up to 16)
   int fine_wgs = 0;        // RFID_FINE_WGS          1..65536: most single-wave workgroups of the fine stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many packs
+  int retune_wgs = 0;      // RFID_RETUNE_WGS        1..65536: most single-wave workgroups of the retune stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
 };
 
 // the timing events of a pass: stage i of the four took the time from event i to event i + 1
@@ -297,7 +299,7 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
-  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine.  What the seven share ----
+  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune.  What the eight share ----
   struct Stage {
     void *blk = nullptr;              // one allocation, carved up (stage_alloc)
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
@@ -318,7 +320,7 @@ struct rfid_ctx {
     int64_t *d_off = nullptr;         // [B_plan x max_tags + 1]
     int *d_base = nullptr, *d_head = nullptr;
   } trk;
-  // ---- the five window-table stages: one [B_plan][rows] table of fixed-size records each (csrc/rfid_stage.hpp) ----
+  // ---- the six window-table stages: one [B_plan][rows] table of fixed-size records each (csrc/rfid_stage.hpp) ----
   struct Table : Stage {
     void *d_table = nullptr;          // [B_plan][rows] records of the stage's type
     template <typename R> R *table() const { return static_cast<R *>(d_table); }
@@ -340,12 +342,16 @@ struct rfid_ctx {
   // slots, commands (rfid_batch_plan_slots / _commands): live and die with the plan; need the pass's statistics only
   struct Slots : Table {} slt;
   struct Commands : Table {} cmd;
+  // retune (rfid_batch_plan_retune): lives and dies with the plan; needs the pass's statistics only
+  struct Retune : Table {
+    int blocks = 0;                   // ceil(rows / RET_ROWS)
+  } ret;
   // fine (rfid_batch_plan_fine): lives and dies with the tracks workspace
   struct Fine : Table {
     rfid_read_fine *d_packed = nullptr;     // [trk.cap]: aligned with the tracks
   } fin;
-  // What the per-call forms (rfid_repair_window, rfid_window_moments_of, rfid_commands_of, rfid_fine_window) upload, compute on
-  // and download from.  One buffer for the four: each synchronises c->stream before it returns, so no two of them ever have
+  // What the per-call forms (rfid_repair_window, rfid_window_moments_of, rfid_commands_of, rfid_fine_window, rfid_retune_window)
+  // upload, compute on and download from.  One buffer for the five: each synchronises c->stream before it returns, so no two of them ever have
   // work in flight on it, and grow() may free and reallocate it.
   DevBuf one;
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
@@ -405,6 +411,7 @@ const KnobEntry g_knob_table[] = {
   {"inventory_slots", "RFID_INVENTORY_SLOTS", &RfidKnobs::inventory_slots, 0, 1024},
   {"commands_rows", "RFID_COMMANDS_ROWS", &RfidKnobs::commands_rows, 0, CMD_ROWS},
   {"fine_wgs", "RFID_FINE_WGS", &RfidKnobs::fine_wgs, 0, 65536},
+  {"retune_wgs", "RFID_RETUNE_WGS", &RfidKnobs::retune_wgs, 0, 65536},
 };
 int clamp_int(long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 // the environment, once per context: values out of range are clamped, anything that is not a number is ignored
@@ -488,7 +495,7 @@ void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
 // `stage` and everything behind it no longer belong to the last pass
 void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
 
-// ---- what the inventory, tracks, quality, repair, slots, commands and fine stages share on the host ----
+// ---- what the inventory, tracks, quality, repair, slots, commands, fine and retune stages share on the host ----
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void stage_free(rfid_ctx::Stage &st) {
@@ -700,6 +707,7 @@ void free_plan(rfid_ctx *c) {
   free_inventory(c);
   table_free(c->slt);
   table_free(c->cmd);
+  table_free(c->ret);
   invalidate_from(c, rfid_ctx::CUR_STATS);
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
@@ -730,7 +738,7 @@ int join_tails(rfid_ctx *c) {
   return RFID_OK;
 }
 
-// ---- the five window-table stages (quality, repair, slots, commands, fine): what their plan, enqueue and get functions share ----
+// ---- the six window-table stages (quality, repair, slots, commands, fine, retune): what their plan, enqueue and get functions share ----
 // A stage's description: what its checks ask for and how its messages name it.
 struct TableStage {
   const char *name;      // as in rfid_batch_<name>
@@ -744,6 +752,7 @@ constexpr TableStage ST_REPAIR = {"repair", true, false, rfid_ctx::CUR_INVENTORY
 constexpr TableStage ST_SLOTS = {"slots", false, false, rfid_ctx::CUR_STATS, false, "windows"};
 constexpr TableStage ST_COMMANDS = {"commands", false, false, rfid_ctx::CUR_STATS, false, "windows"};
 constexpr TableStage ST_FINE = {"fine", true, true, rfid_ctx::CUR_TRACKS, true, "EPC windows"};
+constexpr TableStage ST_RETUNE = {"retune", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
 
 bool table_needs_met(const rfid_ctx *c, const TableStage &d) { return (!d.inv || c->inv.blk) && (!d.trk || c->trk.blk); }
 
@@ -1340,7 +1349,7 @@ int rfid_ctx_destroy(rfid_ctx *c) {
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);
   for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep,
-                               (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd, (rfid_ctx::Stage *)&c->fin})
+                               (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd, (rfid_ctx::Stage *)&c->fin, (rfid_ctx::Stage *)&c->ret})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
@@ -2255,6 +2264,66 @@ int rfid_fine_window(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_resu
   return one_window(c, "rfid_fine_window", gated, res, out, [c](const float2 *g, const rfid_decode_result *r, rfid_read_fine *o) {
     hipLaunchKernelGGL(fine_one_kernel, dim3(1), dim3(64), 0, c->stream, g, r, o);
   });
+}
+
+// ---- retune stage: CRC-failed EPC windows decoded again over the Gen2 BLF tolerance, behind the statistics of a pass (csrc/rfid_retune.hpp) ----
+int rfid_batch_plan_retune(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Retune &p = c->ret;
+  const int rows = (c->wmax + 1) / 2;      // EPC windows are every other window
+  const int r = table_plan(c, p, ST_RETUNE, rows,
+                           {{&p.d_table, sizeof(rfid_retune) * (size_t)rows * (size_t)c->B_plan},
+                            {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan}});
+  if (r) return r;
+  p.blocks = (rows + RET_ROWS - 1) / RET_ROWS;
+  return RFID_OK;
+}
+
+int rfid_batch_retune(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Retune &p = c->ret;
+  int n = 0;
+  RetArgs a;
+  { int r = table_begin(c, p, ST_RETUNE, &n, &a.p); if (r) return r; }
+  a.rows = p.rows; a.blocks = p.blocks; a.table = p.table<rfid_retune>(); a.nrows = p.d_nrows;
+  // the span of a window reaches behind it, but never behind its trace: the lengths of the pass (as its gate scan had them)
+  a.lens = c->d_lens; a.n_dec = c->last_n_raw / DECIM;
+  // single-wave workgroups, each walking blocks of eight rows (16.5 KB of LDS each)
+  const int64_t items = (int64_t)n * p.blocks;
+  const int64_t most = c->knobs.retune_wgs ? (int64_t)c->knobs.retune_wgs : (int64_t)c->n_cus * RET_WGS_PER_CU;
+  hipLaunchKernelGGL(retune_kernel, persistent_grid(items, most), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return table_end(c, p, n);
+}
+
+int rfid_batch_get_window_retunes(rfid_ctx *c, int stream, rfid_retune *out, int64_t cap, int64_t *n) {
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->ret, ST_RETUNE, "rfid_batch_get_window_retunes", sizeof(*out), stream, out, cap, n);
+}
+
+int rfid_batch_retune_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  return stage_ms(c, c->ret, ms);
+}
+
+// the per-call form: one span in host memory through the batch kernel's device functions (one launch, synchronising)
+int rfid_retune_window(rfid_ctx *c, const rfid_cf32 *span, int n, const rfid_decode_result *res, rfid_retune *out) {
+  if (!c || !span || !res || !out) return RFID_ERR_INVALID;
+  if (n < EPC_WIN || n > RET_SPAN) return failf(c, RFID_ERR_INVALID, "rfid_retune_window: a span holds %d to %d samples", EPC_WIN, RET_SPAN);
+  if (res->type != RFID_DECODE_EPC) return fail(c, RFID_ERR_INVALID, "rfid_retune_window: not the result of an EPC window");
+  if (res->index < 65 || res->index > 65 + N_SYNC - 1) return fail(c, RFID_ERR_INVALID, "rfid_retune_window: the result's index is no sync offset (65 .. 79)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_w = up256(sizeof(float2) * (size_t)RET_SPAN), sz_r = up256(sizeof(rfid_decode_result));
+  { int r = grow(c, c->one, sz_w + sz_r + sizeof(rfid_retune)); if (r) return r; }
+  char *b = (char *)c->one.p;
+  HIPCHK(c, hipMemcpyAsync(b, span, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(retune_one_kernel, dim3(1), dim3(64), 0, c->stream, (const float2 *)b, n, (const rfid_decode_result *)(b + sz_w),
+                     (rfid_retune *)(b + sz_w + sz_r));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
 }
 
 }  // extern "C"

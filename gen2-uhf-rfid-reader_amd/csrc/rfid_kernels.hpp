@@ -1829,6 +1829,37 @@ RFID_DEVICE int wave_first_argmax(float v, int nl, int lane, bool strict_from_ze
   return wv::ffs64(hit) & 63;
 }
 
+// ---- what every decoder of an EPC frame does alike once it has a half-bit period T, an index and h_est: one copy, used by the two
+//      decoder kernels below and by the stages that decide a frame again (csrc/rfid_retune.hpp) ----
+// where the two half-bit samples of decision j lie (tag_decoder_impl.cc:171-190); T2 = 2.0f * T
+RFID_DEVICE int epc_index_a(int j, float T2, float fidx) { return wv::f2i((float)j * T2 + fidx); }
+RFID_DEVICE int epc_index_b(int j, float T, float fidx) { return wv::f2i(((float)(j * 2) * T + T) + fidx); }
+// the sign of decision j from its two samples; nhim = -h_im (conj(h_est))
+RFID_DEVICE bool epc_decision(float2 p, float2 q, float hre, float nhim) {
+  return ((p.x - q.x) * hre - (p.y - q.y) * nhim) > 0.0f;
+}
+// the 128 frame bits from the signs of decisions lane (cur0) and lane + 64 (cur1): bit j = (sign j differs from sign j - 1), the sign
+// in front of the first one positive
+RFID_DEVICE void epc_sign_chain(bool cur0, bool cur1, uint64_t &b0, uint64_t &b1) {
+  const uint64_t c0 = wv::ballot(cur0), c1 = wv::ballot(cur1);
+  b0 = c0 ^ ((c0 << 1) | 1ull);
+  b1 = c1 ^ ((c1 << 1) | (c0 >> 63));
+}
+// check_crc (:401-445): CRC-16 over frame bits 0..111 against bits 112..127.  crc_lo / crc_hi: g_crc16.c[lane] / c[lane + 64] (0 from
+// lane 48 on), crc_k: g_crc16.k
+RFID_DEVICE bool epc_crc_holds(uint64_t b0, uint64_t b1, unsigned crc_lo, unsigned crc_hi, unsigned crc_k, int lane) {
+  unsigned x = 0;
+  if ((b0 >> lane) & 1ull) x ^= crc_lo;
+  if (lane < 48 && ((b1 >> lane) & 1ull)) x ^= crc_hi;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) x ^= wv::shfl_xor(x, off);
+  const unsigned crc = (~(x ^ crc_k)) & 0xFFFFu;
+  unsigned rcvd = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) rcvd |= (unsigned)((b1 >> (48 + i)) & 1ull) << (15 - i);
+  return crc == rcvd;
+}
+
 RFID_KERNEL(64) void decode_windows_kernel(DecodeArgs a) {
   RFID_SHARED float2 s[EPC_WIN + 2];
   RFID_SHARED float m2[EPC_WIN + 2];
@@ -1897,36 +1928,15 @@ RFID_KERNEL(64) void decode_windows_kernel(DecodeArgs a) {
       r.T = T;
       // ---- 128 bit decisions (:171-190), lanes take j and j+64 ---------------------------
       const float T2 = 2.0f * T;
-      bool cur0, cur1;
-      {
-        const int j = lane;
-        const float2 p = s[wv::f2i((float)j * T2 + findex)];
-        const float2 q = s[wv::f2i(((float)(j * 2) * T + T) + findex)];
-        cur0 = ((p.x - q.x) * hre - (p.y - q.y) * nhim) > 0.0f;
-      }
-      {
-        const int j = lane + 64;
-        const float2 p = s[wv::f2i((float)j * T2 + findex)];
-        const float2 q = s[wv::f2i(((float)(j * 2) * T + T) + findex)];
-        cur1 = ((p.x - q.x) * hre - (p.y - q.y) * nhim) > 0.0f;
-      }
-      const uint64_t c0 = wv::ballot(cur0), c1 = wv::ballot(cur1);
-      const uint64_t b0 = c0 ^ ((c0 << 1) | 1ull);
-      const uint64_t b1 = c1 ^ ((c1 << 1) | (c0 >> 63));
+      const bool cur0 = epc_decision(s[epc_index_a(lane, T2, findex)], s[epc_index_b(lane, T, findex)], hre, nhim);
+      const bool cur1 = epc_decision(s[epc_index_a(lane + 64, T2, findex)], s[epc_index_b(lane + 64, T, findex)], hre, nhim);
+      uint64_t b0, b1;
+      epc_sign_chain(cur0, cur1, b0, b1);
       r.bits[0] = (uint32_t)b0; r.bits[1] = (uint32_t)(b0 >> 32);
       r.bits[2] = (uint32_t)b1; r.bits[3] = (uint32_t)(b1 >> 32);
       r.n_bits = 128;
       // ---- CRC-16 over frame bits 0..111 vs bits 112..127 (:401-445) ---------------------
-      unsigned x = 0;
-      if ((b0 >> lane) & 1ull) x ^= g_crc16.c[lane];
-      if (lane < 48 && ((b1 >> lane) & 1ull)) x ^= g_crc16.c[lane + 64];
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) x ^= wv::shfl_xor(x, off);
-      const unsigned crc = (~(x ^ g_crc16.k)) & 0xFFFFu;
-      unsigned rcvd = 0;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) rcvd |= (unsigned)((b1 >> (48 + i)) & 1ull) << (15 - i);
-      r.crc_ok = (crc == rcvd) ? 1 : 0;
+      r.crc_ok = epc_crc_holds(b0, b1, g_crc16.c[lane], (lane < 48) ? g_crc16.c[lane + 64] : 0u, g_crc16.k, lane) ? 1 : 0;
       if (r.crc_ok) {
         int id = 0;
 #pragma unroll
@@ -2152,30 +2162,21 @@ RFID_DEVICE void decode_epc3_body(const DecodeListArgs &a) {
       const float h_re = wv::readlane(hre, lead), h_im = wv::readlane(him, lead);
       const float nhim = -h_im, T2 = 2.0f * T;
       const int j0 = lane, j1 = lane + 64;
-      const float2 pa = cs[wv::f2i((float)j0 * T2 + fidx)];
-      const float2 qa = cs[wv::f2i(((float)(j0 * 2) * T + T) + fidx)];
-      const float2 pb = cs[wv::f2i((float)j1 * T2 + fidx)];
-      const float2 qb = cs[wv::f2i(((float)(j1 * 2) * T + T) + fidx)];
-      const bool cur0 = ((pa.x - qa.x) * h_re - (pa.y - qa.y) * nhim) > 0.0f;
-      const bool cur1 = ((pb.x - qb.x) * h_re - (pb.y - qb.y) * nhim) > 0.0f;
-      const uint64_t c0 = wv::ballot(cur0), c1 = wv::ballot(cur1);
-      const uint64_t b0 = c0 ^ ((c0 << 1) | 1ull);
-      const uint64_t b1 = c1 ^ ((c1 << 1) | (c0 >> 63));
-      unsigned x = 0;
-      if ((b0 >> lane) & 1ull) x ^= crc_lo;
-      if (lane < 48 && ((b1 >> lane) & 1ull)) x ^= crc_hi;
-#pragma unroll
-      for (int off = 32; off >= 1; off >>= 1) x ^= wv::shfl_xor(x, off);
-      const unsigned crc = (~(x ^ crc_k)) & 0xFFFFu;
-      unsigned rcvd = 0;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) rcvd |= (unsigned)((b1 >> (48 + i)) & 1ull) << (15 - i);
+      const float2 pa = cs[epc_index_a(j0, T2, fidx)];
+      const float2 qa = cs[epc_index_b(j0, T, fidx)];
+      const float2 pb = cs[epc_index_a(j1, T2, fidx)];
+      const float2 qb = cs[epc_index_b(j1, T, fidx)];
+      const bool cur0 = epc_decision(pa, qa, h_re, nhim);
+      const bool cur1 = epc_decision(pb, qb, h_re, nhim);
+      uint64_t b0, b1;
+      epc_sign_chain(cur0, cur1, b0, b1);
+      const bool crc_holds = epc_crc_holds(b0, b1, crc_lo, crc_hi, crc_k, lane);
       rfid_decode_result r;
       r.type = RFID_DECODE_EPC; r.index = wv::f2i(fidx); r.h_re = h_re; r.h_im = h_im; r.T = T;
       r.bits[0] = (uint32_t)b0; r.bits[1] = (uint32_t)(b0 >> 32);
       r.bits[2] = (uint32_t)b1; r.bits[3] = (uint32_t)(b1 >> 32);
       r.n_bits = 128;
-      r.crc_ok = (crc == rcvd) ? 1 : 0;
+      r.crc_ok = crc_holds ? 1 : 0;
       r.tag_id = -1;
       if (r.crc_ok) {
         int id = 0;

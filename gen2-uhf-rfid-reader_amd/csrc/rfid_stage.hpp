@@ -1,10 +1,10 @@
 // rfid_stage.hpp -- what the stages behind a batch pass decide in the same way, written once.  Every stage header includes
 // this file and, beside it, only the stage headers whose symbols it uses (the tracks: the inventory's table walk).
 //   stage_windows / stage_fetch   which windows of a trace count in a pass, how a result record is read and which records are
-//                                 reads (all seven stages / inventory and tracks);
+//                                 reads (all eight stages / inventory and tracks);
 //   scan_share / scan_partials    the one-workgroup offsets scan (inventory, tracks; the repair stage takes the shares);
-//   StagePass                     what a pass left, as the five window-table stages see it -- quality, repair, slots, commands,
-//                                 fine: each fills one [trace][row] table of fixed-size records with a persistent grid of single-wave
+//   StagePass                     what a pass left, as the six window-table stages see it -- quality, repair, slots, commands,
+//                                 fine, retune: each fills one [trace][row] table of fixed-size records with a persistent grid of single-wave
 //                                 workgroups, stage_windows gives the cut-off, rows behind it are zeroed, nrows[s] is written by
 //                                 the first pack.  How a table kernel loads, parks, sums and stores is its own (its header says why);
 //   epc_clamp / epc_gather        the decoder's half-bit gather of an EPC window (quality, repair, fine);
@@ -80,7 +80,7 @@ RFID_DEVICE int scan_partials(int *part, int tid, int nthr, int sum, int &total)
 }
 
 // ---- the window-table stages -----------------------------------------------------------------------------------------
-// What a pass left: the FIRST member of QualArgs, RepArgs, MomArgs, CmdArgs and FineArgs, filled by the host's table_begin.
+// What a pass left: the FIRST member of QualArgs, RepArgs, MomArgs, CmdArgs, FineArgs and RetArgs, filled by the host's table_begin.
 // (InvArgs and TrkArgs carry no y and another order: they stay their own.)
 struct StagePass {
   const float2 *y;                  // the matched filter's output of the pass
@@ -100,10 +100,10 @@ RFID_DEVICE int epc_clamp(int i) { return (i < 0) ? 0 : ((i > EPC_WIN - 1) ? (EP
 RFID_DEVICE void epc_gather(const float2 *src, float T, float fidx, int lane, float2 &pa, float2 &qa, float2 &pb, float2 &qb) {
   const float T2 = 2.0f * T;
   const int j0 = lane, j1 = lane + 64;
-  pa = src[epc_clamp(wv::f2i((float)j0 * T2 + fidx))];
-  qa = src[epc_clamp(wv::f2i(((float)(j0 * 2) * T + T) + fidx))];
-  pb = src[epc_clamp(wv::f2i((float)j1 * T2 + fidx))];
-  qb = src[epc_clamp(wv::f2i(((float)(j1 * 2) * T + T) + fidx))];
+  pa = src[epc_clamp(epc_index_a(j0, T2, fidx))];
+  qa = src[epc_clamp(epc_index_b(j0, T, fidx))];
+  pb = src[epc_clamp(epc_index_a(j1, T2, fidx))];
+  qb = src[epc_clamp(epc_index_b(j1, T, fidx))];
 }
 
 // ---- the records of the CRC-verified reads, aligned with the tracks: out[i] belongs to reads[i] --------------------------

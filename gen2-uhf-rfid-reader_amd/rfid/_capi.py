@@ -99,6 +99,10 @@ FINE_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("fl
                        ("pow", "<f4"), ("reserved_", "<i4"), ("seg_re", "<f4", (8,)), ("seg_im", "<f4", (8,)), ("seg_pow", "<f4", (8,))])
 FINE_SEGMENTS, FINE_SEGMENT_BITS = 8, 16
 assert FINE_DTYPE.itemsize == 128
+RETUNE_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("flags", "<i4"), ("t_index", "<i4"), ("T", "<f4"),
+                         ("h_re", "<f4"), ("h_im", "<f4"), ("energy", "<f4"), ("frame", "<u4", (4,)), ("reserved_", "<i4", (3,))])
+RETUNE_SPAN, RETUNE_CANDIDATES = 1408, 81
+assert RETUNE_DTYPE.itemsize == 64
 GATE_FSM_IN_DTYPE = np.dtype([("mode", "<i4"), ("n_samples", "<i4"), ("signal_state", "<i4"), ("num_pulses", "<i4"),
                               ("gate_open", "<i4"), ("n_to_ungate", "<i4"), ("wtype", "<i4"), ("nvalid", "<i4"), ("pos", "<i4"),
                               ("reserved_", "<i4"), ("below", "<u8"), ("above", "<u8")])
@@ -200,6 +204,11 @@ SIGNATURES = {
     "rfid_batch_get_window_fine": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_fine_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_fine_window": (_i, [_vp, _vp, _vp, _vp]),
+    "rfid_batch_plan_retune": (_i, [_vp]),
+    "rfid_batch_retune": (_i, [_vp]),
+    "rfid_batch_get_window_retunes": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_retune_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_retune_window": (_i, [_vp, _vp, _i, _vp, _vp]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

@@ -55,6 +55,8 @@ class BatchDecoder:
         self.last_commands = None     # one commands array per trace (every window before the cut-off) of the last decode(..., commands=True)
         self._fine_planned = False
         self.last_fine = None         # one record per read, aligned with last_tracks[0], of the last decode(..., fine=True)
+        self._ret_planned = False
+        self.last_retunes = None      # one retune array per trace (every EPC window before the cut-off) of the last decode(..., retune=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -72,6 +74,7 @@ class BatchDecoder:
             self._slots_planned = False
             self._cmd_planned = False
             self._fine_planned = False
+            self._ret_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -82,7 +85,8 @@ class BatchDecoder:
 
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
                inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False,
-               repair: bool = False, slots: bool = False, commands: bool = False, fine: bool = False):
+               repair: bool = False, slots: bool = False, commands: bool = False, fine: bool = False,
+               retune: bool = False):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
@@ -103,7 +107,11 @@ class BatchDecoder:
         timings).  fine=True (implies tracks=True): the data-aided channel estimate of every EPC window -- from all 256 half-bit
         samples of the frame instead of six of the preamble -- and of its eight 16-bit segments is worked out behind the
         tracks; `self.last_fine` keeps one capi.FINE_DTYPE record per read, aligned with the reads (fine_fields() turns them
-        into h, snr_db, the segments' h_k and the phase drift); a trace's whole row: `self.ctx.batch_window_fine(stream)`."""
+        into h, snr_db, the segments' h_k and the phase drift); a trace's whole row: `self.ctx.batch_window_fine(stream)`.
+        retune=True (implies nothing): the CRC-failed EPC windows are decoded again behind the pass with the half-bit period
+        searched over the whole +- 4 % Gen2 allows a tag's link frequency (the decoder searches +- 1 %); `self.last_retunes` keeps
+        one capi.RETUNE_DTYPE array per trace, a record per EPC window (retune_fields() turns it into the link frequency and its
+        offset); a retuned frame is not a read and changes nothing else."""
         torch = self._torch
         n = len(traces)
         lens = np.array([len(t) for t in traces], dtype=np.int64)
@@ -148,6 +156,9 @@ class BatchDecoder:
         if commands and not self._cmd_planned:
             self.ctx.batch_plan_commands()
             self._cmd_planned = True
+        if retune and not self._ret_planned:
+            self.ctx.batch_plan_retune()
+            self._ret_planned = True
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
         if inventory:
             self.ctx.batch_inventory_enqueue()
@@ -163,6 +174,8 @@ class BatchDecoder:
             self.ctx.batch_commands_enqueue()
         if fine:
             self.ctx.batch_fine_enqueue()
+        if retune:
+            self.ctx.batch_retune_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
@@ -179,6 +192,8 @@ class BatchDecoder:
             self.last_commands = [self.ctx.batch_window_commands(b) for b in range(n)]
         if fine:
             self.last_fine = self.ctx.batch_fine_fetch()
+        if retune:
+            self.last_retunes = [self.ctx.batch_window_retunes(b) for b in range(n)]
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -393,6 +408,66 @@ def format_repairs(repairs: np.ndarray, names: Sequence[str]) -> str:
     return "\n".join(lines) + "\n"
 
 
+RETUNES_HEADER = "file,epc,pc,seq,t_s,T,blf_khz,blf_off_pct,h_re,h_im,clamped,known"
+RETUNE_HALF_BIT = 5.0     # samples per half-bit at the nominal link frequency: 400 ksps / (2 x 40 kHz)
+
+
+def retune_fields(rows: np.ndarray) -> dict:
+    """rfid_retune records -> a dict of arrays, one value per record: retuned (flags bit 1: the frame decoded again passes the
+    CRC), clamped (bit 2), and in binary64 blf_khz = 200 / T, the tag's backscatter link frequency, and blf_off_pct =
+    100 (5 / T - 1), its offset from the nominal 40 kHz (nan for a window that was a read: nothing was searched)."""
+    rows = np.asarray(rows)
+    T = rows["T"].astype(np.float64)
+    searched = (rows["flags"] & 1) == 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        khz = np.where(searched, 400.0 / (2.0 * T), np.nan)
+        off = np.where(searched, 100.0 * (RETUNE_HALF_BIT / T - 1.0), np.nan)
+    return dict(retuned=(rows["flags"] & 2) != 0, clamped=(rows["flags"] & 4) != 0, blf_khz=khz, blf_off_pct=off)
+
+
+def retune_known(rows: np.ndarray, entries: np.ndarray) -> np.ndarray:
+    """Host side: per record of one trace's retune rows, whether it was retuned AND the trace's inventory (`entries`: its
+    capi.TAG_ENTRY_DTYPE records, Context.batch_inventory) holds the retuned frame."""
+    rows = np.asarray(rows)
+    have = {bytes(np.ascontiguousarray(f)) for f in np.asarray(entries)["frame"]} if len(entries) else set()
+    return np.array([bool(r["flags"] & 2) and bytes(np.ascontiguousarray(r["frame"])) in have for r in rows], dtype=bool)
+
+
+def format_retune(rows: np.ndarray, entries: np.ndarray) -> str:
+    """One line for one trace's EPC windows before the cut-off (Context.batch_window_retunes) and its inventory: how many failed
+    their CRC, how many of those pass when decoded again over the +- 4 % tolerance, how many distinct EPCs those are and how many of
+    them the inventory lacks -- tags the pass did not see at all -- and the median and the extremes of their link-frequency offset."""
+    rows = np.asarray(rows)
+    f = retune_fields(rows)
+    got = f["retuned"]
+    known = retune_known(rows, entries)
+    frames = {bytes(np.ascontiguousarray(r["frame"])) for r in rows[got]}
+    new = {bytes(np.ascontiguousarray(r["frame"])) for r in rows[got & ~known]}
+    off = f["blf_off_pct"][got]
+    stat = ("median : %+.2f %%  min : %+.2f %%  max : %+.2f %%" % (float(np.median(off)), float(off.min()), float(off.max()))) if len(off) else "median : -  min : -  max : -"
+    return ("| failed EPC windows : %d  retuned : %d  distinct EPCs : %d  not in the inventory : %d  BLF offset %s\n" %
+            (int(((rows["flags"] & 1) == 0).sum()), int(got.sum()), len(frames), len(new), stat))
+
+
+def format_retunes_csv(rows: Sequence[np.ndarray], entries: Sequence[np.ndarray], names: Sequence[str]) -> str:
+    """CSV text, one line per retuned window, by trace, then by seq: file,epc,pc,seq,t_s,T,blf_khz,blf_off_pct,h_re,h_im,clamped,
+    known.  rows[b]: the rfid_retune records of trace b; entries[b]: its inventory; names[b]: its file.  epc / pc of the RETUNED
+    frame, t_s = start / 400e3 as in the tracks CSV, T, h_re and h_im with %.9g (a binary32 value survives the round trip), known: 1
+    when the trace's inventory holds the frame."""
+    lines = [RETUNES_HEADER]
+    for rec, ent, name in zip(rows, entries, names):
+        rec = np.asarray(rec)
+        f = retune_fields(rec)
+        known = retune_known(rec, ent)
+        for k in np.flatnonzero(f["retuned"]):
+            r = rec[k]
+            pc, epc = frame_fields(r["frame"])
+            lines.append("%s,%s,%04x,%d,%.9g,%.9g,%.6f,%.4f,%.9g,%.9g,%d,%d" %
+                         (name, epc, pc, int(r["seq"]), int(r["start"]) / TRACKS_RATE, float(r["T"]), float(f["blf_khz"][k]),
+                          float(f["blf_off_pct"][k]), float(r["h_re"]), float(r["h_im"]), int(f["clamped"][k]), int(known[k])))
+    return "\n".join(lines) + "\n"
+
+
 MOMENTS_N = 240           # RFID_MOMENTS_SAMPLES: the samples of a window its moments are taken over
 SLOT_EMPTY, SLOT_SINGLE, SLOT_COLLIDED, SLOT_UNKNOWN = 0, 1, 2, -1
 SCHOUTE = 2.39            # Schoute's estimate of the tags behind a collided slot of a framed-ALOHA round
@@ -562,7 +637,7 @@ def format_commands_csv(rows: Sequence[np.ndarray], starts: Sequence[np.ndarray]
 
 
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -590,15 +665,21 @@ def main(argv=None) -> int:
                     help="the data-aided channel estimate of every EPC window, from all 256 half-bit samples of its frame (built on "
                          "the device); one line per file, and with --tracks the CSV gains the columns "
                          "hd_re,hd_im,hd_mag_db,hd_phase_rad,hd_snr_db,drift_rad_s")
+    ap.add_argument("--retune", metavar="OUT.csv", default=None,
+                    help="decode the CRC-failed EPC windows again with the half-bit period searched over the +- 4 %% Gen2 allows a "
+                         "tag's link frequency (built on the device): finds tags the decoder's +- 1 %% never reads; one line per "
+                         "file, the retuned windows to this CSV file; implies --inventory")
     args = ap.parse_args(argv)
-    if args.tracks or args.repair:
+    if args.tracks or args.repair or args.retune:
         args.inventory = True
     dec = BatchDecoder(device=args.device, fixed_q=args.fixed_q, max_num_queries=args.max_queries)
     try:
         timing = {}
         stats, windows, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
                                             tracks=bool(args.tracks), quality=args.quality, repair=bool(args.repair),
-                                            slots=bool(args.slots), commands=bool(args.commands), fine=args.fine)
+                                            slots=bool(args.slots), commands=bool(args.commands), fine=args.fine,
+                                            retune=bool(args.retune))
+        per_trace = lambda entries, counts: np.split(entries, np.cumsum(counts)[:-1]) if len(counts) else []
         for i, (path, row) in enumerate(zip(args.files, stats)):
             print(path)
             print(format_results(row), end="")
@@ -612,6 +693,8 @@ def main(argv=None) -> int:
                 print(format_commands(dec.last_commands[i]), end="")
             if args.fine:
                 print(format_fine(dec.ctx.batch_window_fine(i)), end="")
+            if args.retune:
+                print(format_retune(dec.last_retunes[i], per_trace(*dec.last_inventory)[i]), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
               (len(args.files), timing["raw_samples"] / 1e6, timing["total_s"], timing["h2d_s"], timing["gpu_s"]))
         if args.inventory:
@@ -636,6 +719,9 @@ def main(argv=None) -> int:
             starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
             with open(args.slots, "w") as f:
                 f.write(format_slots_csv([classify_slots(m) for m in dec.last_slots], starts, args.files))
+        if args.retune:
+            with open(args.retune, "w") as f:
+                f.write(format_retunes_csv(dec.last_retunes, per_trace(*dec.last_inventory), args.files))
         if args.commands:
             starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
             with open(args.commands, "w") as f:

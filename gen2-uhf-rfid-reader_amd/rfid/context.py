@@ -572,6 +572,39 @@ class Context:
         corrected).  -> one capi.FINE_DTYPE record, stream = seq = start = 0."""
         return self._one_window(self._lib.rfid_fine_window, capi.FINE_DTYPE, gated, result)
 
+    def batch_plan_retune(self) -> None:
+        """Reserves the retune workspace of the current plan (a new plan drops it; no other stage's plan call does, and it
+        needs none of them)."""
+        self._chk(self._lib.rfid_batch_plan_retune(self._h))
+
+    def batch_retune_enqueue(self) -> None:
+        """Asynchronous: the CRC-failed EPC windows of the last pass decoded again over the Gen2 BLF tolerance, behind its
+        statistics (rfid_batch_retune).  The pass's per-trace lengths must still be valid."""
+        self._chk(self._lib.rfid_batch_retune(self._h))
+
+    def batch_window_retunes(self, stream: int, extra: int = 0) -> np.ndarray:
+        """One trace's row of the retune table (synchronises): the capi.RETUNE_DTYPE record of EVERY EPC window before the
+        cut-off, in seq order (n_windows_used // 2 of them), of the last batch_retune_enqueue: flags bit 0 = the window was a
+        read (nothing searched), bit 1 = the frame decoded again passes the CRC, bit 2 = the search ran into the trace's end.
+        extra > 0: up to that many of the table's rows behind them as well (zeroed by the stage)."""
+        return self._window_rows(self._lib.rfid_batch_get_window_retunes, capi.RETUNE_DTYPE, stream, extra)
+
+    def batch_retune_ms(self) -> float:
+        return self._stage_ms(self._lib.rfid_batch_retune_ms)
+
+    def retune_window(self, span, result) -> np.ndarray:
+        """The retune search for ONE span in host memory (rfid_retune_window): span = 1370 .. 1408 DC-free samples from the
+        window's first on (indices behind the last one are held there), result = the window's capi.RESULT_DTYPE record (its
+        index is the sync).  -> one capi.RETUNE_DTYPE record, stream = seq = start = 0."""
+        span = np.ascontiguousarray(span, dtype=np.complex64)
+        if span.ndim != 1 or not 1370 <= len(span) <= capi.RETUNE_SPAN:
+            raise ValueError("a span has 1370 to %d samples" % capi.RETUNE_SPAN)
+        res = np.zeros(1, dtype=capi.RESULT_DTYPE)
+        res[0] = result
+        out = np.zeros(1, dtype=capi.RETUNE_DTYPE)
+        self._chk(self._lib.rfid_retune_window(self._h, span.ctypes.data, len(span), res.ctypes.data, out.ctypes.data))
+        return out[0]
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

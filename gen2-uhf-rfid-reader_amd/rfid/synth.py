@@ -172,7 +172,8 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
                sigma: float = 0.002, seed: int = 1, leak: complex = 1.0 * np.exp(0.7j),
                h: complex = 0.10 * np.exp(2.1j), corrupt_rounds: Sequence[int] = (),
                t1_us: float = T1_US, tail_us: int = 200, noise: bool = True,
-               t1_jitter_raw: int = 0, render: bool = True) -> Trace:
+               t1_jitter_raw: int = 0, render: bool = True,
+               blf_offsets: Optional[Sequence[float]] = None) -> Trace:
     """Build one RX trace of `n_rounds` inventory rounds with 2**fixed_q slots each.
 
     Each tag picks a slot uniformly per round; slots with exactly one tag carry an
@@ -184,7 +185,21 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
     `render=False` skips the numpy rendering (samples = None) and only returns the ground truth and the
     slot table (`.plan`) from which rfid_synth_gen2 builds the identical noise-free trace in HBM -- the
     way the large configurations (10 000 rounds x 16 slots = 17.5 GB) are generated.
+
+    `blf_offsets`: one relative offset d per tag of its half-bit period (Gen2 allows a tag's backscatter link frequency +- 4 % at
+    this link setting): every reply of that tag has half-bits of 25 (1 + d) raw samples, the level at raw sample n of a reply
+    being levels[floor(n / (25 (1 + d)))].  The random draws are the same with and without offsets; None or zeros give the
+    samples of a trace without them, byte for byte.  The slot table knows no offsets: with `render=False` they raise.
     """
+    if blf_offsets is None:
+        blf_offsets = [0.0] * len(tag_ids)
+    blf_offsets = [float(d) for d in blf_offsets]
+    if len(blf_offsets) != len(tag_ids):
+        raise ValueError("blf_offsets: one offset per tag")
+    if any(not -0.5 < d < 0.5 for d in blf_offsets):
+        raise ValueError("blf_offsets: relative offsets of the half-bit period, well inside +- 0.5")
+    if not render and any(blf_offsets):
+        raise ValueError("blf_offsets: the slot table of render=False holds no offsets")
     rng = np.random.default_rng(seed)
     n_slots = 1 << fixed_q
     tx_parts: List[np.ndarray] = []
@@ -225,7 +240,7 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
             for i_who, k in enumerate(who):
                 bits = rng.integers(0, 2, 16).tolist()
                 if render:
-                    events.append((reply_at, fm0_levels(bits), hs[k]))
+                    events.append((reply_at, fm0_levels(bits), hs[k], blf_offsets[k]))
                 rec["tag"][i_who] = k
                 rec["rn16"][i_who] = _pack16(bits)
                 rn = bits
@@ -248,7 +263,7 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
                 jit = int(rng.integers(-t1_jitter_raw, t1_jitter_raw + 1)) if t1_jitter_raw else 0
                 reply_at = t + t1_us + jit / 2.0
                 if render:
-                    events.append((reply_at, fm0_levels(frame), hs[k]))
+                    events.append((reply_at, fm0_levels(frame), hs[k], blf_offsets[k]))
                 rec["has_epc"] = 1
                 rec["epc_off_raw"] = int(round(reply_at * 2)) - 2 * t
                 rec["epc"] = _pack_frame(frame)
@@ -266,9 +281,14 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
 
     tx = np.repeat(np.concatenate(tx_parts), 2)     # 1 Msps -> 2 Msps
     x = (np.complex64(leak) * tx).astype(np.complex64)
-    for (start_us, levels, hk) in events:
+    for (start_us, levels, hk, off) in events:
         a = int(round(start_us * 2))
-        wave = np.repeat(levels, HALF_BIT_RAW)
+        if off == 0.0:
+            wave = np.repeat(levels, HALF_BIT_RAW)
+        else:
+            half = HALF_BIT_RAW * (1.0 + off)          # (binary64)
+            at = np.floor(np.arange(int(np.ceil(len(levels) * half))) / half).astype(np.int64)
+            wave = levels[at[at < len(levels)]]
         b = min(a + len(wave), len(x))
         x[a:b] += (np.complex64(hk) * wave[: b - a] * tx[a:b]).astype(np.complex64)
     if noise and sigma > 0:

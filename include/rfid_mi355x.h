@@ -239,6 +239,42 @@ typedef struct rfid_read_fine {      /* 128 bytes */
   float   seg_re[8], seg_im[8], seg_pow[8];
 } rfid_read_fine;
 
+/* what the retune stage (rfid_batch_retune, rfid_retune_window) finds for one EPC window whose CRC-16 failed: the frame decoded
+ * again with the half-bit period searched over the whole tolerance Gen2 allows a tag's backscatter link frequency at this link
+ * setting (DR = 8, TRcal = 200 us: 40 kHz +- 4 %, Gen2 table 6.9) -- 81 candidates over 5.0 +- 4 % samples, where the decoder
+ * searches 20 over +- 1 % (lib/tag_decoder_impl.cc:150-166).  A tag further off than that fails every CRC and is otherwise absent
+ * from everything a pass reports.  A retuned frame is NOT a read: nothing else the library reports changes.
+ * THE DEFINITION (the contract; binary32 throughout, every operation rounded by itself, no fused multiply-add, every sum in order
+ * from 0.0f), for an EPC window with seq < n_windows_used and crc_ok == 0:
+ *   span   s[i] = y[start + min(i, last)] - dc per component, 0 <= i < RFID_RETUNE_SPAN: the gate's output and what follows it --
+ *          a slow tag's frame ends up to 38 samples behind the window (the furthest index is 14 + 268 x 5.2 = 1407.6).  last: the
+ *          trace's own last matched-filter output relative to start; no sample behind it is read.  p[i] = s.x * s.x + s.y * s.y.
+ *   sync   the decoder's: m = rfid_decode_result::index - 65, in 0 .. 14.
+ *   grid   t = 0 .. 80:  T_t = 4.8f + (float)t * ((5.2f - 4.8f) / 80.0f),  idx_t = (float)m + 13.0f * T_t   (at T = 5: m + 65)
+ *   energy[t] = sum over i = 0 .. 255 of p[(int)((float)i * T_t + idx_t)]     (the decoder's metric); t* = the first maximum
+ *   at T = T_t*, idx = idx_t*:
+ *     h    = the sum, left to right, of s[(int)((float)m + (float)j * T)], j = 0, 1, 3, 6, 10, 11 (the preamble's ones), each
+ *            component divided by 6.0f
+ *     bits = the decoder's 128 decisions (tag_decoder_impl.cc:171-190) on s with that h, T and idx: samples at
+ *            (int)((float)j * (2.0f * T) + idx) and (int)(((float)(2 j) * T + T) + idx), the same sign chain
+ *     the frame passes when the reference's check_crc (:401-445) accepts it
+ * A window with a non-finite sample: unspecified, as its decoding is. */
+#define RFID_RETUNE_SPAN 1408
+#define RFID_RETUNE_CANDIDATES 81
+typedef struct rfid_retune {         /* 64 bytes */
+  int32_t  stream, seq;              /* the EPC window (rfid_window::stream / seq) */
+  int32_t  start;                    /* rfid_window::start of that window */
+  int32_t  flags;                    /* bit 0: crc_ok of the window's result (then nothing is searched: every field below is 0);
+                                        bit 1: the frame decoded again passes the CRC; bit 2: an index the search used lay behind
+                                        the trace's (the span's) last sample and was held there */
+  int32_t  t_index;                  /* t* */
+  float    T;                        /* T_t* */
+  float    h_re, h_im;               /* h at T_t* */
+  float    energy;                   /* energy[t*] */
+  uint32_t frame[4];                 /* the bits decoded at T_t*, packed as rfid_decode_result::bits, whether they pass or not */
+  int32_t  reserved_[3];             /* 0 */
+} rfid_retune;
+
 /* the second-order moments of one window's gated samples: what the slots stage (rfid_batch_slots, rfid_window_moments_of)
  * works out for EVERY window before the TERMINATED cut-off, RN16 and EPC alike.  The reference ACKs every slot, so a
  * FIXED_Q > 0 trace yields an RN16 / EPC window pair per slot whatever was on the air; the moments tell an empty slot (an
@@ -828,6 +864,31 @@ RFID_API int rfid_batch_fine_ms(rfid_ctx *ctx, float *ms);
  * RFID_ERR_INVALID) -- or that result with bits a caller has corrected, from rfid_repair::frame for instance.  One launch of
  * the batch kernel's device functions, synchronising.  out: stream = seq = start = 0, flags bit 0 = res->crc_ok. */
 RFID_API int rfid_fine_window(rfid_ctx *ctx, const rfid_cf32 *gated, const rfid_decode_result *res, rfid_read_fine *out);
+/* ---- (2i) batch retune: CRC-failed EPC frames decoded again over the Gen2 BLF tolerance, built on the device ----------------- */
+/* Behind a pass: one rfid_retune (see its definition above) per EPC window with seq < n_windows_used in a device table
+ * [n_streams][ceil(wmax / 2)] (row = seq >> 1; the rows of a trace behind its cut-off are zeroed: the table's bytes repeat from
+ * pass to pass).  Nothing else a pass reports changes: a retuned frame is not a read.  rfid_batch_plan_retune reserves the table
+ * (64 bytes per possible EPC window).  RFID_ERR_STATE without a plan; RFID_ERR_HIP when the allocation fails (the plan and every
+ * other workspace stay usable).  A new rfid_batch_plan drops it; it neither needs nor drops any other stage's workspace, and their
+ * plan calls do not drop it. */
+RFID_API int rfid_batch_plan_retune(rfid_ctx *ctx);
+/* enqueues the retune stage of the LAST pass behind its statistics (asynchronous, no host synchronisation).  RFID_ERR_STATE: no
+ * retune workspace, or no pass with statistics yet.  It needs no inventory and may be enqueued before or behind the other stages:
+ * it neither needs nor changes their level.  It reads that pass's matched-filter output -- up to 38 samples behind a window, never
+ * behind the trace's own length: the lengths are the pass's (d_lens, which must still be valid, or n_raw) -- window table, results
+ * and statistics on the context's main stream and has rfid_batch_slots' duties there.  ONE table per plan, as rfid_batch_commands. */
+RFID_API int rfid_batch_retune(rfid_ctx *ctx);
+/* synchronises; one trace's row of the table: every EPC window before the cut-off in seq order, verified, retuned or not:
+ * *n = n_windows_used / 2.  cap as rfid_batch_get_window_quality.  RFID_ERR_STATE before the first rfid_batch_retune of this plan. */
+RFID_API int rfid_batch_get_window_retunes(rfid_ctx *ctx, int stream, rfid_retune *out, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_retune (HIP events) */
+RFID_API int rfid_batch_retune_ms(rfid_ctx *ctx, float *ms);
+/* the same search for ONE span in host memory: the per-call form.  span: n samples from the window's first on, DC-free already
+ * (dc = 0 in the definition), 1370 <= n <= RFID_RETUNE_SPAN (else RFID_ERR_INVALID): indices are held at n - 1 (flags bit 2); res:
+ * the result rfid_decoder_work gave for the window (type RFID_DECODE_EPC with index 65 .. 79, else RFID_ERR_INVALID).  One launch
+ * of the batch kernel's device functions, synchronising.  out: stream = seq = start = 0; flags bit 0 = res->crc_ok (then nothing
+ * is searched). */
+RFID_API int rfid_retune_window(rfid_ctx *ctx, const rfid_cf32 *span, int n, const rfid_decode_result *res, rfid_retune *out);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
