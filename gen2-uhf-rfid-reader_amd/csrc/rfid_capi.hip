@@ -570,6 +570,36 @@ dim3 persistent_grid(int64_t items, int64_t most) { return dim3((unsigned)(items
 // the gate scan's and the fused front end's: GATE_STREAMS_PER_WG traces per workgroup
 dim3 gate_grid(const rfid_ctx *c) { return dim3((unsigned)((c->B + GATE_STREAMS_PER_WG - 1) / GATE_STREAMS_PER_WG)); }
 
+// ---- the launches of the inventory and of the tracks, with the rule that picks a kernel's instantiation: one place for the batch
+// calls (waves = 1, or INV_MAX_WAVES for wide_traces) and for the test entry rfid_selftest_inventory ----
+// the table: 128 slots in LDS, or 1024
+int launch_inventory(rfid_ctx *c, const InvArgs &a, const InvPackArgs &p, int waves) {
+  const dim3 block(64 * (unsigned)waves);
+  if (a.slots <= 128) hipLaunchKernelGGL(inventory_kernel<128>, dim3((unsigned)a.n_streams), block, 0, c->stream, a);
+  else hipLaunchKernelGGL(inventory_kernel<1024>, dim3((unsigned)a.n_streams), block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(inventory_offsets_kernel, dim3(1), scan_block(a.n_streams), 0, c->stream, p);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(inventory_pack_kernel, dim3((unsigned)a.n_streams), dim3(64), 0, c->stream, p);
+  HIPCHK(c, hipGetLastError());
+  return RFID_OK;
+}
+int launch_tracks(rfid_ctx *c, const TrkScanArgs &p, const TrkArgs &a, int waves) {
+  const int n = a.n_streams;
+  hipLaunchKernelGGL(tracks_offsets_kernel, dim3(1), scan_block(n), 0, c->stream, p);
+  HIPCHK(c, hipGetLastError());
+  // the small instantiation: a table of up to 128 slots and up to 64 entries per trace
+  const bool small = a.slots <= 128 && a.max_tags <= 64;
+  const bool wide = waves > 1;
+  const dim3 grid((unsigned)n), block(64 * (unsigned)waves);
+  if (small && !wide) hipLaunchKernelGGL((tracks_kernel<128, 64, 1>), grid, block, 0, c->stream, a);
+  else if (!wide) hipLaunchKernelGGL((tracks_kernel<1024, 512, 1>), grid, block, 0, c->stream, a);
+  else if (small) hipLaunchKernelGGL((tracks_kernel<128, 64, INV_MAX_WAVES>), grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((tracks_kernel<1024, 512, INV_MAX_WAVES>), grid, block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return RFID_OK;
+}
+
 // ---- the argument blocks of the batch front end: built here, a launch site sets only what it does differently ----
 // rows of raw samples whose float4 loads are aligned: an even stride from a 16-byte aligned base
 int rows_vec_ok(const void *d_raw, int64_t raw_stride) { return ((raw_stride & 1) == 0 && (((uintptr_t)d_raw) & 15) == 0) ? 1 : 0; }
@@ -1620,6 +1650,92 @@ int rfid_selftest_stats(rfid_ctx *c, const rfid_decode_result *res, const int32_
   return rc;
 }
 
+// the inventory's and the tracks' five launches by themselves on a caller-given result table (a test entry: the expected values
+// are the caller's).  launch_inventory / launch_tracks are the batch calls' own, and with them the choice of instantiation; the
+// statistics rows hold the caller's n_windows_used and nothing else, the window table the caller's starts.  Every output array is
+// copied to the device before the launches and back behind them: what comes back unchanged, the kernels left alone.
+int rfid_selftest_inventory(rfid_ctx *c, const rfid_decode_result *res, const int32_t *wcount, const int32_t *n_windows_used,
+                            const int32_t *start, int n_streams, int wmax, int waves, int max_tags, int slots, int64_t reads_cap,
+                            int64_t reads_len, rfid_tag_entry *rows, int32_t *counts, int32_t *overflow, int32_t *head,
+                            int32_t *ent_off, rfid_tag_entry *packed, int32_t *base, int32_t *reads_head, int64_t *offsets,
+                            rfid_tag_read *reads) {
+  if (!c || !res || !wcount || !n_windows_used || !start || !rows || !counts || !overflow || !head || !ent_off || !packed || !base ||
+      !reads_head || !offsets || !reads || n_streams <= 0 || wmax <= 0 || (waves != 1 && waves != INV_MAX_WAVES) || max_tags < 1 ||
+      reads_cap < 0 || reads_len < reads_cap || reads_len < 1)
+    return RFID_ERR_INVALID;
+  if (slots < 2 || slots > 1024 || (slots & (slots - 1))) return fail(c, RFID_ERR_INVALID, "rfid_selftest_inventory: slots is not a power of two in 2..1024");
+  if (max_tags > 512) return fail(c, RFID_ERR_UNSUPPORTED, "rfid_selftest_inventory: at most 512 tags per trace");
+  if ((int64_t)n_streams * wmax > 0x7fffffffLL || (int64_t)max_tags * n_streams > 0x7fffffffLL / (int64_t)sizeof(rfid_tag_entry) ||
+      reads_len > 0x7fffffffLL)
+    return RFID_ERR_UNSUPPORTED;
+  for (int s = 0; s < n_streams; ++s)
+    if (wcount[s] < 0 || wcount[s] > wmax) return RFID_ERR_INVALID;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n = (size_t)n_streams * (size_t)wmax, n_rows = (size_t)n_streams * (size_t)max_tags;
+  std::vector<rfid_window> wtab(n);
+  std::vector<rfid_stream_stats> stats((size_t)n_streams);
+  memset(stats.data(), 0, sizeof(rfid_stream_stats) * stats.size());
+  for (int s = 0; s < n_streams; ++s) {
+    stats[(size_t)s].n_windows = wcount[s];
+    stats[(size_t)s].n_windows_used = n_windows_used[s];
+    for (int k = 0; k < wmax; ++k) {
+      rfid_window &w = wtab[(size_t)s * (size_t)wmax + (size_t)k];
+      w.stream = s; w.seq = k; w.start = start[(size_t)s * (size_t)wmax + (size_t)k]; w.type = k & 1; w.dc_re = 0.0f; w.dc_im = 0.0f;
+    }
+  }
+  // one block, carved up (256-byte aligned pieces, as a plan's): inputs, then the outputs in the order of the arguments
+  struct Piece { void **dev; const void *in; void *out; size_t bytes; };
+  rfid_decode_result *d_res = nullptr; rfid_window *d_wtab = nullptr; int *d_wc = nullptr; rfid_stream_stats *d_stats = nullptr;
+  rfid_tag_entry *d_rows = nullptr, *d_packed = nullptr; rfid_tag_read *d_reads = nullptr; int64_t *d_offsets = nullptr;
+  int *d_counts = nullptr, *d_over = nullptr, *d_head = nullptr, *d_ent_off = nullptr, *d_base = nullptr, *d_reads_head = nullptr;
+  const size_t ib = sizeof(int) * (size_t)n_streams;
+  const Piece pieces[] = {
+      {(void **)&d_res, res, nullptr, sizeof(rfid_decode_result) * n}, {(void **)&d_wtab, wtab.data(), nullptr, sizeof(rfid_window) * n},
+      {(void **)&d_wc, wcount, nullptr, ib}, {(void **)&d_stats, stats.data(), nullptr, sizeof(rfid_stream_stats) * (size_t)n_streams},
+      {(void **)&d_rows, rows, rows, sizeof(rfid_tag_entry) * n_rows}, {(void **)&d_counts, counts, counts, ib},
+      {(void **)&d_over, overflow, overflow, ib}, {(void **)&d_head, head, head, 2 * sizeof(int)}, {(void **)&d_ent_off, ent_off, ent_off, ib},
+      {(void **)&d_packed, packed, packed, sizeof(rfid_tag_entry) * n_rows}, {(void **)&d_base, base, base, ib},
+      {(void **)&d_reads_head, reads_head, reads_head, sizeof(int)}, {(void **)&d_offsets, offsets, offsets, sizeof(int64_t) * (n_rows + 1)},
+      {(void **)&d_reads, reads, reads, sizeof(rfid_tag_read) * (size_t)reads_len}};
+  size_t total = 0;
+  for (const Piece &p : pieces) total += up256(p.bytes);
+  char *blk = nullptr;
+  HIPCHK(c, hipMalloc((void **)&blk, total));
+  int rc = RFID_OK;
+  auto step = [&](hipError_t e) { if (e != hipSuccess && rc == RFID_OK) { snprintf(c->err, sizeof(c->err), "selftest_inventory: %s", hipGetErrorString(e)); rc = RFID_ERR_HIP; } };
+  {
+    char *b = blk;
+    for (const Piece &p : pieces) {
+      *p.dev = b;
+      step(hipMemcpyAsync(b, p.in, p.bytes, hipMemcpyHostToDevice, c->stream));
+      b += up256(p.bytes);
+    }
+  }
+  if (rc == RFID_OK) {
+    InvArgs a;
+    a.res = d_res; a.wcount = d_wc; a.stats = d_stats; a.wmax = wmax; a.n_streams = n_streams;
+    a.max_tags = max_tags; a.slots = slots; a.out = d_rows; a.counts = d_counts; a.overflow = d_over;
+    InvPackArgs p;
+    p.in = d_rows; p.counts = d_counts; p.overflow = d_over; p.n_streams = n_streams; p.max_tags = max_tags;
+    p.offsets = d_ent_off; p.head = d_head; p.packed = d_packed;
+    TrkScanArgs sp;
+    sp.ent = d_rows; sp.counts = d_counts; sp.inv_head = d_head; sp.n_streams = n_streams; sp.max_tags = max_tags;
+    sp.base = d_base; sp.head = d_reads_head; sp.offsets = d_offsets;
+    TrkArgs t;
+    t.res = d_res; t.wtab = d_wtab; t.wcount = d_wc; t.stats = d_stats; t.wmax = wmax; t.n_streams = n_streams;
+    t.ent = d_rows; t.counts = d_counts; t.ent_off = d_ent_off; t.max_tags = max_tags; t.slots = slots;
+    t.base = d_base; t.out = d_reads; t.cap = reads_cap; t.offsets = d_offsets;
+    rc = launch_inventory(c, a, p, waves);
+    if (rc == RFID_OK) rc = launch_tracks(c, sp, t, waves);
+  }
+  if (rc == RFID_OK)
+    for (const Piece &p : pieces)
+      if (p.out) step(hipMemcpyAsync(p.out, *p.dev, p.bytes, hipMemcpyDeviceToHost, c->stream));
+  step(hipStreamSynchronize(c->stream));
+  (void)hipFree(blk);
+  return rc;
+}
+
 // ======================================================================================
 // (2) batched offline path
 // ======================================================================================
@@ -1880,14 +1996,7 @@ int rfid_batch_inventory(rfid_ctx *c) {
   p.in = v.d_ent; p.counts = v.d_counts; p.overflow = v.d_over; p.n_streams = c->B; p.max_tags = v.max_tags;
   p.offsets = v.d_off; p.head = v.d_head; p.packed = v.d_packed;
   { int r = stage_record(c, v, 0); if (r) return r; }
-  const dim3 block = trace_block(c);
-  if (v.slots <= 128) hipLaunchKernelGGL(inventory_kernel<128>, dim3((unsigned)c->B), block, 0, c->stream, a);
-  else hipLaunchKernelGGL(inventory_kernel<1024>, dim3((unsigned)c->B), block, 0, c->stream, a);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(inventory_offsets_kernel, dim3(1), scan_block(c->B), 0, c->stream, p);
-  HIPCHK(c, hipGetLastError());
-  hipLaunchKernelGGL(inventory_pack_kernel, dim3((unsigned)c->B), dim3(64), 0, c->stream, p);
-  HIPCHK(c, hipGetLastError());
+  { int r = launch_inventory(c, a, p, wide_traces(c) ? INV_MAX_WAVES : 1); if (r) return r; }
   { int r = stage_record(c, v, 1); if (r) return r; }
   v.enqueued = true;
   v.n_streams = c->B;
@@ -1952,17 +2061,7 @@ int rfid_batch_tracks(rfid_ctx *c) {
   a.ent = v.d_ent; a.counts = v.d_counts; a.ent_off = v.d_off; a.max_tags = v.max_tags; a.slots = v.slots;
   a.base = t.d_base; a.out = t.d_reads; a.cap = t.cap; a.offsets = t.d_off;
   { int r = stage_record(c, t, 0); if (r) return r; }
-  hipLaunchKernelGGL(tracks_offsets_kernel, dim3(1), scan_block(n), 0, c->stream, p);
-  HIPCHK(c, hipGetLastError());
-  // the small instantiation: a table of up to 128 slots and up to 64 entries per trace
-  const bool small = v.slots <= 128 && v.max_tags <= 64;
-  const bool wide = wide_traces(c);
-  const dim3 grid((unsigned)n), block = trace_block(c);
-  if (small && !wide) hipLaunchKernelGGL((tracks_kernel<128, 64, 1>), grid, block, 0, c->stream, a);
-  else if (!wide) hipLaunchKernelGGL((tracks_kernel<1024, 512, 1>), grid, block, 0, c->stream, a);
-  else if (small) hipLaunchKernelGGL((tracks_kernel<128, 64, INV_MAX_WAVES>), grid, block, 0, c->stream, a);
-  else hipLaunchKernelGGL((tracks_kernel<1024, 512, INV_MAX_WAVES>), grid, block, 0, c->stream, a);
-  HIPCHK(c, hipGetLastError());
+  { int r = launch_tracks(c, p, a, wide_traces(c) ? INV_MAX_WAVES : 1); if (r) return r; }
   { int r = stage_record(c, t, 1); if (r) return r; }
   t.enqueued = true;
   mark_current(c, rfid_ctx::CUR_TRACKS);

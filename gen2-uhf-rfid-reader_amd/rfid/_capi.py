@@ -114,6 +114,22 @@ assert GATE_FSM_IN_DTYPE.itemsize == 56 and GATE_FSM_OUT_DTYPE.itemsize == 64
 assert WINDOW_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 48
 assert SCORES_DTYPE.itemsize == 144 and STATS_DTYPE.itemsize == 1056
 
+# the output arrays of rfid_selftest_inventory, in the order of its arguments
+INVENTORY_SELFTEST_OUTPUTS = ("rows", "counts", "overflow", "head", "ent_off", "packed", "base", "reads_head", "offsets", "reads")
+
+
+def inventory_selftest_outputs(n_streams: int, max_tags: int, reads_len: int, prefill: int = 0) -> dict:
+    """the arrays rfid_selftest_inventory fills, every 32-bit word of them `prefill`"""
+    n_rows = max(0, n_streams * max_tags)
+
+    def arr(dtype, n, shape=None):
+        a = np.full(max(0, n) * np.dtype(dtype).itemsize // 4, prefill, dtype=np.int32).view(dtype)
+        return a if shape is None else a.reshape(shape)
+    return dict(rows=arr(TAG_ENTRY_DTYPE, n_rows, (n_streams, max(0, max_tags))), counts=arr(np.int32, n_streams), overflow=arr(np.int32, n_streams),
+                head=arr(np.int32, 2), ent_off=arr(np.int32, n_streams), packed=arr(TAG_ENTRY_DTYPE, n_rows), base=arr(np.int32, n_streams),
+                reads_head=arr(np.int32, 1), offsets=arr(np.int64, n_rows + 1), reads=arr(TAG_READ_DTYPE, reads_len))
+
+
 # every symbol include/rfid_mi355x.h declares: name -> (restype, argtypes)
 _vp, _i, _i64, _ip = C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int)
 SIGNATURES = {
@@ -127,6 +143,7 @@ SIGNATURES = {
     "rfid_selftest": (_i, [_vp, _ip]),
     "rfid_selftest_gate_fsm": (_i, [_vp, _vp, _i, _vp, _vp]),
     "rfid_selftest_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "rfid_selftest_inventory": (_i, [_vp] * 5 + [_i] * 5 + [_i64, _i64] + [_vp] * 10),
     "rfid_mf_work": (_i, [_vp, _vp, _i, _vp, _i, _ip]),
     "rfid_gate_work": (_i, [_vp, _vp, _i, _vp, _i, _ip, _ip]),
     "rfid_decoder_work": (_i, [_vp, _vp, _i, _vp, _i, _ip, _ip, _vp, _vp]),

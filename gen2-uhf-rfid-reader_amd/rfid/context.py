@@ -86,6 +86,25 @@ class Context:
                                                 int(number_unique_tags), st.ctypes.data))
         return st
 
+    def selftest_inventory(self, results, wcount, n_windows_used, start, waves: int, max_tags: int, slots: int, reads_cap: int,
+                           reads_len: Optional[int] = None, prefill: int = 0) -> dict:
+        """rfid_selftest_inventory: the inventory's and the tracks' kernels by themselves, in the batch calls' launch sequence, on a
+        [n_streams][wmax] table of RESULT_DTYPE records with its window counts, cut-offs and window starts; `waves` (1 or 16)
+        wavefronts per trace.  Every output array starts from `prefill` in every 32-bit word -> dict(rows, counts, overflow, head,
+        ent_off, packed, base, reads_head, offsets, reads) as the launches left them.  A test entry: nothing is judged here."""
+        res = np.ascontiguousarray(results, dtype=capi.RESULT_DTYPE)
+        n_streams, wmax = res.shape
+        wc = np.ascontiguousarray(wcount, dtype=np.int32)
+        used = np.ascontiguousarray(n_windows_used, dtype=np.int32)
+        st = np.ascontiguousarray(start, dtype=np.int32)
+        assert len(wc) == n_streams and len(used) == n_streams and st.shape == (n_streams, wmax)
+        out = capi.inventory_selftest_outputs(n_streams, int(max_tags), int(reads_cap if reads_len is None else reads_len), prefill)
+        self._chk(self._lib.rfid_selftest_inventory(self._h, res.ctypes.data, wc.ctypes.data, used.ctypes.data, st.ctypes.data, n_streams,
+                                                    wmax, int(waves), int(max_tags), int(slots), int(reads_cap),
+                                                    int(reads_cap if reads_len is None else reads_len),
+                                                    *[out[k].ctypes.data for k in capi.INVENTORY_SELFTEST_OUTPUTS]))
+        return out
+
     @property
     def stream_handle(self) -> int:
         return int(self._lib.rfid_ctx_stream(self._h) or 0)

@@ -421,7 +421,7 @@ RFID_API const char *rfid_strerror(int status);
 RFID_API const char *rfid_last_error(const rfid_ctx *ctx);
 RFID_API const char *rfid_version(void);
 /* RFID_MI355X_ABI of the library that was loaded: it changes whenever a struct of this header changes size or layout
- * (4: rfid_ls_report has 13 fields since round 3; 5: its last field is dc_finished since round 6; 6: rfid_repair and the repair stage; 7: rfid_window_moments and the slots stage; still 7 with rfid_command and the commands stage, which only add functions and one struct).  A caller built against another value must not pass structs. */
+ * (4: rfid_ls_report has 13 fields since round 3; 5: its last field is dc_finished since round 6; 6: rfid_repair and the repair stage; 7: rfid_window_moments and the slots stage; still 7 with rfid_command and the commands stage, which only add functions and one struct, and with the test entry rfid_selftest_inventory, a function).  A caller built against another value must not pass structs. */
 RFID_API int rfid_abi_version(void);
 /* device self-test of the wave-level primitives the kernels rely on (DPP wave shift,
  * IEEE division, double sqrt).  0 = all good, >0 = number of failing checks. */
@@ -440,6 +440,26 @@ RFID_API int rfid_selftest_gate_fsm(rfid_ctx *ctx, const rfid_gate_fsm_in *in, i
 RFID_API int rfid_selftest_stats(rfid_ctx *ctx, const rfid_decode_result *res, const int32_t *wcount, int n_streams, int wmax,
                                  int waves, int from_summaries, int max_slot_number, int max_num_queries,
                                  int number_unique_tags, rfid_stream_stats *out);
+/* test entry: the inventory's and the tracks' kernels by themselves on a caller-given result table res[n_streams][wmax] (host
+ * memory), in the launch sequence of rfid_batch_inventory + rfid_batch_tracks and with their choice of instantiation (a table of up
+ * to 128 slots or of 1024; rows of up to 64 entries or of 512): the inventory, its offsets, its packed copy, the tracks' offsets, the
+ * tracks.  wcount[s] (0 .. wmax) and n_windows_used[s] (any value) are what the statistics of a pass would hold for trace s: the
+ * records before the smaller of the two count.  start[n_streams][wmax]: rfid_window::start of every window (stream, seq and type =
+ * seq & 1 are filled in here).  waves: 1 or 16 wavefronts per trace -- the batch path launches 16 for wmax > 2048.  max_tags
+ * (1 .. 512) and slots (a power of two in 2 .. 1024) as rfid_batch_plan_inventory and the inventory_slots knob set them; unlike a
+ * plan's, slots may be smaller than 2 max_tags.  reads_cap: the capacity the tracks kernel is given; reads_len >= reads_cap (and
+ * >= 1): the records of `reads`.
+ * Outputs, every one copied to the device before the launches and back behind them, so that what the kernels leave alone comes back
+ * as the caller filled it: rows[n_streams][max_tags], counts[n_streams], overflow[n_streams], head[2] (entries in all; the first
+ * trace that overflowed, INT32_MAX when none did), ent_off[n_streams], packed[n_streams * max_tags], base[n_streams],
+ * reads_head[1], offsets[n_streams * max_tags + 1], reads[reads_len].  The caller holds the expected values
+ * (tests/inventory_ref.py, tests/tracks_ref.py); nothing is judged here.  RFID_ERR_INVALID / RFID_ERR_UNSUPPORTED for arguments
+ * outside these ranges, as the planning calls answer. */
+RFID_API int rfid_selftest_inventory(rfid_ctx *ctx, const rfid_decode_result *res, const int32_t *wcount,
+                                     const int32_t *n_windows_used, const int32_t *start, int n_streams, int wmax, int waves,
+                                     int max_tags, int slots, int64_t reads_cap, int64_t reads_len, rfid_tag_entry *rows,
+                                     int32_t *counts, int32_t *overflow, int32_t *head, int32_t *ent_off, rfid_tag_entry *packed,
+                                     int32_t *base, int32_t *reads_head, int64_t *offsets, rfid_tag_read *reads);
 
 /* ---- (1) streaming, host buffers: one call per reference work() ----------------------- */
 /* fir_filter_ccc(5,[1]*25): consumes all n_in samples, keeps the filter history and the decimation

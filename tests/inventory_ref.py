@@ -13,6 +13,31 @@ def pack_frames(bits: np.ndarray) -> np.ndarray:
     return (b << np.arange(32, dtype=np.uint64)).sum(axis=2).astype(np.uint32)
 
 
+# the fields of the oracle's dumps that expected() here and tests/tracks_ref.py's read
+TABLE_DUMP_DTYPE = np.dtype([("type", "<i4"), ("index", "<i4"), ("h_est", "<f4", (2,)), ("T", "<f4"), ("bits", "u1", (128,)),
+                             ("crc_ok", "<i4"), ("tag_id", "<i4")])
+NO_TRACE = 2 ** 31 - 1      # the head's second word when no trace overflowed
+
+
+def dumps_of_table(res: np.ndarray, wcount: int, n_windows_used: int) -> np.ndarray:
+    """one row of a result table (capi.RESULT_DTYPE records, crafted or the library's own) -> the dumps-shaped array expected()
+    takes: the records before min(wcount, n_windows_used), the bits unpacked from bits[4].  Fields are copied, floats bit for bit"""
+    nw = max(0, min(int(wcount), int(n_windows_used), len(res)))
+    r = res[:nw]
+    d = np.zeros(nw, dtype=TABLE_DUMP_DTYPE)
+    for f in ("type", "index", "T", "crc_ok", "tag_id"):
+        d[f] = r[f]
+    d["h_est"][:, 0], d["h_est"][:, 1] = r["h_re"], r["h_im"]
+    d["bits"] = ((r["bits"][:, :, None] >> np.arange(32, dtype=np.uint32)) & np.uint32(1)).reshape(nw, 128)
+    return d
+
+
+def fits(n_entries: int, max_tags: int, slots: int) -> bool:
+    """the limits the kernels have on top: a trace with more distinct frames than max_tags, or than the table has slots, lists
+    nothing (count 0, overflow 1, no reads)"""
+    return n_entries <= max_tags and n_entries <= slots
+
+
 def expected(dumps: np.ndarray, stream: int = 0) -> np.ndarray:
     """oracle dumps of one trace -> its rfid_tag_entry records, ordered by first_seq"""
     seq = np.flatnonzero((dumps["type"] == 1) & (dumps["crc_ok"] == 1))
@@ -21,7 +46,8 @@ def expected(dumps: np.ndarray, stream: int = 0) -> np.ndarray:
         return out
     frames = pack_frames(dumps["bits"][seq])
     h = np.ascontiguousarray(dumps["h_est"][seq]).astype(np.float32)
-    norm = h[:, 0] * h[:, 0] + h[:, 1] * h[:, 1]          # binary32: two products, one sum, each rounded
+    with np.errstate(over="ignore", under="ignore"):      # (crafted tables: norms that overflow to +inf or underflow to 0)
+        norm = h[:, 0] * h[:, 0] + h[:, 1] * h[:, 1]      # binary32: two products, one sum, each rounded
     assert norm.dtype == np.float32
     rows = []
     seen = {}

@@ -40,6 +40,36 @@ def expected_batch(results):
             np.concatenate(offs))
 
 
+def expected_tables(res, wcount, n_windows_used, start, max_tags: int, slots: int) -> dict:
+    """a crafted result table res[n][wmax] with its counts, cut-offs and window starts -> everything the inventory and the tracks
+    of that table must report, with the limits the kernels have on top (inv.fits): per-trace entries (`per`), counts, overflow,
+    head = [entries in all, the first overflowed trace or inv.NO_TRACE], the entries' offsets per trace, the packed entries, the
+    reads' bases per trace, the reads in all, the reads' offsets aligned with the packed entries (+ 1), the reads"""
+    n = len(res)
+    per, reads, offs = [], [], []
+    counts, over = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    base = np.zeros(n, dtype=np.int32)
+    total = 0
+    for s in range(n):
+        e, r, off = expected(inv.dumps_of_table(res[s], wcount[s], n_windows_used[s]), start[s], s)
+        if not inv.fits(len(e), max_tags, slots):
+            over[s] = 1
+            e, r, off = e[:0], r[:0], off[:1]
+        per.append(e)
+        counts[s] = len(e)
+        base[s] = total
+        reads.append(r)
+        offs.append(off[:-1] + total)
+        total += len(r)
+    cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dtype=dt)
+    first_over = np.flatnonzero(over)
+    return dict(per=per, counts=counts, overflow=over,
+                head=np.array([counts.sum(), first_over[0] if len(first_over) else inv.NO_TRACE], dtype=np.int32),
+                ent_off=(np.cumsum(counts) - counts).astype(np.int32), packed=cat(per, capi.TAG_ENTRY_DTYPE), base=base,
+                reads_head=np.array([total], dtype=np.int32),
+                offsets=np.concatenate(offs + [np.array([total], dtype=np.int64)]).astype(np.int64), reads=cat(reads, capi.TAG_READ_DTYPE))
+
+
 def assert_equal(got, got_off, want, want_off, what="") -> None:
     """exact: integers equal, floats by bit pattern, then the bytes of the whole arrays"""
     assert len(got) == len(want), (what, len(got), len(want))

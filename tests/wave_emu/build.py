@@ -15,6 +15,7 @@ def build(force: bool = False, fin_wpb: int = 16) -> str:
     out = VARIANTS[fin_wpb]
     srcs = [os.path.join(HERE, "emu_driver.cpp"), os.path.join(HERE, "rfid_device_env.h"),
             os.path.join(CSRC, "rfid_kernels.hpp"), os.path.join(CSRC, "rfid_ls2.hpp"), os.path.join(CSRC, "rfid_ls2_enqueue.hpp"),
+            os.path.join(CSRC, "rfid_stage.hpp"), os.path.join(CSRC, "rfid_inventory.hpp"), os.path.join(CSRC, "rfid_tracks.hpp"),
             os.path.join(CSRC, "rfid_host_math.h"),
             os.path.join(CSRC, "rfid_gen2_host.h"),
             os.path.join(ROOT, "include", "rfid_mi355x.h")]

@@ -292,6 +292,29 @@ def stats_selftest(results, wcount, waves, from_summaries, max_slot_number, max_
     return st
 
 
+def inventory_selftest(results, wcount, n_windows_used, start, waves, max_tags, slots, reads_cap, reads_len=None, prefill=0):
+    """The inventory's and the tracks' kernels as rfid_selftest_inventory launches them: a [n_streams][wmax] table of capi.RESULT_DTYPE
+    records with its window counts, cut-offs and window starts, `waves` (1 or 16) wavefronts per trace.  Every output array starts
+    from `prefill` in every 32-bit word -> dict(rows, counts, overflow, head, ent_off, packed, base, reads_head, offsets, reads)."""
+    res = np.ascontiguousarray(results, dtype=capi.RESULT_DTYPE)
+    n_streams, wmax = res.shape
+    wc = np.ascontiguousarray(wcount, dtype=np.int32)
+    used = np.ascontiguousarray(n_windows_used, dtype=np.int32)
+    st = np.ascontiguousarray(start, dtype=np.int32)
+    assert len(wc) == n_streams and len(used) == n_streams and st.shape == (n_streams, wmax)
+    reads_len = int(reads_cap if reads_len is None else reads_len)
+    assert reads_len >= reads_cap and reads_len >= 1
+    out = capi.inventory_selftest_outputs(n_streams, int(max_tags), reads_len, prefill)
+    rc = lib().emu_inventory_selftest(C.c_void_p(res.ctypes.data), C.c_void_p(wc.ctypes.data), C.c_void_p(used.ctypes.data),
+                                      C.c_void_p(st.ctypes.data), n_streams, wmax, int(waves), int(max_tags), int(slots), C.c_long(reads_cap),
+                                      *[C.c_void_p(out[k].ctypes.data) for k in capi.INVENTORY_SELFTEST_OUTPUTS])
+    if rc == EMU_DEADLOCK:
+        _raise_deadlock(lib(), "inventory_selftest")
+    assert rc != -2, "a 16-byte load of the inventory or the tracks kernel on an address that is no multiple of 16"
+    assert rc == 0, rc
+    return out
+
+
 def chain_scan(x, carry):
     """-> (chain, scan, clean): the exact 63-deep chain, chain_add_scan (or its fallback), and whether the scan applied."""
     x = np.ascontiguousarray(x, dtype=np.float32)

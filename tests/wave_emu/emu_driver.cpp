@@ -23,6 +23,7 @@
 #include <rfid_device_env.h>
 #include "rfid_host_math.h"
 #include "rfid_kernels.hpp"
+#include "rfid_tracks.hpp"   // (and through it rfid_inventory.hpp, rfid_stage.hpp)
 #include "rfid_gen2_host.h"
 #define LS2_DCB_SNAPS_N 2   // (a unit's gate openings go through LDS two at a time here: the in-between writes are exercised)
 #ifndef LS2_FIN_WPB       // (build.py builds both: 16 -- the finishing walk's waves of a trace share one workgroup by default, or two and
@@ -737,6 +738,60 @@ int emu_stats_selftest(const rfid_decode_result *res, const int *wcount, int n_s
   emu::launch(emu::Idx3{(unsigned)n_streams, 1, 1}, emu::Idx3{64 * (unsigned)waves, 1, 1}, [&]() { stream_stats_kernel(sa); });
   free(sum);
   return run.rc(emu::g_misaligned16 ? -2 : 0);      // (-2: a 16-byte load of the kernel was not 16-byte aligned)
+}
+
+// the inventory's and the tracks' kernels on a caller-given result table, as rfid_selftest_inventory launches them (launch_inventory /
+// launch_tracks of csrc/rfid_capi.hip: the same five launches, the same choice of instantiation, restated here because that file is
+// not part of this library).  The kernels write the caller's arrays themselves.  -1: an argument outside the entry's ranges; -2: a
+// 16-byte load of a kernel on an address that is no multiple of 16.
+int emu_inventory_selftest(const rfid_decode_result *res, const int *wcount, const int *n_windows_used, const int *start, int n_streams,
+                           int wmax, int waves, int max_tags, int slots, long reads_cap, rfid_tag_entry *rows, int *counts, int *overflow,
+                           int *head, int *ent_off, rfid_tag_entry *packed, int *base, int *reads_head, int64_t *offsets, rfid_tag_read *reads) {
+  EmuRun run;
+  if (n_streams <= 0 || wmax <= 0 || (waves != 1 && waves != INV_MAX_WAVES) || max_tags < 1 || max_tags > 512 || slots < 2 || slots > 1024 ||
+      (slots & (slots - 1)) || reads_cap < 0)
+    return -1;
+  for (int s = 0; s < n_streams; ++s)
+    if (wcount[s] < 0 || wcount[s] > wmax) return -1;
+  const size_t n = (size_t)n_streams * (size_t)wmax;
+  std::vector<rfid_window> wtab(n);
+  std::vector<rfid_stream_stats> stats((size_t)n_streams);
+  memset(stats.data(), 0, sizeof(rfid_stream_stats) * stats.size());
+  for (int s = 0; s < n_streams; ++s) {
+    stats[(size_t)s].n_windows = wcount[s];
+    stats[(size_t)s].n_windows_used = n_windows_used[s];
+    for (int k = 0; k < wmax; ++k) {
+      rfid_window &w = wtab[(size_t)s * (size_t)wmax + (size_t)k];
+      w.stream = s; w.seq = k; w.start = start[(size_t)s * (size_t)wmax + (size_t)k]; w.type = k & 1; w.dc_re = 0.0f; w.dc_im = 0.0f;
+    }
+  }
+  InvArgs a;
+  a.res = res; a.wcount = wcount; a.stats = stats.data(); a.wmax = wmax; a.n_streams = n_streams;
+  a.max_tags = max_tags; a.slots = slots; a.out = rows; a.counts = counts; a.overflow = overflow;
+  InvPackArgs p;
+  p.in = rows; p.counts = counts; p.overflow = overflow; p.n_streams = n_streams; p.max_tags = max_tags;
+  p.offsets = ent_off; p.head = head; p.packed = packed;
+  TrkScanArgs sp;
+  sp.ent = rows; sp.counts = counts; sp.inv_head = head; sp.n_streams = n_streams; sp.max_tags = max_tags;
+  sp.base = base; sp.head = reads_head; sp.offsets = offsets;
+  TrkArgs t;
+  t.res = res; t.wtab = wtab.data(); t.wcount = wcount; t.stats = stats.data(); t.wmax = wmax; t.n_streams = n_streams;
+  t.ent = rows; t.counts = counts; t.ent_off = ent_off; t.max_tags = max_tags; t.slots = slots;
+  t.base = base; t.out = reads; t.cap = reads_cap; t.offsets = offsets;
+  const emu::Idx3 grid{(unsigned)n_streams, 1, 1}, block{64 * (unsigned)waves, 1, 1};
+  const emu::Idx3 one{1, 1, 1}, scan{(unsigned)((n_streams >= INV_SCAN_THREADS) ? INV_SCAN_THREADS : ((n_streams + 63) & ~63)), 1, 1};
+  emu::g_misaligned16 = 0;
+  if (slots <= 128) emu::launch(grid, block, [&]() { inventory_kernel<128>(a); }, "inventory_kernel<128>");
+  else emu::launch(grid, block, [&]() { inventory_kernel<1024>(a); }, "inventory_kernel<1024>");
+  emu::launch(one, scan, [&]() { inventory_offsets_kernel(p); }, "inventory_offsets_kernel");
+  emu::launch(grid, emu::Idx3{64, 1, 1}, [&]() { inventory_pack_kernel(p); }, "inventory_pack_kernel");
+  emu::launch(one, scan, [&]() { tracks_offsets_kernel(sp); }, "tracks_offsets_kernel");
+  const bool small = slots <= 128 && max_tags <= 64, wide = waves > 1;
+  if (small && !wide) emu::launch(grid, block, [&]() { tracks_kernel<128, 64, 1>(t); }, "tracks_kernel<128, 64, 1>");
+  else if (!wide) emu::launch(grid, block, [&]() { tracks_kernel<1024, 512, 1>(t); }, "tracks_kernel<1024, 512, 1>");
+  else if (small) emu::launch(grid, block, [&]() { tracks_kernel<128, 64, INV_MAX_WAVES>(t); }, "tracks_kernel<128, 64, 16>");
+  else emu::launch(grid, block, [&]() { tracks_kernel<1024, 512, INV_MAX_WAVES>(t); }, "tracks_kernel<1024, 512, 16>");
+  return run.rc(emu::g_misaligned16 ? -2 : 0);
 }
 
 // in-order sum: the integer-scan form against the chain; scan_out[64] = 1 when the scan was provably exact
