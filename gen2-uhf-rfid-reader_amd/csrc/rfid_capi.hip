@@ -31,6 +31,7 @@
 #include "rfid_commands.hpp"
 #include "rfid_fine.hpp"
 #include "rfid_retune.hpp"
+#include "rfid_collide.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
 // the launch list of the long-stream front end, on the stream named by the enclosing scope's `ls2_stream`
@@ -84,6 +85,7 @@ struct RfidKnobs {
   int commands_rows = 0;   // RFID_COMMANDS_ROWS     1..16: rows per wave and step of the commands stage (0: one while the launch has a wave per row, then the next powers of two up to 16)
   int fine_wgs = 0;        // RFID_FINE_WGS          1..65536: most single-wave workgroups of the fine stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many packs
   int retune_wgs = 0;      // RFID_RETUNE_WGS        1..65536: most single-wave workgroups of the retune stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
+  int collide_wgs = 0;     // RFID_COLLIDE_WGS       1..65536: most single-wave workgroups of the collisions stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
 };
 
 // the timing events of a pass: stage i of the four took the time from event i to event i + 1
@@ -299,7 +301,7 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
-  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune.  What the eight share ----
+  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune, collisions.  What the nine share ----
   struct Stage {
     void *blk = nullptr;              // one allocation, carved up (stage_alloc)
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
@@ -320,7 +322,7 @@ struct rfid_ctx {
     int64_t *d_off = nullptr;         // [B_plan x max_tags + 1]
     int *d_base = nullptr, *d_head = nullptr;
   } trk;
-  // ---- the six window-table stages: one [B_plan][rows] table of fixed-size records each (csrc/rfid_stage.hpp) ----
+  // ---- the seven window-table stages: one [B_plan][rows] table of fixed-size records each (csrc/rfid_stage.hpp) ----
   struct Table : Stage {
     void *d_table = nullptr;          // [B_plan][rows] records of the stage's type
     template <typename R> R *table() const { return static_cast<R *>(d_table); }
@@ -346,12 +348,16 @@ struct rfid_ctx {
   struct Retune : Table {
     int blocks = 0;                   // ceil(rows / RET_ROWS)
   } ret;
+  // collisions (rfid_batch_plan_collisions): lives and dies with the plan; needs the pass's statistics only
+  struct Collisions : Table {
+    int blocks = 0;                   // ceil(rows / COL_ROWS)
+  } col;
   // fine (rfid_batch_plan_fine): lives and dies with the tracks workspace
   struct Fine : Table {
     rfid_read_fine *d_packed = nullptr;     // [trk.cap]: aligned with the tracks
   } fin;
-  // What the per-call forms (rfid_repair_window, rfid_window_moments_of, rfid_commands_of, rfid_fine_window, rfid_retune_window)
-  // upload, compute on and download from.  One buffer for the five: each synchronises c->stream before it returns, so no two of them ever have
+  // What the per-call forms (rfid_repair_window, rfid_window_moments_of, rfid_commands_of, rfid_fine_window, rfid_retune_window, rfid_collisions_of)
+  // upload, compute on and download from.  One buffer for the six: each synchronises c->stream before it returns, so no two of them ever have
   // work in flight on it, and grow() may free and reallocate it.
   DevBuf one;
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
@@ -412,6 +418,7 @@ const KnobEntry g_knob_table[] = {
   {"commands_rows", "RFID_COMMANDS_ROWS", &RfidKnobs::commands_rows, 0, CMD_ROWS},
   {"fine_wgs", "RFID_FINE_WGS", &RfidKnobs::fine_wgs, 0, 65536},
   {"retune_wgs", "RFID_RETUNE_WGS", &RfidKnobs::retune_wgs, 0, 65536},
+  {"collide_wgs", "RFID_COLLIDE_WGS", &RfidKnobs::collide_wgs, 0, 65536},
 };
 int clamp_int(long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 // the environment, once per context: values out of range are clamped, anything that is not a number is ignored
@@ -495,7 +502,7 @@ void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
 // `stage` and everything behind it no longer belong to the last pass
 void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
 
-// ---- what the inventory, tracks, quality, repair, slots, commands, fine and retune stages share on the host ----
+// ---- what the inventory, tracks, quality, repair, slots, commands, fine, retune and collisions stages share on the host ----
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void stage_free(rfid_ctx::Stage &st) {
@@ -738,6 +745,7 @@ void free_plan(rfid_ctx *c) {
   table_free(c->slt);
   table_free(c->cmd);
   table_free(c->ret);
+  table_free(c->col);
   invalidate_from(c, rfid_ctx::CUR_STATS);
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
@@ -768,7 +776,7 @@ int join_tails(rfid_ctx *c) {
   return RFID_OK;
 }
 
-// ---- the six window-table stages (quality, repair, slots, commands, fine, retune): what their plan, enqueue and get functions share ----
+// ---- the seven window-table stages (quality, repair, slots, commands, fine, retune, collisions): what their plan, enqueue and get functions share ----
 // A stage's description: what its checks ask for and how its messages name it.
 struct TableStage {
   const char *name;      // as in rfid_batch_<name>
@@ -783,6 +791,7 @@ constexpr TableStage ST_SLOTS = {"slots", false, false, rfid_ctx::CUR_STATS, fal
 constexpr TableStage ST_COMMANDS = {"commands", false, false, rfid_ctx::CUR_STATS, false, "windows"};
 constexpr TableStage ST_FINE = {"fine", true, true, rfid_ctx::CUR_TRACKS, true, "EPC windows"};
 constexpr TableStage ST_RETUNE = {"retune", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
+constexpr TableStage ST_COLLISIONS = {"collisions", false, false, rfid_ctx::CUR_STATS, false, "RN16 windows"};
 
 bool table_needs_met(const rfid_ctx *c, const TableStage &d) { return (!d.inv || c->inv.blk) && (!d.trk || c->trk.blk); }
 
@@ -1379,7 +1388,8 @@ int rfid_ctx_destroy(rfid_ctx *c) {
   for (hipEvent_t e : c->ev)
     if (e) (void)hipEventDestroy(e);
   for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep,
-                               (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd, (rfid_ctx::Stage *)&c->fin, (rfid_ctx::Stage *)&c->ret})
+                               (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd, (rfid_ctx::Stage *)&c->fin, (rfid_ctx::Stage *)&c->ret,
+                               (rfid_ctx::Stage *)&c->col})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
@@ -2421,6 +2431,70 @@ int rfid_retune_window(rfid_ctx *c, const rfid_cf32 *span, int n, const rfid_dec
                      (rfid_retune *)(b + sz_w + sz_r));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
+}
+
+// ---- collisions stage: both RN16s and both channels of a two-tag collided slot, behind the statistics of a pass (csrc/rfid_collide.hpp) ----
+int rfid_batch_plan_collisions(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Collisions &p = c->col;
+  const int rows = (c->wmax + 1) / 2;      // RN16 windows are every other window, the first among them
+  const int r = table_plan(c, p, ST_COLLISIONS, rows,
+                           {{&p.d_table, sizeof(rfid_collision) * (size_t)rows * (size_t)c->B_plan},
+                            {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan}});
+  if (r) return r;
+  p.blocks = (rows + COL_ROWS - 1) / COL_ROWS;
+  return RFID_OK;
+}
+
+int rfid_batch_collisions(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Collisions &p = c->col;
+  int n = 0;
+  ColArgs a;
+  { int r = table_begin(c, p, ST_COLLISIONS, &n, &a.p); if (r) return r; }
+  a.rows = p.rows; a.blocks = p.blocks; a.table = p.table<rfid_collision>(); a.nrows = p.d_nrows;
+  // single-wave workgroups, each walking blocks of sixteen rows (1.3 KB of LDS each)
+  const int64_t items = (int64_t)n * p.blocks;
+  const int64_t most = c->knobs.collide_wgs ? (int64_t)c->knobs.collide_wgs : (int64_t)c->n_cus * COL_WGS_PER_CU;
+  hipLaunchKernelGGL(collide_kernel, persistent_grid(items, most), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return table_end(c, p, n);
+}
+
+int rfid_batch_get_window_collisions(rfid_ctx *c, int stream, rfid_collision *out, int64_t cap, int64_t *n) {
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->col, ST_COLLISIONS, "rfid_batch_get_window_collisions", sizeof(*out), stream, out, cap, n);
+}
+
+int rfid_batch_collisions_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  return stage_ms(c, c->col, ms);
+}
+
+// the per-call form: windows and their results in host memory through the batch kernel's device function (one launch, synchronising)
+int rfid_collisions_of(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_result *results, int n_windows, rfid_collision *out) {
+  if (!c || n_windows < 0 || (n_windows > 0 && (!gated || !results || !out))) return RFID_ERR_INVALID;
+  if (n_windows == 0) return RFID_OK;
+  for (int k = 0; k < n_windows; ++k) {
+    if (results[k].type != RFID_DECODE_RN16)
+      return failf(c, RFID_ERR_INVALID, "rfid_collisions_of: result %d is not the result of an RN16 window", k);
+    if (results[k].index < 65 || results[k].index > 65 + N_SYNC - 1)
+      return failf(c, RFID_ERR_INVALID, "rfid_collisions_of: the index of result %d is no sync offset (65 .. 79)", k);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_w = up256(sizeof(float2) * (size_t)RN16_WIN * (size_t)n_windows),
+               sz_r = up256(sizeof(rfid_decode_result) * (size_t)n_windows), sz_out = sizeof(rfid_collision) * (size_t)n_windows;
+  { int r = grow(c, c->one, sz_w + sz_r + sz_out); if (r) return r; }
+  char *b = (char *)c->one.p;
+  HIPCHK(c, hipMemcpyAsync(b, gated, sizeof(float2) * (size_t)RN16_WIN * (size_t)n_windows, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_w, results, sizeof(rfid_decode_result) * (size_t)n_windows, hipMemcpyHostToDevice, c->stream));
+  // (the copies around it are what a call costs: two workgroups per compute unit will do)
+  hipLaunchKernelGGL(collide_one_kernel, persistent_grid(((int64_t)n_windows + COL_PACK - 1) / COL_PACK, (int64_t)c->n_cus * 2), dim3(64), 0,
+                     c->stream, (const float2 *)b, (const rfid_decode_result *)(b + sz_w), n_windows, (rfid_collision *)(b + sz_w + sz_r));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sz_out, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
 }

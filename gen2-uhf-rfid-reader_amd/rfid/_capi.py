@@ -103,6 +103,11 @@ RETUNE_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("
                          ("h_re", "<f4"), ("h_im", "<f4"), ("energy", "<f4"), ("frame", "<u4", (4,)), ("reserved_", "<i4", (3,))])
 RETUNE_SPAN, RETUNE_CANDIDATES = 1408, 81
 assert RETUNE_DTYPE.itemsize == 64
+COLLISION_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("flags", "<i4"), ("n_same", "<i4"), ("n_diff", "<i4"), ("rn16_a", "<i4"),
+                            ("rn16_b", "<i4"), ("ha_re", "<f4"), ("ha_im", "<f4"), ("hb_re", "<f4"), ("hb_im", "<f4"), ("resid", "<f4"),
+                            ("sum_sq", "<f4"), ("c_re", "<f4"), ("c_im", "<f4"), ("reserved_", "<i4")])
+RN16_WINDOW = 250         # the gated samples of an RN16 window
+assert COLLISION_DTYPE.itemsize == 64
 GATE_FSM_IN_DTYPE = np.dtype([("mode", "<i4"), ("n_samples", "<i4"), ("signal_state", "<i4"), ("num_pulses", "<i4"),
                               ("gate_open", "<i4"), ("n_to_ungate", "<i4"), ("wtype", "<i4"), ("nvalid", "<i4"), ("pos", "<i4"),
                               ("reserved_", "<i4"), ("below", "<u8"), ("above", "<u8")])
@@ -226,6 +231,11 @@ SIGNATURES = {
     "rfid_batch_get_window_retunes": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_retune_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_retune_window": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "rfid_batch_plan_collisions": (_i, [_vp]),
+    "rfid_batch_collisions": (_i, [_vp]),
+    "rfid_batch_get_window_collisions": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_collisions_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_collisions_of": (_i, [_vp, _vp, _vp, _i, _vp]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

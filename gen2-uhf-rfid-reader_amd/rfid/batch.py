@@ -57,6 +57,8 @@ class BatchDecoder:
         self.last_fine = None         # one record per read, aligned with last_tracks[0], of the last decode(..., fine=True)
         self._ret_planned = False
         self.last_retunes = None      # one retune array per trace (every EPC window before the cut-off) of the last decode(..., retune=True)
+        self._col_planned = False
+        self.last_collisions = None   # one collisions array per trace (every RN16 window before the cut-off) of the last decode(..., collisions=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -75,6 +77,7 @@ class BatchDecoder:
             self._cmd_planned = False
             self._fine_planned = False
             self._ret_planned = False
+            self._col_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -86,7 +89,7 @@ class BatchDecoder:
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
                inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False,
                repair: bool = False, slots: bool = False, commands: bool = False, fine: bool = False,
-               retune: bool = False):
+               retune: bool = False, collisions: bool = False):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
@@ -111,7 +114,10 @@ class BatchDecoder:
         retune=True (implies nothing): the CRC-failed EPC windows are decoded again behind the pass with the half-bit period
         searched over the whole +- 4 % Gen2 allows a tag's link frequency (the decoder searches +- 1 %); `self.last_retunes` keeps
         one capi.RETUNE_DTYPE array per trace, a record per EPC window (retune_fields() turns it into the link frequency and its
-        offset); a retuned frame is not a read and changes nothing else."""
+        offset); a retuned frame is not a read and changes nothing else.  collisions=True (implies slots=True: the report needs the
+        class): both RN16s and both channels of every RN16 window, as of two tags replying at once, are worked out behind the pass;
+        `self.last_collisions` keeps one capi.COLLISION_DTYPE array per trace, a record per RN16 window (classify_collisions() keeps
+        those of the collided slots and tells two tags from more); nothing else changes."""
         torch = self._torch
         n = len(traces)
         lens = np.array([len(t) for t in traces], dtype=np.int64)
@@ -130,6 +136,7 @@ class BatchDecoder:
             torch.cuda.current_stream().synchronize()
         t1 = time.perf_counter()
         tracks = tracks or quality or fine
+        slots = slots or collisions
         inventory = inventory or tracks or repair
         if inventory and self._inv_tags != int(max_tags):
             self.ctx.batch_plan_inventory(int(max_tags))
@@ -159,6 +166,9 @@ class BatchDecoder:
         if retune and not self._ret_planned:
             self.ctx.batch_plan_retune()
             self._ret_planned = True
+        if collisions and not self._col_planned:
+            self.ctx.batch_plan_collisions()
+            self._col_planned = True
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
         if inventory:
             self.ctx.batch_inventory_enqueue()
@@ -176,6 +186,8 @@ class BatchDecoder:
             self.ctx.batch_fine_enqueue()
         if retune:
             self.ctx.batch_retune_enqueue()
+        if collisions:
+            self.ctx.batch_collisions_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
@@ -194,6 +206,8 @@ class BatchDecoder:
             self.last_fine = self.ctx.batch_fine_fetch()
         if retune:
             self.last_retunes = [self.ctx.batch_window_retunes(b) for b in range(n)]
+        if collisions:
+            self.last_collisions = [self.ctx.batch_window_collisions(b) for b in range(n)]
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -567,6 +581,79 @@ def format_slots_csv(slots: Sequence[np.ndarray], starts: Sequence[np.ndarray], 
     return "\n".join(lines) + "\n"
 
 
+COLLISIONS_HEADER = "file,slot,seq,t_s,rn16_a,rn16_b,ha_re,ha_im,hb_re,hb_im,ratio_db,fit,order,decoded"
+COLLISION_ORDER_K = 0.0477        # fit above which a collided slot held three or more tags (classify_collisions)
+COLLISION_SLOT_DTYPE = np.dtype([("slot", "<i4"), ("seq", "<i4"), ("order", "<i4"), ("rn16_a", "<i4"), ("rn16_b", "<i4"),
+                                 ("ha", "<c16"), ("hb", "<c16"), ("ratio_db", "<f8"), ("fit", "<f8"), ("decoded", "U1")])
+
+
+def collision_fields(rows: np.ndarray) -> dict:
+    """rfid_collision records -> a dict of arrays, one value per record, in binary64: ha_db / hb_db = 20 log10 of |hA| / |hB| (the
+    stronger and the weaker tag, in the units of h_est), ratio_db = hb_db - ha_db (<= 0), phase_rad = arg(hB conj(hA)), fit =
+    resid / sum_sq (nan when sum_sq == 0): how much of the window's energy four points do NOT explain, and decoded: "a" when the
+    decoder's own RN16 is the stronger tag's, "b" when the weaker's (and not also the stronger's), "-" when neither's."""
+    rows = np.asarray(rows)
+    ha = rows["ha_re"].astype(np.float64) + 1j * rows["ha_im"].astype(np.float64)
+    hb = rows["hb_re"].astype(np.float64) + 1j * rows["hb_im"].astype(np.float64)
+    resid, sum_sq = rows["resid"].astype(np.float64), rows["sum_sq"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ha_db, hb_db = 20.0 * np.log10(np.abs(ha)), 20.0 * np.log10(np.abs(hb))
+        fit = np.where(sum_sq != 0.0, resid / sum_sq, np.nan)
+        ratio = hb_db - ha_db
+    decoded = np.where((rows["flags"] & 1) != 0, "a", np.where((rows["flags"] & 2) != 0, "b", "-"))
+    return dict(ha_db=ha_db, hb_db=hb_db, ratio_db=ratio, phase_rad=np.angle(hb * np.conj(ha)), fit=fit, decoded=decoded)
+
+
+def classify_collisions(rows: np.ndarray, slots: np.ndarray, order_k: float = COLLISION_ORDER_K) -> np.ndarray:
+    """One trace's collision rows (Context.batch_window_collisions: row k is the RN16 window of slot k) and its slots
+    (classify_slots of the same pass) -> one COLLISION_SLOT_DTYPE record per slot whose class is SLOT_COLLIDED: the two handles and
+    channels, their ratio, fit and decoded (collision_fields), and order = 2 when fit <= order_k (two tags: rn16_a and rn16_b are
+    theirs), else 3 -- three or more tags, which four points do not explain; the handles are then of no use.  On the reference's
+    records of the test traces (sigma = 0.03; the ragged batch and the crowded trace of tests/collide_suite.py and
+    tests/test_gpu_collide.py) the fit of two-tag slots stays at or below 0.0151 and that of slots with three or more tags at or
+    above 0.150: the default lies between them, at their geometric mean."""
+    rows, slots = np.asarray(rows), np.asarray(slots)
+    n = min(len(rows), len(slots))
+    pick = np.flatnonzero(slots["cls"][:n] == SLOT_COLLIDED)
+    out = np.zeros(len(pick), dtype=COLLISION_SLOT_DTYPE)
+    f = collision_fields(rows[pick])
+    out["slot"], out["seq"] = pick, rows["seq"][pick]
+    out["rn16_a"], out["rn16_b"] = rows["rn16_a"][pick], rows["rn16_b"][pick]
+    out["ha"] = rows["ha_re"][pick].astype(np.float64) + 1j * rows["ha_im"][pick].astype(np.float64)
+    out["hb"] = rows["hb_re"][pick].astype(np.float64) + 1j * rows["hb_im"][pick].astype(np.float64)
+    out["ratio_db"], out["fit"], out["decoded"] = f["ratio_db"], f["fit"], f["decoded"]
+    out["order"] = np.where(f["fit"] <= order_k, 2, 3)
+    return out
+
+
+def format_collisions(collided: np.ndarray) -> str:
+    """One line for one trace's collided slots (classify_collisions): how many there are, how many were resolved as two tags and how
+    many held more; among the resolved ones, whether the RN16 the decoder handed to the ACK was the stronger tag's, the weaker's
+    or neither's, and the median |hB| / |hA| in dB."""
+    collided = np.asarray(collided)
+    two = collided[collided["order"] == 2]
+    med = ("%.2f" % float(np.median(two["ratio_db"]))) if len(two) else "-"
+    return ("| collided slots : %d  two tags : %d  more : %d  decoder's RN16 the stronger tag's : %d  the weaker's : %d  neither's : %d  "
+            "median |hB|/|hA| dB : %s\n" %
+            (len(collided), len(two), len(collided) - len(two), int((two["decoded"] == "a").sum()), int((two["decoded"] == "b").sum()),
+             int((two["decoded"] == "-").sum()), med))
+
+
+def format_collisions_csv(collided: Sequence[np.ndarray], starts: Sequence[np.ndarray], names: Sequence[str]) -> str:
+    """CSV text, one line per collided slot, by trace, then by slot: file,slot,seq,t_s,rn16_a,rn16_b,ha_re,ha_im,hb_re,hb_im,
+    ratio_db,fit,order,decoded.  collided[b]: classify_collisions of trace b; starts[b][seq]: rfid_window::start of its windows;
+    names[b]: its file.  seq is the slot's RN16 window, t_s = start / 400e3 as in the tracks CSV, the handles four hex digits,
+    floats with %.9g (a binary32 value survives the round trip), order 2 or 3 (three or more), decoded a, b or -."""
+    lines = [COLLISIONS_HEADER]
+    for b, (rec, name) in enumerate(zip(collided, names)):
+        for r in rec:
+            lines.append("%s,%d,%d,%.9g,%04x,%04x,%.9g,%.9g,%.9g,%.9g,%.9g,%.9g,%d,%s" %
+                         (name, int(r["slot"]), int(r["seq"]), int(starts[b][int(r["seq"])]) / TRACKS_RATE, int(r["rn16_a"]),
+                          int(r["rn16_b"]), r["ha"].real, r["ha"].imag, r["hb"].real, r["hb"].imag, float(r["ratio_db"]),
+                          float(r["fit"]), int(r["order"]), str(r["decoded"])))
+    return "\n".join(lines) + "\n"
+
+
 COMMAND_NAMES = ("none", "query", "queryrep", "ack", "nak", "queryadjust", "unknown")   # by RFID_CMD_*
 SAMPLE_US = 2.5           # one sample behind the decimation of a 2 Msps trace (400 ksps)
 COMMAND_FIELDS_DTYPE = np.dtype([("seq", "<i4"), ("name", "U11"), ("q", "<i4"), ("rn16", "<i4"), ("crc5_ok", "<i4"), ("ack_echo", "<i4"),
@@ -637,7 +724,7 @@ def format_commands_csv(rows: Sequence[np.ndarray], starts: Sequence[np.ndarray]
 
 
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] [--collisions OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -669,6 +756,11 @@ def main(argv=None) -> int:
                     help="decode the CRC-failed EPC windows again with the half-bit period searched over the +- 4 %% Gen2 allows a "
                          "tag's link frequency (built on the device): finds tags the decoder's +- 1 %% never reads; one line per "
                          "file, the retuned windows to this CSV file; implies --inventory")
+    ap.add_argument("--collisions", metavar="OUT.csv", default=None,
+                    help="separate the two RN16s and the two channels of every collided slot (built on the device): which handles "
+                         "were on the air, how strong the two tags were, whether the decoder's RN16 was one of them, and whether "
+                         "more than two tags collided; one line per file, the collided slots to this CSV file; classifies the slots "
+                         "as --slots does, without its line and CSV")
     args = ap.parse_args(argv)
     if args.tracks or args.repair or args.retune:
         args.inventory = True
@@ -678,7 +770,9 @@ def main(argv=None) -> int:
         stats, windows, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
                                             tracks=bool(args.tracks), quality=args.quality, repair=bool(args.repair),
                                             slots=bool(args.slots), commands=bool(args.commands), fine=args.fine,
-                                            retune=bool(args.retune))
+                                            retune=bool(args.retune), collisions=bool(args.collisions))
+        collided = ([classify_collisions(c, classify_slots(m)) for c, m in zip(dec.last_collisions, dec.last_slots)]
+                    if args.collisions else None)
         per_trace = lambda entries, counts: np.split(entries, np.cumsum(counts)[:-1]) if len(counts) else []
         for i, (path, row) in enumerate(zip(args.files, stats)):
             print(path)
@@ -695,6 +789,8 @@ def main(argv=None) -> int:
                 print(format_fine(dec.ctx.batch_window_fine(i)), end="")
             if args.retune:
                 print(format_retune(dec.last_retunes[i], per_trace(*dec.last_inventory)[i]), end="")
+            if args.collisions:
+                print(format_collisions(collided[i]), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
               (len(args.files), timing["raw_samples"] / 1e6, timing["total_s"], timing["h2d_s"], timing["gpu_s"]))
         if args.inventory:
@@ -722,6 +818,10 @@ def main(argv=None) -> int:
         if args.retune:
             with open(args.retune, "w") as f:
                 f.write(format_retunes_csv(dec.last_retunes, per_trace(*dec.last_inventory), args.files))
+        if args.collisions:
+            starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
+            with open(args.collisions, "w") as f:
+                f.write(format_collisions_csv(collided, starts, args.files))
         if args.commands:
             starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
             with open(args.commands, "w") as f:

@@ -624,6 +624,42 @@ class Context:
         self._chk(self._lib.rfid_retune_window(self._h, span.ctypes.data, len(span), res.ctypes.data, out.ctypes.data))
         return out[0]
 
+    def batch_plan_collisions(self) -> None:
+        """Reserves the collisions workspace of the current plan (a new plan drops it; no other stage's plan call does, and it
+        needs none of them)."""
+        self._chk(self._lib.rfid_batch_plan_collisions(self._h))
+
+    def batch_collisions_enqueue(self) -> None:
+        """Asynchronous: both RN16s and both channels of every RN16 window of the last pass, as of a two-tag collision, behind
+        its statistics (rfid_batch_collisions)."""
+        self._chk(self._lib.rfid_batch_collisions(self._h))
+
+    def batch_window_collisions(self, stream: int, extra: int = 0) -> np.ndarray:
+        """One trace's row of the collisions table (synchronises): the capi.COLLISION_DTYPE record of EVERY RN16 window before
+        the cut-off, in seq order ((n_windows_used + 1) // 2 of them), of the last batch_collisions_enqueue: rn16_a / ha of the
+        stronger tag, rn16_b / hb of the weaker, flags bit 0 / 1 = the decoder's own RN16 is tag A's / tag B's, bit 2 = one
+        cluster only, bit 3 = the tags were swapped.  extra > 0: up to that many of the table's rows behind them as well (zeroed
+        by the stage)."""
+        return self._window_rows(self._lib.rfid_batch_get_window_collisions, capi.COLLISION_DTYPE, stream, extra)
+
+    def batch_collisions_ms(self) -> float:
+        return self._stage_ms(self._lib.rfid_batch_collisions_ms)
+
+    def collisions_of(self, windows, results) -> np.ndarray:
+        """The same records for RN16 windows in host memory (rfid_collisions_of): windows = [n][250] gated, DC-free samples,
+        results = their n capi.RESULT_DTYPE records (type RN16, index 65 .. 79).  -> capi.COLLISION_DTYPE records, stream = 0,
+        seq = the window's position."""
+        windows = np.ascontiguousarray(windows, dtype=np.complex64)
+        if windows.ndim == 1:
+            windows = windows.reshape(-1, capi.RN16_WINDOW) if len(windows) else windows.reshape(0, capi.RN16_WINDOW)
+        if windows.ndim != 2 or windows.shape[1] != capi.RN16_WINDOW:
+            raise ValueError("an RN16 window has 250 samples")
+        res = np.zeros(len(windows), dtype=capi.RESULT_DTYPE)
+        res[:] = np.atleast_1d(results)
+        out = np.zeros(len(windows), dtype=capi.COLLISION_DTYPE)
+        self._chk(self._lib.rfid_collisions_of(self._h, windows.ctypes.data, res.ctypes.data, len(windows), out.ctypes.data))
+        return out
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

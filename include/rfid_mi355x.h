@@ -275,6 +275,56 @@ typedef struct rfid_retune {         /* 64 bytes */
   int32_t  reserved_[3];             /* 0 */
 } rfid_retune;
 
+/* what the collisions stage (rfid_batch_collisions, rfid_collisions_of) works out for one RN16 window: the two RN16s and the two
+ * channels of a slot in which two tags replied at once.  The decoder is single-tag by construction (tag_detection_RN16,
+ * lib/tag_decoder_impl.cc:114-142, 237-253): decision j is the difference d_j of two adjacent half-bit samples across a bit
+ * boundary, and with two synchronous FM0 replies d_j = +-h1 +- h2 -- four points in the I/Q plane.  h1 + h2 is known: it is the
+ * decoder's h_est, both tags send the same preamble.  Squared, the d_j fall into two clusters, one around (h1 + h2)^2 and one around
+ * (h1 - h2)^2, 4 |h1| |h2| apart.  A record is worked out for EVERY RN16 window before the TERMINATED cut-off, whatever its slot
+ * held: which slots collided is the slots stage's to say (rfid.batch.classify_collisions puts the two together, on the host).
+ * THE DEFINITION (the contract; binary32 throughout, every operation rounded by itself, no fused multiply-add, every sum in order
+ * from 0.0f, every division the correctly rounded binary32 quotient), from the window's rfid_window (start, dc) and its own
+ * rfid_decode_result (index, hs = (h_re, h_im), bits[0]):
+ *   samples    m = min(max(index - 65, 0), 14);  z_i = y[start + m + 65 + 5 i] - dc per component, i = 0 .. 31: the decoder's 32
+ *              half-bit samples (the largest index is 234, inside the 250-sample window);  d_j = z_2j - z_2j+1 per component,
+ *              j = 0 .. 15; below (dx, dy) = d_j.
+ *   squares    sq(v) = (v.x * v.x - v.y * v.y, (2.0f * v.x) * v.y);  w_j = sq(d_j);  A = sq(hs);
+ *              dist(p, q) = (p.x - q.x) * (p.x - q.x) + (p.y - q.y) * (p.y - q.y)
+ *   clusters   two, the centre of one held at A.  The other starts at c = w_j*, j* the first j with the largest dist(w_j, A)
+ *              (j* = 0; j = 1 .. 15: taken when dist(w_j, A) > the largest so far).  Four rounds: j is a member iff
+ *              dist(w_j, c) < dist(w_j, A); with at least one member c becomes (sum of the members' w_j.x / (float)count, the
+ *              same of w_j.y), j ascending; with none c stays.  One more assignment with the c of the fourth round gives the members
+ *              that count below: n_diff of them, n_same = 16 - n_diff.
+ *   channels   hs' = the sum over the NON-members, j ascending, of +d_j when dx * hs.x + dy * hs.y > 0.0f and of -d_j otherwise, per
+ *              component, divided by (float)n_same; hs' = hs when n_same == 0.
+ *              hd  = the sum over the members, j ascending, of +d_j when dx * r.x + dy * r.y > 0.0f and of -d_j otherwise, r the d_j
+ *              of the member of lowest j, divided by (float)n_diff; hd = (0.0f, 0.0f) when n_diff == 0.
+ *   decisions  for every j the nearest, by dist(d_j, P), of P0 = hs' (alpha, beta = +, +), P1 = -hs' (-, -), P2 = hd (+, -) and
+ *              P3 = -hd (-, +): the first minimum in that order (P_k, k = 1 .. 3, is taken when its distance is < the smallest so
+ *              far).  resid = the sum of the 16 smallest distances, sum_sq = the sum of dx * dx + dy * dy, both j ascending.
+ *   handles    bit_j of the first tag = (alpha_j != alpha_j-1), alpha_-1 = + (the decoder's sign chain); its handle is the sum of
+ *              bit_j << (15 - j): MSB first as sent, the convention of rfid_command's RN16.  The second tag's likewise from beta.
+ *              dec = the decoder's own 16 bits in the same convention: the sum of ((bits[0] >> j) & 1) << (15 - j).
+ *   labels     h1 = (hs' + hd) / 2.0f, h2 = (hs' - hd) / 2.0f per component.  Tag A is the first tag and tag B the second, unless
+ *              h2.x * h2.x + h2.y * h2.y > h1.x * h1.x + h1.y * h1.y: then they swap, channels and handles both (flags bit 3).
+ *              A is the stronger tag.
+ * A record is a function of the input alone and is compared by bit pattern.  A window with a non-finite sample: unspecified.
+ * What a host makes of it (rfid.batch.collision_fields, in binary64): |hA|, |hB| and their ratio in dB, the phase between them,
+ * fit = resid / sum_sq -- small when four points explain the window, large when three or more tags replied -- and which of the two
+ * handles, if any, the decoder handed to the ACK. */
+typedef struct rfid_collision {      /* 64 bytes */
+  int32_t  stream, seq;              /* the RN16 window (rfid_window::stream / seq) */
+  int32_t  flags;                    /* bit 0: dec == rn16_a; bit 1: dec == rn16_b; bit 2: n_diff == 0 (one cluster: nothing to
+                                        separate); bit 3: the two tags were swapped */
+  int32_t  n_same, n_diff;           /* decisions around (h1 + h2)^2 / around (h1 - h2)^2 */
+  int32_t  rn16_a, rn16_b;           /* the handles of tag A and tag B, 0 .. 65535 */
+  float    ha_re, ha_im;             /* the channel of tag A, in the units of h_est */
+  float    hb_re, hb_im;             /* ... of tag B */
+  float    resid, sum_sq;
+  float    c_re, c_im;               /* c of the last assignment: the centre around (h1 - h2)^2 */
+  int32_t  reserved_;                /* 0 */
+} rfid_collision;
+
 /* the second-order moments of one window's gated samples: what the slots stage (rfid_batch_slots, rfid_window_moments_of)
  * works out for EVERY window before the TERMINATED cut-off, RN16 and EPC alike.  The reference ACKs every slot, so a
  * FIXED_Q > 0 trace yields an RN16 / EPC window pair per slot whatever was on the air; the moments tell an empty slot (an
@@ -909,6 +959,31 @@ RFID_API int rfid_batch_retune_ms(rfid_ctx *ctx, float *ms);
  * of the batch kernel's device functions, synchronising.  out: stream = seq = start = 0; flags bit 0 = res->crc_ok (then nothing
  * is searched). */
 RFID_API int rfid_retune_window(rfid_ctx *ctx, const rfid_cf32 *span, int n, const rfid_decode_result *res, rfid_retune *out);
+/* ---- (2j) batch collisions: both RN16s and both channels of a two-tag collided slot, built on the device ---------------------- */
+/* Behind a pass: one rfid_collision (see its definition above) per RN16 window with seq < n_windows_used in a device table
+ * [n_streams][ceil(wmax / 2)] (row = seq >> 1; the rows of a trace behind its cut-off are zeroed: the table's bytes repeat from
+ * pass to pass).  Nothing else a pass reports changes: what the reader ACKed stays what it ACKed.  rfid_batch_plan_collisions
+ * reserves the table (64 bytes per possible RN16 window).  RFID_ERR_STATE without a plan; RFID_ERR_HIP when the allocation fails
+ * (the plan and every other workspace stay usable).  A new rfid_batch_plan drops it; it neither needs nor drops any other stage's
+ * workspace, and their plan calls do not drop it. */
+RFID_API int rfid_batch_plan_collisions(rfid_ctx *ctx);
+/* enqueues the collisions stage of the LAST pass behind its statistics (asynchronous, no host synchronisation).  RFID_ERR_STATE:
+ * no collisions workspace, or no pass with statistics yet.  It needs no inventory and may be enqueued before or behind the other
+ * stages: it neither needs nor changes their level.  It reads that pass's matched-filter output, window table, results and
+ * statistics on the context's main stream and has rfid_batch_slots' duties there.  ONE table per plan, as rfid_batch_commands. */
+RFID_API int rfid_batch_collisions(rfid_ctx *ctx);
+/* synchronises; one trace's row of the table: every RN16 window before the cut-off in seq order:
+ * *n = (n_windows_used + 1) / 2.  cap as rfid_batch_get_window_quality.  RFID_ERR_STATE before the first rfid_batch_collisions of
+ * this plan. */
+RFID_API int rfid_batch_get_window_collisions(rfid_ctx *ctx, int stream, rfid_collision *out, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_collisions (HIP events) */
+RFID_API int rfid_batch_collisions_ms(rfid_ctx *ctx, float *ms);
+/* the same records for windows in host memory: the per-call form (as rfid_window_moments_of).  gated: n_windows x 250 gated,
+ * DC-free samples (dc = 0 in the definition); results[k]: the result rfid_decoder_work gave for window k (type RFID_DECODE_RN16
+ * with index 65 .. 79, else RFID_ERR_INVALID and nothing is launched).  One launch of the batch kernel's device functions,
+ * synchronising.  out[k]: stream = 0, seq = k. */
+RFID_API int rfid_collisions_of(rfid_ctx *ctx, const rfid_cf32 *gated, const rfid_decode_result *results, int n_windows,
+                                rfid_collision *out);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
