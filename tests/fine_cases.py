@@ -1,14 +1,83 @@
-"""What tests/test_fine_emu.py and tests/test_gpu_fine.py share: the crafted windows of the per-call form (rfid_fine_window) with the
-oracle's answers, and the checks on them.  Everything expected comes from tests/fine_ref.py, i.e. from the oracle alone."""
+"""What the fine stage's cases (tests/fine_suite.py, on both sides; tests/test_fine_emu.py and tests/test_gpu_fine.py, on one) are built
+from: their small inputs, with what the ORACLE alone says about them, the plan and the check that are the same wherever the records
+come from, and the crafted windows of the per-call form (rfid_fine_window) with the checks on them.  Everything expected comes from
+tests/fine_ref.py, i.e. from the oracle alone.
+
+The traces are FIXED_Q = 2, tags (0x27, 0x27, 0x31), sigma = 0.02: a third of the slots are empty or collided, and the reference ACKs
+every one of them.  4, 3, 2 and 3 inventory rounds: 16, 12, 8 and 12 EPC windows -- a trace's rows fill two packs of eight, one and a
+half, or one."""
 import numpy as np
 import pytest
 
 import decoder_windows as dw
 import fine_ref as ref
 import repair_ref
+from stage_backend import lay_out, oracle_pass
 
+TAGS = (0x27, 0x27, 0x31)
+SEEDS = ((104, 4), (112, 3), (120, 2), (128, 3))       # (seed, inventory rounds) per trace
 PHIS = (0.0, 0.3, 0.6)         # phase a frame gains over its 1370 samples
 SEG_SPAN = 1120.0              # samples between the centres of segments 0 and 7: 7 x 16 bits x 10 samples
+
+
+def ragged_batch(oracle_mod, synth_mod):
+    """-> (host, lens, L, stride, oracle Results, matched-filter outputs, (packed, rows)) of the four traces, the first cut short"""
+    ts = [synth_mod.make_trace(n_rounds=n, fixed_q=2, tag_ids=TAGS, seed=seed, sigma=0.02, t1_jitter_raw=3).samples for seed, n in SEEDS]
+    host, lens, L, stride = lay_out(ts, shorten=777)
+    refs, ys = oracle_pass(oracle_mod, host, lens, 2)
+    packed, rows = ref.expected_batch(refs, ys)
+    # the input does what the case is about, by the oracle alone: row counts that fill two packs, one and a half, and one; failed
+    # windows next to the reads in every trace
+    assert [len(r) for r in rows] == [16, 12, 8, 12], [len(r) for r in rows]
+    for b, r in enumerate(rows):
+        ok = r["flags"] == 1
+        assert len(r) == refs[b].n_windows // 2 and (~ok).sum() >= 1 and ok.sum() >= 2, (b, len(r), ok.sum())
+    assert len(packed) == sum(o.state.n_epc_correct for o in refs)
+    return host, lens, L, stride, refs, ys, (packed, rows)
+
+
+def corrupted_trace(oracle_mod, synth_mod):
+    """FIXED_Q = 0, one tag, five rounds, one bit of round 3's EPC frame flipped by the tag -> (host, lens, L, stride, (packed, [rows])):
+    by the oracle alone that window fails its CRC; five rows: less than a pack"""
+    x = synth_mod.make_trace(n_rounds=5, fixed_q=0, tag_ids=(0x27,), seed=7, sigma=0.02, corrupt_rounds=(3,)).samples
+    host, lens, L, stride = lay_out([x])
+    (o,), (y,) = oracle_pass(oracle_mod, host, lens, 0)
+    packed, rows = ref.expected(o, y, 0)
+    assert len(rows) == 5 and rows["flags"].tolist() == [1, 1, 0, 1, 1] and packed["seq"].tolist() == [1, 3, 7, 9]
+    # the corrupted frame is a cleanly modulated frame whose CRC is wrong: its decision-directed estimate is as good as a read's
+    h = ref.h_of(rows)
+    assert abs(abs(h[2]) / np.median(np.abs(h)) - 1.0) < 0.2 and np.ptp(np.angle(h * np.conj(h[0]))) < 0.1, h
+    return host, lens, L, stride, (packed, [rows])
+
+
+def first_traces(want, n):
+    """the expected records of the first n traces of a batch"""
+    return want[0][want[0]["stream"] < n], want[1][:n]
+
+
+def plan(ctx, n, L, max_tags=8):
+    ctx.batch_plan(n, L)
+    ctx.batch_plan_inventory(max_tags)
+    ctx.batch_plan_tracks()
+    ctx.batch_plan_fine()
+
+
+def enqueue(ctx):
+    ctx.batch_inventory_enqueue()
+    ctx.batch_tracks_enqueue()
+    ctx.batch_fine_enqueue()
+
+
+def check(ctx, want, what="", extra=3):
+    """inventory + tracks + fine of the last pass; the packed records (aligned with the tracks) and every trace's row against the
+    oracle's: check_rows -> all the bytes"""
+    enqueue(ctx)
+    ctx.batch_inventory_fetch()
+    reads, off = ctx.batch_tracks_fetch()
+    f = ctx.batch_fine_fetch()
+    assert np.array_equal(f["stream"], reads["stream"]) and np.array_equal(f["seq"], reads["seq"])
+    assert np.array_equal(f["start"], reads["start"])
+    return check_rows(ctx, want, what, extra)
 
 
 def rotated_frames(oracle_mod):

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 import slots_ref as ref
-from stage_backend import lay_out
+from stage_backend import lay_out, oracle_pass
 
 SIGMA = 0.01
 
@@ -21,8 +21,7 @@ def cut_behind(oracle_mod, x, fixed_q, keep):
 
 def oracle_of(oracle_mod, host, lens, fixed_q, **cfg):
     """-> (oracle Results, expected moments per trace)"""
-    refs = [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=fixed_q, **cfg)) for b in range(len(lens))]
-    ys = [oracle_mod.fir(host[b, : lens[b]]) for b in range(len(lens))]
+    refs, ys = oracle_pass(oracle_mod, host, lens, fixed_q, **cfg)
     return refs, ref.expected_batch(refs, ys)
 
 

@@ -20,6 +20,22 @@ def lay_out(traces, odd_stride=False, shorten=0):
     return host, lens, L, stride
 
 
+def carrier_between(host, lens, L):
+    """traces 0 and 1 of a laid-out batch with a pure-carrier trace of half the length between them (no window, no row, no read)
+    -> (host [3][stride], lens)"""
+    three = np.zeros((3, host.shape[1]), dtype=np.complex64)
+    three[0], three[2] = host[0], host[1]
+    three[1, : L // 2] = 0.8 + 0.1j
+    return three, np.array([lens[0], L // 2, lens[1]], dtype=np.int64)
+
+
+def oracle_pass(oracle_mod, host, lens, fixed_q, **cfg):
+    """-> (oracle Results, the oracle's matched-filter outputs) of the traces of a laid-out batch; cfg goes to oracle.config as it is"""
+    refs = [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=fixed_q, **cfg)) for b in range(len(lens))]
+    ys = [oracle_mod.fir(host[b, : lens[b]]) for b in range(len(lens))]
+    return refs, ys
+
+
 class Emulated:
     """host pointers: the stand-in runtime reads the arrays themselves"""
     name = "emulator"

@@ -1,7 +1,10 @@
 """The read-quality stage on the device (rfid_batch_plan_quality / rfid_batch_quality / rfid_batch_get_quality /
 rfid_batch_get_window_quality): SNR and decision margin of every EPC window of a pass.  Every expected record is worked out in numpy
 from the ORACLE alone (tests/quality_ref.py: oracle.fir, the oracle's openings, dc_est and per-window dumps); every comparison is
-exact -- integers equal, floats by bit pattern, then the bytes of the whole arrays.  The shapes are those of tests/test_gpu_tracks.py."""
+exact -- integers equal, floats by bit pattern, then the bytes of the whole arrays.  The cases that also run on the wave emulator are
+written once, in tests/quality_suite.py, and run here through stage_backend.Device: the smallest shapes at which the kernel can still go
+wrong -- a ragged batch, rows behind a cut-off, a plan larger than the batch, a trace without windows, the protocol.  Below them, what
+only the device runs, in the shapes of tests/test_gpu_tracks.py: eight traces, 1 024 replicas, one long trace and the command line."""
 import os
 import subprocess
 import sys
@@ -10,9 +13,11 @@ import numpy as np
 import pytest
 
 import stage_backend
-from stage_backend import lay_out
+from stage_backend import lay_out, oracle_pass
+import quality_cases as cases
 import quality_ref as ref
 import tracks_ref as tref
+from quality_suite import *
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -28,20 +33,6 @@ def backend():
     return stage_backend.Device()
 
 
-def _plan(ctx, n, L, max_tags):
-    ctx.batch_plan(n, L)
-    ctx.batch_plan_inventory(max_tags)
-    ctx.batch_plan_tracks()
-    ctx.batch_plan_quality()
-
-
-def _stages(ctx):
-    """inventory, tracks and quality of the last pass -> (reads, packed quality records)"""
-    ctx.batch_inventory()
-    reads, off = ctx.batch_tracks()
-    return reads, ctx.batch_quality()
-
-
 @pytest.mark.parametrize("mode", [0, 2], ids=["fused-front-end", "long-stream"])
 def test_ragged_batch_of_eight_traces(backend, oracle_mod, synth_mod, mode):
     """40 rounds, FIXED_Q = 3, six tags, sigma = 0.03; eight traces of different lengths.  The pass three times: byte-identical
@@ -50,9 +41,7 @@ def test_ragged_batch_of_eight_traces(backend, oracle_mod, synth_mod, mode):
     ts = [synth_mod.make_trace(n_rounds=40 - 3 * k, fixed_q=3, tag_ids=TAGS6, seed=900 + k, sigma=0.03, t1_jitter_raw=3).samples for k in range(8)]
     host, lens, L, stride = lay_out(ts)
     dev = backend.put(host, lens)
-    refs = [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=3, max_num_queries=BIG)) for b in range(8)]
-    ys = [oracle_mod.fir(host[b, : lens[b]]) for b in range(8)]
-    packed, rows = ref.expected_batch(refs, ys)
+    packed, rows = ref.expected_batch(*oracle_pass(oracle_mod, host, lens, 3, max_num_queries=BIG))
     # the input does what the case is about, by the oracle alone: every trace holds many failed windows next to its reads
     for b, r in enumerate(rows):
         ok = r["flags"] == 1
@@ -60,24 +49,14 @@ def test_ragged_batch_of_eight_traces(backend, oracle_mod, synth_mod, mode):
     ctx = rfid.Context(device=0, fixed_q=3, max_num_queries=BIG)
     try:
         ctx.batch_set_long_stream(mode)
-        _plan(ctx, 8, L, 16)
+        cases.plan(ctx, 8, L, 16)
         blobs = []
         for rep in range(3):
             backend.run_pass(ctx, dev, L, stride)
-            reads, q = _stages(ctx)
-            ref.assert_equal(q, packed, (mode, rep))
-            assert np.array_equal(q["stream"], reads["stream"]) and np.array_equal(q["seq"], reads["seq"])
-            st = ctx.batch_stats()
-            blob = q.tobytes()
-            for b in range(8):
-                r = ctx.batch_window_quality(b, extra=3)
-                assert len(r) == int(st[b]["n_windows_used"]) // 2 + 3 and not r[-3:].tobytes().strip(b"\0")
-                ref.assert_equal(r[:-3], rows[b], (mode, rep, b))
-                blob += r.tobytes()
-            blobs.append(blob)
+            blobs.append(cases.check(ctx, (packed, rows), (mode, rep)))
         assert blobs[0] == blobs[1] == blobs[2]
         print("quality of 8 traces: %.4f ms, %d reads, %d EPC windows; decode %.4f ms" %
-              (ctx.batch_quality_ms(), len(q), sum(map(len, rows)), ctx.batch_timing()["decode_ms"]))
+              (ctx.batch_quality_ms(), len(packed), sum(map(len, rows)), ctx.batch_timing()["decode_ms"]))
     finally:
         ctx.close()
 
@@ -106,11 +85,11 @@ def test_1024_replicas_one_failed_window_each(oracle_mod, synth_mod, overlap):
         ctx.synth_replicas_ptr(base.data_ptr(), L, data.data_ptr(), stride, B, 0.002, 777, first_replica=0)
         ctx.synth_replicas_ptr(base.data_ptr(), L, other.data_ptr(), stride, B, 0.004, 4242, first_replica=0)
         ctx.batch_sync()
-        _plan(ctx, B, L, 4)
+        cases.plan(ctx, B, L, 4)
         blobs = []
         for rep in range(3):
             ctx.batch_process_ptr(data.data_ptr(), stride, L, 0)
-            reads, q = _stages(ctx)
+            reads, q = cases.stages(ctx)
             blobs.append(q.tobytes())
         assert blobs[0] == blobs[1] == blobs[2]
         quality_ms, decode_ms = ctx.batch_quality_ms(), ctx.batch_timing()["decode_ms"]
@@ -145,7 +124,7 @@ def test_1024_replicas_one_failed_window_each(oracle_mod, synth_mod, overlap):
         ctx.batch_process_ptr(other.data_ptr(), stride, L, 0)
         assert ctx.batch_quality_fetch().tobytes() == blobs[0]
         assert ctx.batch_window_quality(B - 1).tobytes() == table[B - 1].tobytes()
-        reads2, q2 = _stages(ctx)                       # ... and the pass over the other samples gets its own
+        reads2, q2 = cases.stages(ctx)                       # ... and the pass over the other samples gets its own
         assert len(q2) == len(reads2) and q2.tobytes() != blobs[0]
         x = other[3, : 2 * L].cpu().numpy().view(np.complex64)
         o = oracle_mod.run_trace(x)
@@ -174,11 +153,11 @@ def test_one_long_trace(oracle_mod, synth_mod):
         torch.cuda.synchronize()
         ctx.synth_gen2_ptr(t.plan, data.data_ptr(), stride, sigma=0.002, seed=99)
         ctx.batch_sync()
-        _plan(ctx, 1, L, 64)
+        cases.plan(ctx, 1, L, 64)
         blobs = []
         for rep in range(3):
             ctx.batch_process_ptr(data.data_ptr(), stride, L, 0)
-            reads, q = _stages(ctx)
+            reads, q = cases.stages(ctx)
             rows = ctx.batch_window_quality(0)
             blobs.append(q.tobytes() + rows.tobytes())
         assert blobs[0] == blobs[1] == blobs[2]

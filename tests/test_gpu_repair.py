@@ -1,8 +1,11 @@
 """The repair stage on the device (rfid_batch_plan_repair / rfid_batch_repair / rfid_batch_get_repairs / rfid_batch_get_window_repairs
 and the per-call rfid_repair_window): CRC-failed EPC frames recovered from their weakest decisions.  Every expected record is worked
 out from the ORACLE alone (tests/repair_ref.py: the definition of include/rfid_mi355x.h run literally, the oracle's check_crc); every
-comparison is exact -- integers equal, floats by bit pattern, then the bytes of the whole arrays.  The traces are those of
-tests/test_repair_emu.py, at the sensitivity edge (sigma = 0.02, tag amplitude 0.014 .. 0.018)."""
+comparison is exact -- integers equal, floats by bit pattern, then the bytes of the whole arrays.  The cases that also run on the wave
+emulator are written once, in tests/repair_suite.py, and run here through stage_backend.Device: the smallest shapes at which the kernel
+can still go wrong -- single traces, a ragged batch with a trace without windows, rows behind a cut-off, crafted windows, the protocol.
+Below them, what only the device runs: eight traces, 1 024 replicas and the command line.  The traces are those of
+tests/repair_cases.py, at the sensitivity edge (sigma = 0.02, tag amplitude 0.014 .. 0.018)."""
 import os
 import subprocess
 import sys
@@ -11,9 +14,10 @@ import numpy as np
 import pytest
 
 import stage_backend
-from stage_backend import lay_out
+from stage_backend import lay_out, oracle_pass
+import repair_cases as cases
 import repair_ref as ref
-import repair_windows as rw
+from repair_suite import *
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -28,16 +32,9 @@ def backend():
 
 
 def _eight(synth_mod):
-    mk = lambda A, **kw: synth_mod.make_trace(sigma=0.02, t1_jitter_raw=3, h=A * np.exp(2.1j), **kw).samples
-    ts = [mk(0.016, fixed_q=0, tag_ids=(0x27,), seed=1, n_rounds=24), mk(0.014, fixed_q=0, tag_ids=(0x27,), seed=15, n_rounds=3),
-          mk(0.018, fixed_q=2, tag_ids=(0x27, 0x27, 0x31), seed=2, n_rounds=8)]
-    return ts + [mk(0.016, fixed_q=0, tag_ids=(0x27,), seed=3 + k, n_rounds=10 + 2 * k) for k in range(5)]
-
-
-def _plan(ctx, n, L, max_tags):
-    ctx.batch_plan(n, L)
-    ctx.batch_plan_inventory(max_tags)
-    ctx.batch_plan_repair()
+    """the edge trace, the lost tag, the mixed slots and five more seeds at A = 0.016"""
+    mk = lambda **kw: synth_mod.make_trace(sigma=0.02, t1_jitter_raw=3, h=0.016 * np.exp(2.1j), fixed_q=0, tag_ids=(0x27,), **kw).samples
+    return [cases.make(synth_mod, n) for n in ("edge", "lost", "mixed")] + [mk(seed=3 + k, n_rounds=10 + 2 * k) for k in range(5)]
 
 
 @pytest.mark.parametrize("mode", [0, 2], ids=["fused-front-end", "long-stream"])
@@ -47,49 +44,22 @@ def test_ragged_batch_of_eight_traces(backend, oracle_mod, synth_mod, mode):
     import rfid
     host, lens, L, stride = lay_out(_eight(synth_mod))
     dev = backend.put(host, lens)
-    refs = [oracle_mod.run_trace(host[b, : lens[b]], oracle_mod.config(fixed_q=2, max_num_queries=BIG)) for b in range(8)]
-    ys = [oracle_mod.fir(host[b, : lens[b]]) for b in range(8)]
-    packed, rows = ref.expected_batch(oracle_mod, refs, ys)
+    packed, rows = ref.expected_batch(oracle_mod, *oracle_pass(oracle_mod, host, lens, 2, max_num_queries=BIG))
     fixed = [int((r["n_flips"] > 0).sum()) for r in rows]
     assert fixed[:3] == [14, 3, 6] and min(fixed[3:]) >= 1 and (packed["entry"] >= 0).sum() >= 20 and (packed["entry"] < 0).sum() >= 6, fixed
     assert sorted(set(packed["n_flips"].tolist())) == [1, 2, 3]
     ctx = rfid.Context(device=0, fixed_q=2, max_num_queries=BIG)
     try:
         ctx.batch_set_long_stream(mode)
-        _plan(ctx, 8, L, 8)
+        cases.plan(ctx, 8, L, 8)
         blobs = []
         for rep in range(3):
             backend.run_pass(ctx, dev, L, stride)
-            ctx.batch_inventory_enqueue()
-            got = ctx.batch_repair()
-            ref.assert_equal(got, packed, (mode, rep))
-            st = ctx.batch_stats()
-            blob = got.tobytes()
-            for b in range(8):
-                r = ctx.batch_window_repairs(b, extra=3)
-                assert len(r) == int(st[b]["n_windows_used"]) // 2 + 3 and not r[-3:].tobytes().strip(b"\0")
-                ref.assert_equal(r[:-3], rows[b], (mode, rep, b))
-                blob += r.tobytes()
-            blobs.append(blob)
+            blobs.append(cases.check(ctx, (packed, rows), (mode, rep)))
         assert blobs[0] == blobs[1] == blobs[2]
         print("repair of 8 traces: %.4f ms, %d repaired of %d failed of %d EPC windows; decode %.4f ms" %
-              (ctx.batch_repair_ms(), len(got), sum(int(((r["flags"] & 1) == 0).sum()) for r in rows), sum(map(len, rows)),
+              (ctx.batch_repair_ms(), len(packed), sum(int(((r["flags"] & 1) == 0).sum()) for r in rows), sum(map(len, rows)),
                ctx.batch_timing()["decode_ms"]))
-    finally:
-        ctx.close()
-
-
-def test_crafted_windows_through_repair_window(oracle_mod):
-    """rfid_repair_window on the crafted windows of tests/repair_windows.py: ties at exactly 0, a lone wrong decision 127, two passing
-    sets of equal cost, four wrong decisions, wrong decisions behind weaker right ones, a frame that verifies"""
-    import rfid
-    sets = rw.build(oracle_mod)
-    rw.check(oracle_mod, sets)
-    assert "equal" in sets
-    ctx = rfid.Context(device=0)
-    try:
-        for name, (w, d, want, r, wrong) in sets.items():
-            ref.assert_equal(ctx.repair_window(w, ref.result_of_dump(d)), want, name)
     finally:
         ctx.close()
 
@@ -120,7 +90,7 @@ def test_1024_noise_replicas_of_the_edge_trace(oracle_mod, synth_mod, overlap):
         ctx.synth_replicas_ptr(base.data_ptr(), L, data.data_ptr(), stride, B, 0.02, 777, first_replica=0)
         ctx.synth_replicas_ptr(base.data_ptr(), L, other.data_ptr(), stride, B, 0.02, 4242, first_replica=0)
         ctx.batch_sync()
-        _plan(ctx, B, L, 4)
+        cases.plan(ctx, B, L, 4)
         blobs = []
         for rep in range(3):
             ctx.batch_process_ptr(data.data_ptr(), stride, L, 0)
