@@ -31,6 +31,7 @@
 #include "rfid_commands.hpp"
 #include "rfid_fine.hpp"
 #include "rfid_retune.hpp"
+#include "rfid_lengths.hpp"
 #include "rfid_collide.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
@@ -86,6 +87,7 @@ struct RfidKnobs {
   int fine_wgs = 0;        // RFID_FINE_WGS          1..65536: most single-wave workgroups of the fine stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many packs
   int retune_wgs = 0;      // RFID_RETUNE_WGS        1..65536: most single-wave workgroups of the retune stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
   int collide_wgs = 0;     // RFID_COLLIDE_WGS       1..65536: most single-wave workgroups of the collisions stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
+  int lengths_wgs = 0;     // RFID_LENGTHS_WGS       1..65536: most single-wave workgroups of the lengths stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
 };
 
 // the timing events of a pass: stage i of the four took the time from event i to event i + 1
@@ -301,7 +303,7 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
-  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune, collisions.  What the nine share ----
+  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths.  What the ten share ----
   struct Stage {
     void *blk = nullptr;              // one allocation, carved up (stage_alloc)
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
@@ -322,7 +324,7 @@ struct rfid_ctx {
     int64_t *d_off = nullptr;         // [B_plan x max_tags + 1]
     int *d_base = nullptr, *d_head = nullptr;
   } trk;
-  // ---- the seven window-table stages: one [B_plan][rows] table of fixed-size records each (csrc/rfid_stage.hpp) ----
+  // ---- the eight window-table stages: one [B_plan][rows] table of fixed-size records each (csrc/rfid_stage.hpp) ----
   struct Table : Stage {
     void *d_table = nullptr;          // [B_plan][rows] records of the stage's type
     template <typename R> R *table() const { return static_cast<R *>(d_table); }
@@ -352,12 +354,16 @@ struct rfid_ctx {
   struct Collisions : Table {
     int blocks = 0;                   // ceil(rows / COL_ROWS)
   } col;
+  // lengths (rfid_batch_plan_lengths): lives and dies with the plan; needs the pass's statistics only
+  struct Lengths : Table {
+    int blocks = 0;                   // ceil(rows / LEN_ROWS)
+  } len;
   // fine (rfid_batch_plan_fine): lives and dies with the tracks workspace
   struct Fine : Table {
     rfid_read_fine *d_packed = nullptr;     // [trk.cap]: aligned with the tracks
   } fin;
-  // What the per-call forms (rfid_repair_window, rfid_window_moments_of, rfid_commands_of, rfid_fine_window, rfid_retune_window, rfid_collisions_of)
-  // upload, compute on and download from.  One buffer for the six: each synchronises c->stream before it returns, so no two of them ever have
+  // What the per-call forms (rfid_repair_window, rfid_window_moments_of, rfid_commands_of, rfid_fine_window, rfid_retune_window, rfid_collisions_of,
+  // rfid_length_window) upload, compute on and download from.  One buffer for the seven: each synchronises c->stream before it returns, so no two of them ever have
   // work in flight on it, and grow() may free and reallocate it.
   DevBuf one;
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
@@ -419,6 +425,7 @@ const KnobEntry g_knob_table[] = {
   {"fine_wgs", "RFID_FINE_WGS", &RfidKnobs::fine_wgs, 0, 65536},
   {"retune_wgs", "RFID_RETUNE_WGS", &RfidKnobs::retune_wgs, 0, 65536},
   {"collide_wgs", "RFID_COLLIDE_WGS", &RfidKnobs::collide_wgs, 0, 65536},
+  {"lengths_wgs", "RFID_LENGTHS_WGS", &RfidKnobs::lengths_wgs, 0, 65536},
 };
 int clamp_int(long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 // the environment, once per context: values out of range are clamped, anything that is not a number is ignored
@@ -502,7 +509,7 @@ void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
 // `stage` and everything behind it no longer belong to the last pass
 void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
 
-// ---- what the inventory, tracks, quality, repair, slots, commands, fine, retune and collisions stages share on the host ----
+// ---- what the inventory, tracks, quality, repair, slots, commands, fine, retune, collisions and lengths stages share on the host ----
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void stage_free(rfid_ctx::Stage &st) {
@@ -746,6 +753,7 @@ void free_plan(rfid_ctx *c) {
   table_free(c->cmd);
   table_free(c->ret);
   table_free(c->col);
+  table_free(c->len);
   invalidate_from(c, rfid_ctx::CUR_STATS);
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
@@ -776,7 +784,7 @@ int join_tails(rfid_ctx *c) {
   return RFID_OK;
 }
 
-// ---- the seven window-table stages (quality, repair, slots, commands, fine, retune, collisions): what their plan, enqueue and get functions share ----
+// ---- the eight window-table stages (quality, repair, slots, commands, fine, retune, collisions, lengths): what their plan, enqueue and get functions share ----
 // A stage's description: what its checks ask for and how its messages name it.
 struct TableStage {
   const char *name;      // as in rfid_batch_<name>
@@ -792,6 +800,7 @@ constexpr TableStage ST_COMMANDS = {"commands", false, false, rfid_ctx::CUR_STAT
 constexpr TableStage ST_FINE = {"fine", true, true, rfid_ctx::CUR_TRACKS, true, "EPC windows"};
 constexpr TableStage ST_RETUNE = {"retune", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
 constexpr TableStage ST_COLLISIONS = {"collisions", false, false, rfid_ctx::CUR_STATS, false, "RN16 windows"};
+constexpr TableStage ST_LENGTHS = {"lengths", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
 
 bool table_needs_met(const rfid_ctx *c, const TableStage &d) { return (!d.inv || c->inv.blk) && (!d.trk || c->trk.blk); }
 
@@ -1389,7 +1398,7 @@ int rfid_ctx_destroy(rfid_ctx *c) {
     if (e) (void)hipEventDestroy(e);
   for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep,
                                (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd, (rfid_ctx::Stage *)&c->fin, (rfid_ctx::Stage *)&c->ret,
-                               (rfid_ctx::Stage *)&c->col})
+                               (rfid_ctx::Stage *)&c->col, (rfid_ctx::Stage *)&c->len})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
@@ -2495,6 +2504,68 @@ int rfid_collisions_of(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_re
                      c->stream, (const float2 *)b, (const rfid_decode_result *)(b + sz_w), n_windows, (rfid_collision *)(b + sz_w + sz_r));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sz_out, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
+}
+
+// ---- lengths stage: CRC-failed EPC windows read at the length their PC word announces, behind the statistics of a pass (csrc/rfid_lengths.hpp) ----
+int rfid_batch_plan_lengths(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Lengths &p = c->len;
+  const int rows = (c->wmax + 1) / 2;      // EPC windows are every other window
+  const int r = table_plan(c, p, ST_LENGTHS, rows,
+                           {{&p.d_table, sizeof(rfid_sized_frame) * (size_t)rows * (size_t)c->B_plan},
+                            {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan}});
+  if (r) return r;
+  p.blocks = (rows + LEN_ROWS - 1) / LEN_ROWS;
+  return RFID_OK;
+}
+
+int rfid_batch_lengths(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Lengths &p = c->len;
+  int n = 0;
+  LenArgs a;
+  { int r = table_begin(c, p, ST_LENGTHS, &n, &a.p); if (r) return r; }
+  a.rows = p.rows; a.blocks = p.blocks; a.table = p.table<rfid_sized_frame>(); a.nrows = p.d_nrows;
+  // the span of a window reaches behind it, but never behind its trace: the lengths of the pass (as its gate scan had them)
+  a.lens = c->d_lens; a.n_dec = c->last_n_raw / DECIM;
+  // single-wave workgroups, each walking blocks of eight rows (13.5 KB of LDS each)
+  const int64_t items = (int64_t)n * p.blocks;
+  const int64_t most = c->knobs.lengths_wgs ? (int64_t)c->knobs.lengths_wgs : (int64_t)c->n_cus * LEN_WGS_PER_CU;
+  hipLaunchKernelGGL(lengths_kernel, persistent_grid(items, most), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return table_end(c, p, n);
+}
+
+int rfid_batch_get_window_lengths(rfid_ctx *c, int stream, rfid_sized_frame *out, int64_t cap, int64_t *n) {
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->len, ST_LENGTHS, "rfid_batch_get_window_lengths", sizeof(*out), stream, out, cap, n);
+}
+
+int rfid_batch_lengths_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  return stage_ms(c, c->len, ms);
+}
+
+// the per-call form: one span in host memory through the batch kernel's device functions (one launch, synchronising)
+int rfid_length_window(rfid_ctx *c, const rfid_cf32 *span, int n, const rfid_decode_result *res, rfid_sized_frame *out) {
+  if (!c || !span || !res || !out) return RFID_ERR_INVALID;
+  if (n < EPC_WIN || n > LEN_SPAN) return failf(c, RFID_ERR_INVALID, "rfid_length_window: a span holds %d to %d samples", EPC_WIN, LEN_SPAN);
+  if (res->type != RFID_DECODE_EPC) return fail(c, RFID_ERR_INVALID, "rfid_length_window: not the result of an EPC window");
+  if (res->index < 65 || res->index > 65 + N_SYNC - 1) return fail(c, RFID_ERR_INVALID, "rfid_length_window: the result's index is no sync offset (65 .. 79)");
+  if (!(res->T >= LEN_T_LO && res->T <= LEN_T_HI))
+    return fail(c, RFID_ERR_INVALID, "rfid_length_window: the result's T is none of the decoder's (4.94999981 .. 5.05000019)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_w = up256(sizeof(float2) * (size_t)LEN_SPAN), sz_r = up256(sizeof(rfid_decode_result));
+  { int r = grow(c, c->one, sz_w + sz_r + sizeof(rfid_sized_frame)); if (r) return r; }
+  char *b = (char *)c->one.p;
+  HIPCHK(c, hipMemcpyAsync(b, span, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(lengths_one_kernel, dim3(1), dim3(64), 0, c->stream, (const float2 *)b, n, (const rfid_decode_result *)(b + sz_w),
+                     (rfid_sized_frame *)(b + sz_w + sz_r));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
 }

@@ -1791,6 +1791,32 @@ struct Crc16Table {
 };
 __device__ const Crc16Table g_crc16 = Crc16Table();
 
+// The same CRC over messages of other lengths (csrc/rfid_lengths.hpp): what a set bit contributes depends only on how many bits
+// follow it -- d[q]: the register after that bit and q more zero bits (g_crc16.c[j] == d[111 - j]) -- and the constant on the
+// message's length alone -- k[w]: 0xFFFF after 16 + 16 w zero bits, a PC word and w EPC words (k[6] == g_crc16.k).
+struct Crc16Sized {
+  static constexpr int MAX_WORDS = 8, MAX_BITS = 16 + 16 * MAX_WORDS;
+  unsigned short d[MAX_BITS];
+  unsigned short k[MAX_WORDS + 1];
+  constexpr Crc16Sized() : d{}, k{} {
+    unsigned reg = 0x1021u;
+    for (int q = 0; q < MAX_BITS; ++q) {
+      d[q] = (unsigned short)reg;
+      const unsigned msb = (reg >> 15) & 1u;
+      reg = (reg << 1) & 0xFFFFu;
+      if (msb) reg ^= 0x1021u;
+    }
+    reg = 0xFFFFu;
+    for (int i = 1; i <= MAX_BITS; ++i) {
+      const unsigned msb = (reg >> 15) & 1u;
+      reg = (reg << 1) & 0xFFFFu;
+      if (msb) reg ^= 0x1021u;
+      if ((i & 15) == 0) k[i / 16 - 1] = (unsigned short)reg;
+    }
+  }
+};
+__device__ const Crc16Sized g_crc16_sized = Crc16Sized();
+
 template <int LEN>
 RFID_DEVICE void stage_window(const float2 *src, float dcr, float dci, float2 *s, float *m2,
                               int lane) {

@@ -179,23 +179,10 @@ struct RetArgs {
 };
 
 // the matched-filter outputs trace s holds (as gate_extent has it)
-RFID_DEVICE int retune_extent(const RetArgs &a, int s) {
-  int64_t n64 = a.n_dec;
-  if (a.lens) {
-    int64_t r = a.lens[s];
-    if (r < 0) r = 0;
-    n64 = r / DECIM;
-    if (n64 > a.n_dec) n64 = a.n_dec;
-  }
-  return (int)n64;
-}
+RFID_DEVICE int retune_extent(const RetArgs &a, int s) { return stage_extent(a.lens, a.n_dec, s); }
 
 // the span's last own sample of a window that starts at `start` in a trace of n_dec outputs (-1: none)
-RFID_DEVICE int retune_last(int n_dec, int start) {
-  if (start < 0 || start >= n_dec) return -1;
-  const int last = n_dec - 1 - start;
-  return (last > RET_SPAN - 1) ? (RET_SPAN - 1) : last;
-}
+RFID_DEVICE int retune_last(int n_dec, int start) { return stage_span_last(n_dec, start, RET_SPAN); }
 
 RFID_KERNEL(64) void retune_kernel(RetArgs a) {
   RFID_SHARED float2 s[RET_SPAN];

@@ -1,10 +1,10 @@
 // rfid_stage.hpp -- what the stages behind a batch pass decide in the same way, written once.  Every stage header includes
 // this file and, beside it, only the stage headers whose symbols it uses (the tracks: the inventory's table walk).
 //   stage_windows / stage_fetch   which windows of a trace count in a pass, how a result record is read and which records are
-//                                 reads (all nine stages / inventory and tracks);
+//                                 reads (all ten stages / inventory and tracks);
 //   scan_share / scan_partials    the one-workgroup offsets scan (inventory, tracks; the repair stage takes the shares);
-//   StagePass                     what a pass left, as the seven window-table stages see it -- quality, repair, slots, commands,
-//                                 fine, retune, collisions: each fills one [trace][row] table of fixed-size records with a persistent grid of single-wave
+//   StagePass                     what a pass left, as the eight window-table stages see it -- quality, repair, slots, commands,
+//                                 fine, retune, collisions, lengths: each fills one [trace][row] table of fixed-size records with a persistent grid of single-wave
 //                                 workgroups, stage_windows gives the cut-off, rows behind it are zeroed, nrows[s] is written by
 //                                 the first pack.  How a table kernel loads, parks, sums and stores is its own (its header says why);
 //   epc_clamp / epc_gather        the decoder's half-bit gather of an EPC window (quality, repair, fine);
@@ -80,7 +80,7 @@ RFID_DEVICE int scan_partials(int *part, int tid, int nthr, int sum, int &total)
 }
 
 // ---- the window-table stages -----------------------------------------------------------------------------------------
-// What a pass left: the FIRST member of QualArgs, RepArgs, MomArgs, CmdArgs, FineArgs, RetArgs and ColArgs, filled by the host's table_begin.
+// What a pass left: the FIRST member of QualArgs, RepArgs, MomArgs, CmdArgs, FineArgs, RetArgs, ColArgs and LenArgs, filled by the host's table_begin.
 // (InvArgs and TrkArgs carry no y and another order: they stay their own.)
 struct StagePass {
   const float2 *y;                  // the matched filter's output of the pass
@@ -91,6 +91,25 @@ struct StagePass {
   const rfid_stream_stats *stats;   // [n_streams]: n_windows_used of the same pass
   int wmax, n_streams;
 };
+
+// The stages that read behind a window (retune, lengths) never read behind the trace's own length.
+// the matched-filter outputs trace s holds (as gate_extent has it); lens: raw samples per trace, or nullptr: n_dec for all
+RFID_DEVICE int stage_extent(const int64_t *lens, int64_t n_dec, int s) {
+  int64_t n64 = n_dec;
+  if (lens) {
+    int64_t r = lens[s];
+    if (r < 0) r = 0;
+    n64 = r / DECIM;
+    if (n64 > n_dec) n64 = n_dec;
+  }
+  return (int)n64;
+}
+// the last own sample of a span of `span` samples that starts at `start` in a trace of n_dec outputs (-1: none)
+RFID_DEVICE int stage_span_last(int n_dec, int start, int span) {
+  if (start < 0 || start >= n_dec) return -1;
+  const int last = n_dec - 1 - start;
+  return (last > span - 1) ? (span - 1) : last;
+}
 
 RFID_DEVICE int epc_clamp(int i) { return (i < 0) ? 0 : ((i > EPC_WIN - 1) ? (EPC_WIN - 1) : i); }
 

@@ -108,6 +108,10 @@ COLLISION_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("flags", "<i4"),
                             ("sum_sq", "<f4"), ("c_re", "<f4"), ("c_im", "<f4"), ("reserved_", "<i4")])
 RN16_WINDOW = 250         # the gated samples of an RN16 window
 assert COLLISION_DTYPE.itemsize == 64
+SIZED_FRAME_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("flags", "<i4"), ("words", "<i4"), ("n_bits", "<i4"),
+                              ("crc_rcvd", "<i4"), ("crc_calc", "<i4"), ("frame", "<u4", (5,)), ("reserved_", "<i4", (3,))])
+LENGTHS_SPAN, LENGTHS_MAX_WORDS = 1728, 8
+assert SIZED_FRAME_DTYPE.itemsize == 64
 GATE_FSM_IN_DTYPE = np.dtype([("mode", "<i4"), ("n_samples", "<i4"), ("signal_state", "<i4"), ("num_pulses", "<i4"),
                               ("gate_open", "<i4"), ("n_to_ungate", "<i4"), ("wtype", "<i4"), ("nvalid", "<i4"), ("pos", "<i4"),
                               ("reserved_", "<i4"), ("below", "<u8"), ("above", "<u8")])
@@ -236,6 +240,11 @@ SIGNATURES = {
     "rfid_batch_get_window_collisions": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_collisions_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_collisions_of": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "rfid_batch_plan_lengths": (_i, [_vp]),
+    "rfid_batch_lengths": (_i, [_vp]),
+    "rfid_batch_get_window_lengths": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_lengths_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_length_window": (_i, [_vp, _vp, _i, _vp, _vp]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

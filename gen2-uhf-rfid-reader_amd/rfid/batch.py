@@ -59,6 +59,8 @@ class BatchDecoder:
         self.last_retunes = None      # one retune array per trace (every EPC window before the cut-off) of the last decode(..., retune=True)
         self._col_planned = False
         self.last_collisions = None   # one collisions array per trace (every RN16 window before the cut-off) of the last decode(..., collisions=True)
+        self._len_planned = False
+        self.last_lengths = None      # one sized-frame array per trace (every EPC window before the cut-off) of the last decode(..., lengths=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -78,6 +80,7 @@ class BatchDecoder:
             self._fine_planned = False
             self._ret_planned = False
             self._col_planned = False
+            self._len_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -89,7 +92,7 @@ class BatchDecoder:
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
                inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False,
                repair: bool = False, slots: bool = False, commands: bool = False, fine: bool = False,
-               retune: bool = False, collisions: bool = False):
+               retune: bool = False, collisions: bool = False, lengths: bool = False):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
@@ -117,7 +120,10 @@ class BatchDecoder:
         offset); a retuned frame is not a read and changes nothing else.  collisions=True (implies slots=True: the report needs the
         class): both RN16s and both channels of every RN16 window, as of two tags replying at once, are worked out behind the pass;
         `self.last_collisions` keeps one capi.COLLISION_DTYPE array per trace, a record per RN16 window (classify_collisions() keeps
-        those of the collided slots and tells two tags from more); nothing else changes."""
+        those of the collided slots and tells two tags from more); nothing else changes.  lengths=True (implies nothing): the
+        CRC-failed EPC windows are read again behind the pass at the length their own PC word announces (the decoder takes every
+        reply for a 96-bit EPC); `self.last_lengths` keeps one capi.SIZED_FRAME_DTYPE array per trace, a record per EPC window
+        (sized_frame_fields() turns one into PC, EPC and its length); such a frame is not a read and changes nothing else."""
         torch = self._torch
         n = len(traces)
         lens = np.array([len(t) for t in traces], dtype=np.int64)
@@ -169,6 +175,9 @@ class BatchDecoder:
         if collisions and not self._col_planned:
             self.ctx.batch_plan_collisions()
             self._col_planned = True
+        if lengths and not self._len_planned:
+            self.ctx.batch_plan_lengths()
+            self._len_planned = True
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
         if inventory:
             self.ctx.batch_inventory_enqueue()
@@ -188,6 +197,8 @@ class BatchDecoder:
             self.ctx.batch_retune_enqueue()
         if collisions:
             self.ctx.batch_collisions_enqueue()
+        if lengths:
+            self.ctx.batch_lengths_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
@@ -208,6 +219,8 @@ class BatchDecoder:
             self.last_retunes = [self.ctx.batch_window_retunes(b) for b in range(n)]
         if collisions:
             self.last_collisions = [self.ctx.batch_window_collisions(b) for b in range(n)]
+        if lengths:
+            self.last_lengths = [self.ctx.batch_window_lengths(b) for b in range(n)]
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -482,6 +495,53 @@ def format_retunes_csv(rows: Sequence[np.ndarray], entries: Sequence[np.ndarray]
     return "\n".join(lines) + "\n"
 
 
+LENGTHS_HEADER = "file,epc,pc,epc_bits,seq,t_s,T,h_re,h_im,clamped"
+
+
+def sized_frame_fields(rec) -> tuple:
+    """One rfid_sized_frame record that was decoded (n_bits > 0) -> (PC as an int, EPC as epc_bits / 4 hex digits -- the empty string
+    for a PC alone --, epc_bits = 16 x words), bits MSB first as sent."""
+    n = int(rec["n_bits"])
+    if n < 32:
+        raise ValueError("not a decoded frame")
+    w = np.asarray(rec["frame"], dtype=np.uint32)
+    j = np.arange(n)
+    bits = ((w[j >> 5] >> (j & 31)) & 1).astype(np.uint8)
+    val = lambda b: int("".join(map(str, b.tolist())), 2) if len(b) else 0
+    epc_bits = n - 32
+    return val(bits[:16]), ("%0*x" % (epc_bits // 4, val(bits[16:n - 16]))) if epc_bits else "", epc_bits
+
+
+def format_lengths(rows: np.ndarray) -> str:
+    """One line for one trace's EPC windows before the cut-off (Context.batch_window_lengths): how many failed their CRC, how many
+    of those pass when read at the length their PC announces, how many distinct EPCs those are, how many of them there are of each
+    EPC length, and how many windows announce more words than the slot holds."""
+    rows = np.asarray(rows)
+    got = rows[(rows["flags"] & 2) != 0]
+    frames = {(int(r["n_bits"]), bytes(np.ascontiguousarray(r["frame"]))) for r in got}
+    by = sorted({int(r["n_bits"]) - 32 for r in got})
+    hist = "  ".join("%d-bit : %d" % (b, int((got["n_bits"] == b + 32).sum())) for b in by) if by else "-"
+    return ("| failed EPC windows : %d  pass at the PC's length : %d  distinct EPCs : %d  by EPC length : %s  longer than the slot : %d\n" %
+            (int(((rows["flags"] & 1) == 0).sum()), len(got), len(frames), hist, int(((rows["flags"] & 8) != 0).sum())))
+
+
+def format_lengths_csv(rows: Sequence[np.ndarray], names: Sequence[str], results: Sequence[np.ndarray]) -> str:
+    """CSV text, one line per window that passes at its PC's length, by trace, then by seq: file,epc,pc,epc_bits,seq,t_s,T,h_re,h_im,
+    clamped.  rows[b]: the rfid_sized_frame records of trace b; names[b]: its file; results[b]: its windows' capi.RESULT_DTYPE records
+    in seq order -- T, h_re and h_im are the window's result's, with %.9g (a binary32 value survives the round trip); t_s =
+    start / 400e3 as in the tracks CSV."""
+    lines = [LENGTHS_HEADER]
+    for rec, name, res in zip(rows, names, results):
+        rec = np.asarray(rec)
+        for r in rec[(rec["flags"] & 2) != 0]:
+            pc, epc, epc_bits = sized_frame_fields(r)
+            d = res[int(r["seq"])]
+            lines.append("%s,%s,%04x,%d,%d,%.9g,%.9g,%.9g,%.9g,%d" %
+                         (name, epc, pc, epc_bits, int(r["seq"]), int(r["start"]) / TRACKS_RATE, float(d["T"]), float(d["h_re"]),
+                          float(d["h_im"]), 1 if int(r["flags"]) & 4 else 0))
+    return "\n".join(lines) + "\n"
+
+
 MOMENTS_N = 240           # RFID_MOMENTS_SAMPLES: the samples of a window its moments are taken over
 SLOT_EMPTY, SLOT_SINGLE, SLOT_COLLIDED, SLOT_UNKNOWN = 0, 1, 2, -1
 SCHOUTE = 2.39            # Schoute's estimate of the tags behind a collided slot of a framed-ALOHA round
@@ -724,7 +784,7 @@ def format_commands_csv(rows: Sequence[np.ndarray], starts: Sequence[np.ndarray]
 
 
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] [--collisions OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] [--collisions OUT.csv] [--lengths OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -761,16 +821,21 @@ def main(argv=None) -> int:
                          "were on the air, how strong the two tags were, whether the decoder's RN16 was one of them, and whether "
                          "more than two tags collided; one line per file, the collided slots to this CSV file; classifies the slots "
                          "as --slots does, without its line and CSV")
+    ap.add_argument("--lengths", metavar="OUT.csv", default=None,
+                    help="read the CRC-failed EPC windows again at the length their own PC word announces (built on the device): "
+                         "finds tags whose EPC is not the 96 bits the decoder takes every reply for; one line per file, the windows "
+                         "that pass to this CSV file")
     args = ap.parse_args(argv)
     if args.tracks or args.repair or args.retune:
         args.inventory = True
     dec = BatchDecoder(device=args.device, fixed_q=args.fixed_q, max_num_queries=args.max_queries)
     try:
         timing = {}
-        stats, windows, _, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
+        stats, windows, results, _ = dec.decode_files(args.files, timing=timing, inventory=args.inventory, max_tags=args.max_tags,
                                             tracks=bool(args.tracks), quality=args.quality, repair=bool(args.repair),
                                             slots=bool(args.slots), commands=bool(args.commands), fine=args.fine,
-                                            retune=bool(args.retune), collisions=bool(args.collisions))
+                                            retune=bool(args.retune), collisions=bool(args.collisions),
+                                            lengths=bool(args.lengths))
         collided = ([classify_collisions(c, classify_slots(m)) for c, m in zip(dec.last_collisions, dec.last_slots)]
                     if args.collisions else None)
         per_trace = lambda entries, counts: np.split(entries, np.cumsum(counts)[:-1]) if len(counts) else []
@@ -791,6 +856,8 @@ def main(argv=None) -> int:
                 print(format_retune(dec.last_retunes[i], per_trace(*dec.last_inventory)[i]), end="")
             if args.collisions:
                 print(format_collisions(collided[i]), end="")
+            if args.lengths:
+                print(format_lengths(dec.last_lengths[i]), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
               (len(args.files), timing["raw_samples"] / 1e6, timing["total_s"], timing["h2d_s"], timing["gpu_s"]))
         if args.inventory:
@@ -822,6 +889,10 @@ def main(argv=None) -> int:
             starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
             with open(args.collisions, "w") as f:
                 f.write(format_collisions_csv(collided, starts, args.files))
+        if args.lengths:
+            by_seq = [results[windows["stream"] == b] for b in range(len(args.files))]              # (ordered by seq)
+            with open(args.lengths, "w") as f:
+                f.write(format_lengths_csv(dec.last_lengths, args.files, by_seq))
         if args.commands:
             starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
             with open(args.commands, "w") as f:

@@ -660,6 +660,40 @@ class Context:
         self._chk(self._lib.rfid_collisions_of(self._h, windows.ctypes.data, res.ctypes.data, len(windows), out.ctypes.data))
         return out
 
+    def batch_plan_lengths(self) -> None:
+        """Reserves the lengths workspace of the current plan (a new plan drops it; no other stage's plan call does, and it
+        needs none of them)."""
+        self._chk(self._lib.rfid_batch_plan_lengths(self._h))
+
+    def batch_lengths_enqueue(self) -> None:
+        """Asynchronous: the CRC-failed EPC windows of the last pass read again at the length their PC word announces, behind
+        its statistics (rfid_batch_lengths).  The pass's per-trace lengths must still be valid."""
+        self._chk(self._lib.rfid_batch_lengths(self._h))
+
+    def batch_window_lengths(self, stream: int, extra: int = 0) -> np.ndarray:
+        """One trace's row of the lengths table (synchronises): the capi.SIZED_FRAME_DTYPE record of EVERY EPC window before
+        the cut-off, in seq order (n_windows_used // 2 of them), of the last batch_lengths_enqueue: flags bit 0 = the window was
+        a read (nothing done), bit 1 = the frame at the PC's length passes its CRC, bit 2 = the frame ran into the trace's end,
+        bit 3 = the PC announces more words than a slot holds, bit 4 = it announces the decoder's own length.  extra > 0: up to
+        that many of the table's rows behind them as well (zeroed by the stage)."""
+        return self._window_rows(self._lib.rfid_batch_get_window_lengths, capi.SIZED_FRAME_DTYPE, stream, extra)
+
+    def batch_lengths_ms(self) -> float:
+        return self._stage_ms(self._lib.rfid_batch_lengths_ms)
+
+    def length_window(self, span, result) -> np.ndarray:
+        """The same for ONE span in host memory (rfid_length_window): span = 1370 .. 1728 DC-free samples from the window's
+        first on (indices behind the last one are held there), result = the window's capi.RESULT_DTYPE record (its T, index,
+        h and first five bits are used).  -> one capi.SIZED_FRAME_DTYPE record, stream = seq = start = 0."""
+        span = np.ascontiguousarray(span, dtype=np.complex64)
+        if span.ndim != 1 or not 1370 <= len(span) <= capi.LENGTHS_SPAN:
+            raise ValueError("a span has 1370 to %d samples" % capi.LENGTHS_SPAN)
+        res = np.zeros(1, dtype=capi.RESULT_DTYPE)
+        res[0] = result
+        out = np.zeros(1, dtype=capi.SIZED_FRAME_DTYPE)
+        self._chk(self._lib.rfid_length_window(self._h, span.ctypes.data, len(span), res.ctypes.data, out.ctypes.data))
+        return out[0]
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

@@ -107,6 +107,27 @@ def epc_frame(epc96: Sequence[int], pc: Optional[Sequence[int]] = None) -> List[
     return body + crc16(body)
 
 
+def pc_for_words(words: int) -> List[int]:
+    """The PC word of an EPC of `words` 16-bit words: the length in its first five bits, zeros behind (at 6: epc_frame's default)."""
+    return [(words >> i) & 1 for i in (4, 3, 2, 1, 0)] + [0] * 11
+
+
+def sized_epc_frame(epc: Sequence[int]) -> List[int]:
+    """PC + EPC + CRC-16 for an EPC of 0 .. 128 bits, a multiple of 16: 32 + len(epc) frame bits."""
+    epc = list(epc)
+    if len(epc) % 16 or len(epc) > 128:
+        raise ValueError("an EPC holds 0 .. 128 bits, a multiple of 16")
+    body = pc_for_words(len(epc) // 16) + epc
+    return body + crc16(body)
+
+
+def resize_epc(epc96: Sequence[int], n_bits: int) -> List[int]:
+    """The EPC of n_bits a tag with this 96-bit EPC has: the last n_bits of the 96 bits written twice (no random draw is spent on
+    it, and the last byte stays the tag's id)."""
+    twice = list(epc96) + list(epc96)
+    return twice[len(twice) - n_bits:]
+
+
 def epc_for_id(tag_id: int, rng: Optional[np.random.Generator] = None) -> List[int]:
     """96-bit EPC whose last byte (frame bits 104..111) is `tag_id`."""
     head = (rng.integers(0, 2, 88).tolist() if rng is not None else [0] * 88)
@@ -119,7 +140,7 @@ class SlotTruth:
     slot: int
     n_tags: int
     rn16: Optional[List[int]]      # bits backscattered (single responder) or None
-    epc: Optional[List[int]]       # 128 frame bits actually sent (after any corruption)
+    epc: Optional[List[int]]       # the frame bits actually sent (after any corruption): 128, or 32 + the tag's epc_bits
     tag_id: Optional[int]
     epc_valid: bool                # CRC of the sent frame is intact
     rn16_raw_start: int = -1       # raw-sample index where the RN16 preamble begins
@@ -173,7 +194,7 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
                h: complex = 0.10 * np.exp(2.1j), corrupt_rounds: Sequence[int] = (),
                t1_us: float = T1_US, tail_us: int = 200, noise: bool = True,
                t1_jitter_raw: int = 0, render: bool = True,
-               blf_offsets: Optional[Sequence[float]] = None) -> Trace:
+               blf_offsets: Optional[Sequence[float]] = None, epc_bits: Optional[Sequence[int]] = None) -> Trace:
     """Build one RX trace of `n_rounds` inventory rounds with 2**fixed_q slots each.
 
     Each tag picks a slot uniformly per round; slots with exactly one tag carry an
@@ -190,6 +211,14 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
     this link setting): every reply of that tag has half-bits of 25 (1 + d) raw samples, the level at raw sample n of a reply
     being levels[floor(n / (25 (1 + d)))].  The random draws are the same with and without offsets; None or zeros give the
     samples of a trace without them, byte for byte.  The slot table knows no offsets: with `render=False` they raise.
+
+    `epc_bits`: one EPC length per tag, a multiple of 16 in 0 .. 128 (None: 96 for all).  A tag's EPC reply is then PC + EPC +
+    CRC-16 with that many EPC bits, the PC holding the length in words in its first five bits and zeros behind (at 96 bits: the
+    PC of every trace so far), and SlotTruth.epc holds the 32 + epc_bits bits actually sent.  The random draws are the same
+    whatever the lengths -- another length changes that tag's EPC replies and nothing else -- and None or all-96 give the samples
+    and the slot table of a trace without the argument, byte for byte.  The slot table holds 128 frame bits: with `render=False`
+    another length raises, and a rendered trace with another length has no `.plan`.  A 128-bit EPC ends 150 us before the reader's next command; a reply that a slow tag (blf_offsets)
+    stretches -- a 128-bit EPC by more than 3.5 % -- would run into that command: the combination raises.
     """
     if blf_offsets is None:
         blf_offsets = [0.0] * len(tag_ids)
@@ -200,6 +229,19 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
         raise ValueError("blf_offsets: relative offsets of the half-bit period, well inside +- 0.5")
     if not render and any(blf_offsets):
         raise ValueError("blf_offsets: the slot table of render=False holds no offsets")
+    if epc_bits is None:
+        epc_bits = [96] * len(tag_ids)
+    epc_bits = [int(b) for b in epc_bits]
+    if len(epc_bits) != len(tag_ids):
+        raise ValueError("epc_bits: one EPC length per tag")
+    if any(b % 16 or not 0 <= b <= 128 for b in epc_bits):
+        raise ValueError("epc_bits: EPC lengths are multiples of 16 in 0 .. 128")
+    if not render and any(b != 96 for b in epc_bits):
+        raise ValueError("epc_bits: the slot table of render=False holds frames of 128 bits")
+    for b, d in zip(epc_bits, blf_offsets):
+        # preamble, 32 + b frame bits and the dummy bit, two half-bits each, of 12.5 (1 + d) us; the carrier behind an ACK: CW_ACK
+        if b != 96 and t1_us + t1_jitter_raw / 2.0 + (12 + 2 * (32 + b + 1)) * 12.5 * (1.0 + d) > CW_ACK:
+            raise ValueError("epc_bits / blf_offsets: the reply would not end on the reader's carrier")
     rng = np.random.default_rng(seed)
     n_slots = 1 << fixed_q
     tx_parts: List[np.ndarray] = []
@@ -253,11 +295,11 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
             emit(ack_cmd(ack_bits))
             if len(who) == 1:
                 k = who[0]
-                frame = epc_frame(epcs[k])
+                frame = epc_frame(epcs[k]) if epc_bits[k] == 96 else sized_epc_frame(resize_epc(epcs[k], epc_bits[k]))
                 valid = True
                 if (r in corrupt_rounds) and not corrupted:
                     frame = list(frame)
-                    frame[40] ^= 1
+                    frame[min(40, len(frame) - 1)] ^= 1
                     valid = False
                     corrupted = True
                 jit = int(rng.integers(-t1_jitter_raw, t1_jitter_raw + 1)) if t1_jitter_raw else 0
@@ -266,7 +308,8 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
                     events.append((reply_at, fm0_levels(frame), hs[k], blf_offsets[k]))
                 rec["has_epc"] = 1
                 rec["epc_off_raw"] = int(round(reply_at * 2)) - 2 * t
-                rec["epc"] = _pack_frame(frame)
+                if len(frame) == 128:              # (another length: the trace gets no plan, below)
+                    rec["epc"] = _pack_frame(frame)
                 truth.epc = list(frame)
                 truth.tag_id = tag_ids[k]
                 truth.epc_valid = valid
@@ -278,6 +321,8 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
                      tail_us=int(tail_us), n_raw=2 * t)
     if not render:
         return Trace(samples=None, slots=slots, fixed_q=fixed_q, plan=plan)
+    if any(b != 96 for b in epc_bits):
+        plan = None                                # (the slot table cannot hold these frames)
 
     tx = np.repeat(np.concatenate(tx_parts), 2)     # 1 Msps -> 2 Msps
     x = (np.complex64(leak) * tx).astype(np.complex64)

@@ -275,6 +275,45 @@ typedef struct rfid_retune {         /* 64 bytes */
   int32_t  reserved_[3];             /* 0 */
 } rfid_retune;
 
+/* what the lengths stage (rfid_batch_lengths, rfid_length_window) finds for one EPC window whose CRC-16 failed: the frame read at the
+ * length its own PC word announces.  A tag answers an ACK with PC (16 bits) + EPC + CRC-16, and the first five PC bits give the EPC's
+ * length L in 16-bit words (Gen2 6.3.2.1.2.2).  The decoder takes every reply for 128 bits (EPC_BITS = 129, check_crc over 14 bytes:
+ * L = 6, a 96-bit EPC); a tag with a 128- or a 64-bit EPC fails every CRC and is otherwise absent from everything a pass reports.
+ * A frame of L < 6 lies inside the gate's 1 370-sample window; one of L = 7 or 8 ends behind it, on the reader's carrier, which lasts
+ * 1 830 decimated samples after the ACK: the furthest half-bit of a 160-bit frame is at 79 + 319 x 5.05000019 = 1689.95 samples.
+ * A frame found here is NOT a read: nothing else the library reports changes.
+ * THE DEFINITION (the contract; binary32 throughout, every operation rounded by itself, no fused multiply-add), for an EPC window
+ * with seq < n_windows_used and crc_ok == 0:
+ *   L      = sum of bit_i << (4 - i) over the result's frame bits i = 0 .. 4.  L == 6 or L > 8: only `words` and the flag bit (4 / 3)
+ *            are set.  Else n = 32 + 16 L.
+ *   span   s[i] = y[start + min(i, last)] - dc per component, 0 <= i < RFID_LENGTHS_SPAN.  last: the trace's own last
+ *          matched-filter output relative to start (as rfid_retune has it); no sample behind it is read.
+ *   decisions j = 0 .. n - 1, with the result's own T, index, h_re, h_im -- the decoder's two associations and its sign chain
+ *          (tag_decoder_impl.cc:171-190), continued past 127:
+ *            ia = (int)((float)j * (2.0f * T) + (float)index),  ib = (int)(((float)(2 j) * T + T) + (float)index), both held
+ *            inside 0 .. RFID_LENGTHS_SPAN - 1;  (dx, dy) = s[ia] - s[ib];  r_j = dx * h_re - dy * (-h_im);  cur_j = r_j > 0;
+ *            bit_j = (cur_j != cur_(j-1)), cur_(-1) positive.
+ *   CRC    the reference's check_crc (:401-445) over n bits instead of 128: the bits packed MSB first into bytes, CRC-16/CCITT
+ *          (init 0xFFFF, per byte crc ^= b << 8 and eight shift-xor 0x1021 steps) over the first (n - 16) / 8 bytes, complemented,
+ *          compared with the last 16 bits.
+ * Decisions 0 .. 127 are the decoder's own: frame words 0 .. 3, as far as n reaches, equal the result's bits.
+ * A window with a non-finite sample: unspecified, as its decoding is. */
+#define RFID_LENGTHS_SPAN      1728   /* 27 x 64 */
+#define RFID_LENGTHS_MAX_WORDS 8      /* EPC words a slot of this link setting holds: a 160-bit frame */
+typedef struct rfid_sized_frame {    /* 64 bytes */
+  int32_t  stream, seq;              /* the EPC window (rfid_window::stream / seq) */
+  int32_t  start;                    /* rfid_window::start of that window */
+  int32_t  flags;                    /* bit 0: crc_ok of the window's result (then nothing is done: every field below is 0);
+                                        bit 1: the frame at the PC's length passes its CRC-16; bit 2: an index lay behind the
+                                        trace's (the span's) last sample and was held there; bit 3: L > 8: does not fit the slot,
+                                        nothing decoded; bit 4: L == 6: the decoder's own length, nothing to add */
+  int32_t  words;                    /* L */
+  int32_t  n_bits;                   /* 32 + 16 L when decoded, else 0 */
+  int32_t  crc_rcvd, crc_calc;       /* the last 16 bits MSB first / the CRC computed over the bits before them; 0 when not decoded */
+  uint32_t frame[5];                 /* n_bits bits packed as rfid_decode_result::bits; the rest 0 */
+  int32_t  reserved_[3];             /* 0 */
+} rfid_sized_frame;
+
 /* what the collisions stage (rfid_batch_collisions, rfid_collisions_of) works out for one RN16 window: the two RN16s and the two
  * channels of a slot in which two tags replied at once.  The decoder is single-tag by construction (tag_detection_RN16,
  * lib/tag_decoder_impl.cc:114-142, 237-253): decision j is the difference d_j of two adjacent half-bit samples across a bit
@@ -984,6 +1023,31 @@ RFID_API int rfid_batch_collisions_ms(rfid_ctx *ctx, float *ms);
  * synchronising.  out[k]: stream = 0, seq = k. */
 RFID_API int rfid_collisions_of(rfid_ctx *ctx, const rfid_cf32 *gated, const rfid_decode_result *results, int n_windows,
                                 rfid_collision *out);
+/* ---- (2k) batch lengths: CRC-failed EPC frames read at the length their PC word announces, built on the device ---------------- */
+/* Behind a pass: one rfid_sized_frame (see its definition above) per EPC window with seq < n_windows_used in a device table
+ * [n_streams][ceil(wmax / 2)] (row = seq >> 1; the rows of a trace behind its cut-off are zeroed: the table's bytes repeat from
+ * pass to pass).  Nothing else a pass reports changes: a frame found here is not a read.  rfid_batch_plan_lengths reserves the
+ * table (64 bytes per possible EPC window).  RFID_ERR_STATE without a plan; RFID_ERR_HIP when the allocation fails (the plan and
+ * every other workspace stay usable).  A new rfid_batch_plan drops it; it neither needs nor drops any other stage's workspace, and
+ * their plan calls do not drop it. */
+RFID_API int rfid_batch_plan_lengths(rfid_ctx *ctx);
+/* enqueues the lengths stage of the LAST pass behind its statistics (asynchronous, no host synchronisation).  RFID_ERR_STATE: no
+ * lengths workspace, or no pass with statistics yet.  It needs no inventory and may be enqueued before or behind the other stages:
+ * it neither needs nor changes their level.  It reads that pass's matched-filter output -- up to 358 samples behind a window, never
+ * behind the trace's own length: the lengths are the pass's (d_lens, which must still be valid, or n_raw) -- window table, results
+ * and statistics on the context's main stream and has rfid_batch_slots' duties there.  ONE table per plan, as rfid_batch_commands. */
+RFID_API int rfid_batch_lengths(rfid_ctx *ctx);
+/* synchronises; one trace's row of the table: every EPC window before the cut-off in seq order, verified, recovered or not:
+ * *n = n_windows_used / 2.  cap as rfid_batch_get_window_quality.  RFID_ERR_STATE before the first rfid_batch_lengths of this plan. */
+RFID_API int rfid_batch_get_window_lengths(rfid_ctx *ctx, int stream, rfid_sized_frame *out, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_lengths (HIP events) */
+RFID_API int rfid_batch_lengths_ms(rfid_ctx *ctx, float *ms);
+/* the same for ONE span in host memory: the per-call form.  span: n samples from the window's first on, DC-free already (dc = 0
+ * in the definition), 1370 <= n <= RFID_LENGTHS_SPAN (else RFID_ERR_INVALID): indices are held at n - 1 (flags bit 2); res: the
+ * result rfid_decoder_work gave for the window -- type RFID_DECODE_EPC, index 65 .. 79 and T inside the decoder's own
+ * 4.94999981 .. 5.05000019, else RFID_ERR_INVALID.  One launch of the batch kernel's device functions, synchronising.  out:
+ * stream = seq = start = 0; flags bit 0 = res->crc_ok (then nothing is done). */
+RFID_API int rfid_length_window(rfid_ctx *ctx, const rfid_cf32 *span, int n, const rfid_decode_result *res, rfid_sized_frame *out);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
