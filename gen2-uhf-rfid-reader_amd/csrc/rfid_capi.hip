@@ -1617,6 +1617,47 @@ int rfid_selftest_gate_fsm(rfid_ctx *c, const rfid_gate_fsm_in *in, int n, rfid_
   return rc;
 }
 
+// the arithmetic primitives on caller-given operands (a test entry: the expected values are the caller's).  Three launches fill
+// one record per workgroup: arith_selftest_kernel, ls2_arith2_selftest_kernel (the two-carry sum) and the stage kernel of the
+// matched filter, which reads each record's tile as a trace of 340 samples and stores its 64 outputs into the record.
+static_assert(sizeof(rfid_arith_in) % 16 == 0 && offsetof(rfid_arith_in, tile) % 16 == 0, "the tile is read with 16-byte loads");
+static_assert(sizeof(rfid_arith_out) % 8 == 0 && offsetof(rfid_arith_out, mf) % 8 == 0, "mf is a row of float2 for the stage kernel");
+int rfid_selftest_arith(rfid_ctx *c, const rfid_arith_in *in, int n, rfid_arith_out *out) {
+  if (!c || n < 0 || n > 65535 || !out || (n > 0 && !in)) return RFID_ERR_INVALID;
+  if (n == 0) return RFID_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  char *d = nullptr;
+  const size_t in_bytes = sizeof(rfid_arith_in) * (size_t)n, out_bytes = sizeof(rfid_arith_out) * ((size_t)n + 1);
+  HIPCHK(c, hipMalloc((void **)&d, in_bytes + out_bytes));
+  ArithSelfTestArgs a;
+  a.in = reinterpret_cast<const rfid_arith_in *>(d);
+  a.out = reinterpret_cast<rfid_arith_out *>(d + in_bytes);
+  a.n = n;
+  MfArgs m;
+  m.x = reinterpret_cast<const float2 *>(d + offsetof(rfid_arith_in, tile));
+  m.x_stride = (int64_t)(sizeof(rfid_arith_in) / sizeof(float2));
+  m.n_raw = 340; m.lens = nullptr; m.n_out = 64; m.in_off = 0; m.vec_ok = 1;
+  m.y = reinterpret_cast<float2 *>(d + in_bytes + offsetof(rfid_arith_out, mf));
+  m.y_stride = (int64_t)(sizeof(rfid_arith_out) / sizeof(float2));
+  m.tile0 = 0; m.stream0 = 0;
+  int rc = RFID_OK;
+  auto step = [&](hipError_t e) { if (e != hipSuccess && rc == RFID_OK) { snprintf(c->err, sizeof(c->err), "selftest_arith: %s", hipGetErrorString(e)); rc = RFID_ERR_HIP; } };
+  step(hipMemcpyAsync(d, in, in_bytes, hipMemcpyHostToDevice, c->stream));
+  step(hipMemcpyAsync(d + in_bytes, out, out_bytes, hipMemcpyHostToDevice, c->stream));
+  if (rc == RFID_OK) {
+    hipLaunchKernelGGL(arith_selftest_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, a);
+    step(hipGetLastError());
+    hipLaunchKernelGGL(ls2_arith2_selftest_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, a.in, a.out, n);
+    step(hipGetLastError());
+    mf_launch(dim3(1, (unsigned)n), c->stream, m);
+    step(hipGetLastError());
+  }
+  step(hipMemcpyAsync(out, a.out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+  step(hipStreamSynchronize(c->stream));
+  (void)hipFree(d);
+  return rc;
+}
+
 // stream_stats_kernel by itself on a caller-given result table, with a workgroup shape and an input form of the caller's choice
 // (a test entry: the expected values are the caller's).  The summaries are made on the device by stats_summary() and lie in an
 // array of their own sized as rfid_batch_plan sizes d_sum, so a row's alignment is what a plan of this wmax gives it.

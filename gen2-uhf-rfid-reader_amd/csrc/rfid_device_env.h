@@ -101,7 +101,8 @@ RFID_DEVICE void drain_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // glibc-2.35 hypotf: (float)sqrt((double)x*x + (double)y*y), double sqrt correctly rounded.  Both products are
 // exact in binary64, so the fma rounds once exactly like the sum.  The square root is the device library's
 // correctly rounded sequence (v_rsq_f64 + two coupled Newton steps + two residual corrections) without its range
-// scaling: the sum of two squared binary32 numbers is 0, inf, nan or lies in [2^-298, 2^129), where none is needed.
+// scaling: the sum of two squared binary32 numbers is 0, inf, nan or lies in [2^-298, 2^257), where none is needed
+// (checked on the device over that whole range, and next to binary32 rounding midpoints, by tests/test_gpu_arith.py).
 RFID_DEVICE float hypot_f(float x, float y) {
   const double xd = (double)x, yd = (double)y;
   const double s = __builtin_fma(xd, xd, yd * yd);

@@ -292,7 +292,8 @@ struct GateArgs {
 // instead of the ~11 of a generic correctly rounded division:
 //     q1 = x * RN(1/C);   q = fma(fma(-q1, C, x), RN(1/C), q1)
 // equals RN(x / C) bit for bit for every finite |x| >= 2^-120 -- checked exhaustively over all
-// 2^31 magnitudes on the host (tests/tools/divcheck.c) and sampled on the device by rfid_selftest().
+// 2^31 magnitudes on the host (tests/tools/divcheck.c) and sampled on the device by rfid_selftest() and, on crafted
+// numerators around the admission edge, by rfid_selftest_arith (tests/arith_cases.py).
 // div_const_ok() admits |x| in [2^-100, inf) and +0; anything else (tiny, -0, inf, NaN) sends the
 // whole wave through wv::fdiv.
 RFID_DEVICE bool div_const_ok(float x) {
@@ -319,6 +320,10 @@ RFID_DEVICE float div_const(float x) {   // wave-uniform choice of the path
 }
 
 // In-order sum: returns in lane L the value  (((carry + x_0) + x_1) + ...) + x_L.
+// (The shift brings +0 in front of lane 0 at every step, and +0 + x is x for every x but -0: a partial sum that is -0 -- the
+// carry and every addend so far -0 -- comes back as +0 in lanes 0 .. 62, while lane 63, the next carry, keeps it.  No kernel
+// passes a carry of -0: avg_ampl and dc_est start from +0, and a binary32 sum is -0 only when both operands are.  chain_add2
+// likewise; chain_add2_ends, plain additions, returns the -0.  tests/arith_ref.py: chain_sum.)
 RFID_DEVICE float chain_add(float carry, float x, int lane) {
   const float x0 = (lane == 0) ? (carry + x) : x;
   float p = x0;
@@ -2609,6 +2614,102 @@ RFID_KERNEL(64) void gate_fsm_selftest_kernel(GateFsmSelfTestArgs a) {
     gate_fsm_selftest_one(r.mode, g, r.below, r.above, r.pos, r.nvalid, o);
     a.out_lane[base + lane] = o;
   }
+}
+
+// The arithmetic primitives by themselves (rfid_selftest_arith): one 64-lane workgroup per caller-given record, every routine
+// on the record's operands, every result stored.  A thin caller: nothing of the routines is restated here -- the filter sum
+// goes through gate_fir_step (the filter wave's staging and read-out of the tile), the end sums find their addends in LDS as
+// the back wave holds them.  (chain_add_auto2 has its caller beside its definition: ls2_arith2_selftest_kernel; the plain
+// 25-term loop over the same tile is mf_boxcar25_decim5_kernel's, launched by the entry.)
+struct ArithSelfTestArgs {
+  const rfid_arith_in *in;   // [n]
+  rfid_arith_out *out;       // [n]
+  int n;
+};
+
+RFID_KERNEL(64) void arith_selftest_kernel(ArithSelfTestArgs a) {
+  RFID_SHARED float4 tile4[64 * GATE_RAW_LD];
+  RFID_SHARED float4 ends4[32];
+  const int lane = wv::lane_id();
+  const int k = (int)blockIdx.x;
+  if (k >= a.n) return;
+  const rfid_arith_in *r = a.in + k;
+  rfid_arith_out *o = a.out + k;
+  const float carry = wv::uniform(r->carry), carry_b = wv::uniform(r->carry_b);
+  const int fill = wv::uniform(r->fill);
+  const float x0 = r->x0[lane], x1 = r->x1[lane];
+  const int iv = r->iv[lane];
+  // in-order sums from `carry` over x0
+  o->chain[lane] = chain_add(carry, x0, lane);
+  {
+    float v = 0.0f;
+    const bool ok = chain_add_scan(carry, x0, lane, v);
+    o->scan[lane] = v;
+    if (lane == 0) o->scan_flag = ok ? 1 : 0;
+  }
+  o->autosum[lane] = chain_add_auto(carry, x0, lane);
+  // two consecutive steps from one carry, and what gate_pairs_body takes where the pair scan refuses
+  {
+    float v0 = 0.0f, v1 = 0.0f;
+    const bool ok = chain_add_scan_pair(carry, x0, x1, lane, v0, v1);
+    o->pair0[lane] = v0; o->pair1[lane] = v1;
+    if (lane == 0) o->pair_flag = ok ? 1 : 0;
+    const float f0 = chain_add_auto(carry, x0, lane);
+    const float f1 = chain_add_auto(wv::readlane(f0, 63), x1, lane);
+    o->pair_fb0[lane] = f0; o->pair_fb1[lane] = f1;
+  }
+  // two chains side by side; their end values out of LDS
+  {
+    float pa, pb;
+    chain_add2(carry, x0, carry_b, x1, lane, pa, pb);
+    o->chain2_a[lane] = pa; o->chain2_b[lane] = pb;
+    float *t = reinterpret_cast<float *>(ends4);
+    t[lane] = x0; t[64 + lane] = x1;
+    wv::wave_sync();
+    float cr = carry, ci = carry_b;
+    chain_add2_ends(cr, ci, t, t + 64, lane);
+    if (lane == 0) { o->ends_a = cr; o->ends_b = ci; }
+  }
+  // constant divisions
+  o->div100[lane] = div_const<WIN_LEN>(x0);
+  o->div48[lane] = div_const<DC_LEN>(x0);
+  o->fast100[lane] = div_const_fast<WIN_LEN>(x0);
+  o->fast48[lane] = div_const_fast<DC_LEN>(x0);
+  {
+    const uint64_t bad = div_const_bad(x0), ok = wv::ballot(div_const_ok(x0));
+    if (lane == 0) { o->div_bad = bad; o->div_ok = ok; }
+  }
+  // wave operations
+  o->fdiv[lane] = wv::fdiv(x0, x1);
+  o->hypot[lane] = wv::hypot_f(x0, x1);
+  o->shr1[lane] = wv::shr1(x0);
+  {
+    const float rn = wv::rint_f(x0);
+    o->rint[lane] = rn;
+    if (__builtin_fabsf(x0) < 2147483648.0f) o->f2i[lane] = wv::f2i(rn);
+  }
+  // the matched filter's sum of one step
+  {
+    GateRawRegs rr;
+    const float4 *t4 = reinterpret_cast<const float4 *>(r->tile);   // 170 float4 (records are 16-byte multiples)
+#pragma unroll
+    for (int j = 0; j < GATE_RAW_LD; ++j) {
+      int q = lane + 64 * j;
+      q = (q < 170) ? q : 169;
+      rr.v[j] = t4[q];
+    }
+    const float2 y = gate_fir_step(rr, tile4, lane, false);
+    o->sum25[2 * lane] = y.x; o->sum25[2 * lane + 1] = y.y;
+  }
+  // integer scan and its building blocks
+  o->scan_add[lane] = wv::scan_add(iv);
+  o->row_shr1[lane] = wv::dpp_row_shr<1>(iv, fill);
+  o->row_shr2[lane] = wv::dpp_row_shr<2>(iv, fill);
+  o->row_shr4[lane] = wv::dpp_row_shr<4>(iv, fill);
+  o->row_shr8[lane] = wv::dpp_row_shr<8>(iv, fill);
+  o->row_bcast15[lane] = wv::dpp_row_bcast15(iv, fill);
+  o->row_bcast31[lane] = wv::dpp_row_bcast31(iv, fill);
+  o->wave_shr1[lane] = wv::dpp_wave_shr1(iv, fill);
 }
 
 // =========================================================================================

@@ -1058,6 +1058,17 @@ RFID_KERNEL(64) void ls2_scan2_selftest_kernel(const float *x, float ca, float c
   out[lane] = oa; out[64 + lane] = ob;
   if (lane == 0) out[128] = scanned ? 1.0f : 0.0f;
 }
+// the same on caller-given records (rfid_selftest_arith, beside arith_selftest_kernel): one workgroup per record, the sums
+// from carry / carry_b over x0 and whether the shared scan applied
+RFID_KERNEL(64) void ls2_arith2_selftest_kernel(const rfid_arith_in *in, rfid_arith_out *out, int n) {
+  const int lane = wv::lane_id();
+  const int k = (int)blockIdx.x;
+  if (k >= n) return;
+  float oa, ob;
+  const bool scanned = chain_add_auto2(wv::uniform(in[k].carry), wv::uniform(in[k].carry_b), in[k].x0[lane], lane, oa, ob);
+  out[k].auto2_a[lane] = oa; out[k].auto2_b[lane] = ob;
+  if (lane == 0) out[k].auto2_flag = scanned ? 1 : 0;
+}
 constexpr int LS2_CHAIN_WAVES = LS2_CHAIN_THREADS / 64;
 
 // The chain of a trace's pieces: every piece's true start from the latest runs; what is not proven goes on the re-run

@@ -120,6 +120,18 @@ GATE_FSM_OUT_DTYPE = np.dtype([("n_samples", "<i4"), ("signal_state", "<i4"), ("
                                ("open_lane", "<i4"), ("open_type", "<i4"), ("reserved_", "<i4"), ("closedmask", "<u8"),
                                ("openmask", "<u8")])
 assert GATE_FSM_IN_DTYPE.itemsize == 56 and GATE_FSM_OUT_DTYPE.itemsize == 64
+# rfid_selftest_arith: the operands of one wave, and what every arithmetic primitive made of them
+ARITH_IN_DTYPE = np.dtype([("carry", "<f4"), ("carry_b", "<f4"), ("fill", "<i4"), ("reserved_", "<i4"), ("x0", "<f4", (64,)),
+                           ("x1", "<f4", (64,)), ("iv", "<i4", (64,)), ("tile", "<f4", (680,))])
+ARITH_OUT_DTYPE = np.dtype([(k, "<f4", (64,)) for k in ("chain", "scan", "autosum", "pair0", "pair1", "pair_fb0", "pair_fb1", "auto2_a",
+                                                          "auto2_b", "chain2_a", "chain2_b", "div100", "div48", "fast100", "fast48",
+                                                          "fdiv", "hypot", "shr1", "rint")] +
+                           [("f2i", "<i4", (64,)), ("sum25", "<f4", (128,)), ("mf", "<f4", (128,))] +
+                           [(k, "<i4", (64,)) for k in ("scan_add", "row_shr1", "row_shr2", "row_shr4", "row_shr8", "row_bcast15",
+                                                         "row_bcast31", "wave_shr1")] +
+                           [("div_bad", "<u8"), ("div_ok", "<u8"), ("scan_flag", "<i4"), ("pair_flag", "<i4"), ("auto2_flag", "<i4"),
+                            ("reserved_", "<i4"), ("ends_a", "<f4"), ("ends_b", "<f4")])
+assert ARITH_IN_DTYPE.itemsize == 3504 and ARITH_OUT_DTYPE.itemsize == 8232
 assert WINDOW_DTYPE.itemsize == 24 and RESULT_DTYPE.itemsize == 48
 assert SCORES_DTYPE.itemsize == 144 and STATS_DTYPE.itemsize == 1056
 
@@ -151,6 +163,7 @@ SIGNATURES = {
     "rfid_version": (C.c_char_p, []),
     "rfid_selftest": (_i, [_vp, _ip]),
     "rfid_selftest_gate_fsm": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "rfid_selftest_arith": (_i, [_vp, _vp, _i, _vp]),
     "rfid_selftest_stats": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "rfid_selftest_inventory": (_i, [_vp] * 5 + [_i] * 5 + [_i64, _i64] + [_vp] * 10),
     "rfid_mf_work": (_i, [_vp, _vp, _i, _vp, _i, _ip]),

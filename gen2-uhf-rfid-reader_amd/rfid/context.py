@@ -69,6 +69,16 @@ class Context:
             self._chk(self._lib.rfid_selftest_gate_fsm(self._h, rec.ctypes.data, len(rec), ow.ctypes.data, ol.ctypes.data))
         return ow, ol
 
+    def selftest_arith(self, records, prefill: int = 0) -> np.ndarray:
+        """rfid_selftest_arith: every arithmetic primitive on each ARITH_IN_DTYPE record (one wave's operands) -> len(records) + 1
+        ARITH_OUT_DTYPE records whose every byte started as `prefill` (0 .. 255); the last one is the guard behind the records
+        written.  A test entry: nothing is judged here."""
+        rec = np.ascontiguousarray(records, dtype=capi.ARITH_IN_DTYPE)
+        out = np.full((len(rec) + 1) * capi.ARITH_OUT_DTYPE.itemsize, prefill, dtype=np.uint8).view(capi.ARITH_OUT_DTYPE)
+        if len(rec):
+            self._chk(self._lib.rfid_selftest_arith(self._h, rec.ctypes.data, len(rec), out.ctypes.data))
+        return out
+
     def selftest_stats(self, results, wcount, waves: int, from_summaries: bool, max_slot_number: int, max_num_queries: int,
                        number_unique_tags: int, out=None) -> np.ndarray:
         """rfid_selftest_stats: the statistics kernel by itself on a [n_streams][wmax] table of RESULT_DTYPE records, `waves`

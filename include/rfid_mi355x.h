@@ -496,6 +496,45 @@ typedef struct {
   uint64_t closedmask, openmask;
 } rfid_gate_fsm_out;
 
+/* The arithmetic primitives by themselves (rfid_selftest_arith): the operands of one 64-lane wave -- lane L takes x0[L], x1[L],
+ * iv[L]; tile holds the 5 * 63 + 25 complex samples (re, im interleaved) of one matched-filter step ... */
+typedef struct {
+  float carry, carry_b;     /* the carries of the in-order sums */
+  int32_t fill;             /* what the DPP building blocks leave in lanes without a source */
+  int32_t reserved_;
+  float x0[64], x1[64];
+  int32_t iv[64];
+  float tile[680];
+} rfid_arith_in;
+/* ... and what every routine made of them.  Flags are 0 / 1, vote masks have bit L = lane L.  Every field is stored over what
+ * the caller put there, except f2i[L] where |x0[L]| >= 2^31 and reserved_, which keep the caller's words. */
+typedef struct {
+  float chain[64];          /* chain_add(carry, x0) */
+  float scan[64];           /* chain_add_scan(carry, x0): the value as returned, whatever scan_flag says */
+  float autosum[64];        /* chain_add_auto(carry, x0) */
+  float pair0[64], pair1[64];       /* chain_add_scan_pair(carry, x0, x1), as returned */
+  float pair_fb0[64], pair_fb1[64]; /* what the pair body falls back to: chain_add_auto(carry, x0), then from its lane 63 over x1 */
+  float auto2_a[64], auto2_b[64];   /* chain_add_auto2(carry, carry_b, x0) */
+  float chain2_a[64], chain2_b[64]; /* chain_add2(carry, x0, carry_b, x1) */
+  float div100[64], div48[64];      /* div_const<100>(x0), div_const<48>(x0) */
+  float fast100[64], fast48[64];    /* div_const_fast<100>(x0), div_const_fast<48>(x0), unguarded */
+  float fdiv[64];           /* wv::fdiv(x0, x1) */
+  float hypot[64];          /* wv::hypot_f(x0, x1) */
+  float shr1[64];           /* wv::shr1(x0) */
+  float rint[64];           /* wv::rint_f(x0) */
+  int32_t f2i[64];          /* wv::f2i(rint[L]) where |x0[L]| < 2^31 */
+  float sum25[128];         /* wv::lds_sum25_in_order(&tile[5 L]) from the tile staged in LDS as the filter wave stages it: re, im of lane L at [2 L], [2 L + 1] */
+  float mf[128];            /* the stage kernel's (mf_boxcar25_decim5_kernel) plain 25-term loop over the same tile, likewise */
+  int32_t scan_add[64];     /* wv::scan_add(iv) */
+  int32_t row_shr1[64], row_shr2[64], row_shr4[64], row_shr8[64];   /* wv::dpp_row_shr<N>(iv, fill) */
+  int32_t row_bcast15[64], row_bcast31[64], wave_shr1[64];          /* wv::dpp_row_bcast15 / 31, wv::dpp_wave_shr1 (iv, fill) */
+  uint64_t div_bad;         /* div_const_bad(x0) */
+  uint64_t div_ok;          /* the vote of div_const_ok(x0) */
+  int32_t scan_flag, pair_flag, auto2_flag;   /* what chain_add_scan, chain_add_scan_pair, chain_add_auto2 returned */
+  int32_t reserved_;
+  float ends_a, ends_b;     /* chain_add2_ends from (carry, carry_b) over x0 / x1 staged in LDS */
+} rfid_arith_out;
+
 typedef struct rfid_ctx rfid_ctx;
 
 /* ---- lifetime ------------------------------------------------------------------------ */
@@ -510,7 +549,7 @@ RFID_API const char *rfid_strerror(int status);
 RFID_API const char *rfid_last_error(const rfid_ctx *ctx);
 RFID_API const char *rfid_version(void);
 /* RFID_MI355X_ABI of the library that was loaded: it changes whenever a struct of this header changes size or layout
- * (4: rfid_ls_report has 13 fields since round 3; 5: its last field is dc_finished since round 6; 6: rfid_repair and the repair stage; 7: rfid_window_moments and the slots stage; still 7 with rfid_command and the commands stage, which only add functions and one struct, and with the test entry rfid_selftest_inventory, a function).  A caller built against another value must not pass structs. */
+ * (4: rfid_ls_report has 13 fields since round 3; 5: its last field is dc_finished since round 6; 6: rfid_repair and the repair stage; 7: rfid_window_moments and the slots stage; still 7 with rfid_command and the commands stage, which only add functions and one struct, and with the test entries rfid_selftest_inventory, a function, and rfid_selftest_arith, a function and two structs of its own).  A caller built against another value must not pass structs. */
 RFID_API int rfid_abi_version(void);
 /* device self-test of the wave-level primitives the kernels rely on (DPP wave shift,
  * IEEE division, double sqrt).  0 = all good, >0 = number of failing checks. */
@@ -520,6 +559,13 @@ RFID_API int rfid_selftest(rfid_ctx *ctx, int *n_failed);
  * caller holds the expected values (tests/gate_ref.py); nothing is judged here. */
 RFID_API int rfid_selftest_gate_fsm(rfid_ctx *ctx, const rfid_gate_fsm_in *in, int n, rfid_gate_fsm_out *out_wave,
                                     rfid_gate_fsm_out *out_lane);
+/* test entry: the arithmetic primitives under every kernel -- the in-order binary32 sums and their integer-scan shortcuts, the
+ * three-instruction constant divisions and their admission votes, wv::fdiv / hypot_f / shr1 / rint_f / f2i, the matched filter's
+ * in-order sum out of LDS, the integer wave scan and its DPP building blocks -- on `n` caller-given records (host memory), one
+ * 64-lane workgroup per record.  out[n + 1] is copied to the device before the launches and back after them: every field is
+ * stored over the caller's prefill, and out[n], a guard record, must come back as it went.  The caller holds the expected
+ * values (tests/arith_ref.py); nothing is judged here. */
+RFID_API int rfid_selftest_arith(rfid_ctx *ctx, const rfid_arith_in *in, int n, rfid_arith_out *out);
 /* test entry: the per-trace statistics kernel by itself on a caller-given result table res[n_streams][wmax] (host memory;
  * wcount[s] <= wmax records of row s count), one workgroup of `waves` (1 .. 16) wavefronts per trace -- the batch path launches
  * 1, or 16 for wmax > 2048.  from_summaries != 0: the kernel reads the results' one-word summaries, made on the device as the

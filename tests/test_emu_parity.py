@@ -116,6 +116,9 @@ def test_emulated_primitives(emu_mod):
         assert chain[i] == acc
     assert np.array_equal(div, num / den)
     assert np.array_equal(shr[1:], x[:-1]) and shr[0] == 0
+    # hypot(num, x): glibc's formula -- the double sum of the exact squares, its correctly rounded root, one cast
+    want = np.sqrt(num.astype(np.float64) ** 2 + x.astype(np.float64) ** 2).astype(np.float32)
+    assert np.array_equal(hyp.view(np.uint32), want.view(np.uint32))
 
 
 @pytest.mark.parametrize("chunk", [512, 1536, 777])
