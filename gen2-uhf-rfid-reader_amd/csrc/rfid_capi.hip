@@ -32,6 +32,7 @@
 #include "rfid_fine.hpp"
 #include "rfid_retune.hpp"
 #include "rfid_lengths.hpp"
+#include "rfid_diversity.hpp"
 #include "rfid_collide.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
@@ -88,6 +89,7 @@ struct RfidKnobs {
   int retune_wgs = 0;      // RFID_RETUNE_WGS        1..65536: most single-wave workgroups of the retune stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
   int collide_wgs = 0;     // RFID_COLLIDE_WGS       1..65536: most single-wave workgroups of the collisions stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
   int lengths_wgs = 0;     // RFID_LENGTHS_WGS       1..65536: most single-wave workgroups of the lengths stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
+  int diversity_wgs = 0;   // RFID_DIVERSITY_WGS     1..65536: most single-wave workgroups of the diversity stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
 };
 
 // the timing events of a pass: stage i of the four took the time from event i to event i + 1
@@ -303,7 +305,7 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
-  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths.  What the ten share ----
+  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths, diversity.  What the eleven share ----
   struct Stage {
     void *blk = nullptr;              // one allocation, carved up (stage_alloc)
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
@@ -324,7 +326,7 @@ struct rfid_ctx {
     int64_t *d_off = nullptr;         // [B_plan x max_tags + 1]
     int *d_base = nullptr, *d_head = nullptr;
   } trk;
-  // ---- the eight window-table stages: one [B_plan][rows] table of fixed-size records each (csrc/rfid_stage.hpp) ----
+  // ---- the nine window-table stages: one [B_plan][rows] table of fixed-size records each -- the diversity stage: [B_plan / members][rows] -- (csrc/rfid_stage.hpp) ----
   struct Table : Stage {
     void *d_table = nullptr;          // [B_plan][rows] records of the stage's type
     template <typename R> R *table() const { return static_cast<R *>(d_table); }
@@ -358,12 +360,17 @@ struct rfid_ctx {
   struct Lengths : Table {
     int blocks = 0;                   // ceil(rows / LEN_ROWS)
   } len;
+  // diversity (rfid_batch_plan_diversity): lives and dies with the plan; needs the pass's statistics only.  Its table's rows are GROUPS' rows
+  struct Diversity : Table {
+    int blocks = 0;                   // ceil(rows / DIV_ROWS)
+    int members = 0;                  // traces per group
+  } dvs;
   // fine (rfid_batch_plan_fine): lives and dies with the tracks workspace
   struct Fine : Table {
     rfid_read_fine *d_packed = nullptr;     // [trk.cap]: aligned with the tracks
   } fin;
   // What the per-call forms (rfid_repair_window, rfid_window_moments_of, rfid_commands_of, rfid_fine_window, rfid_retune_window, rfid_collisions_of,
-  // rfid_length_window) upload, compute on and download from.  One buffer for the seven: each synchronises c->stream before it returns, so no two of them ever have
+  // rfid_length_window, rfid_diversity_window) upload, compute on and download from.  One buffer for the eight: each synchronises c->stream before it returns, so no two of them ever have
   // work in flight on it, and grow() may free and reallocate it.
   DevBuf one;
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
@@ -426,6 +433,7 @@ const KnobEntry g_knob_table[] = {
   {"retune_wgs", "RFID_RETUNE_WGS", &RfidKnobs::retune_wgs, 0, 65536},
   {"collide_wgs", "RFID_COLLIDE_WGS", &RfidKnobs::collide_wgs, 0, 65536},
   {"lengths_wgs", "RFID_LENGTHS_WGS", &RfidKnobs::lengths_wgs, 0, 65536},
+  {"diversity_wgs", "RFID_DIVERSITY_WGS", &RfidKnobs::diversity_wgs, 0, 65536},
 };
 int clamp_int(long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 // the environment, once per context: values out of range are clamped, anything that is not a number is ignored
@@ -509,7 +517,7 @@ void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
 // `stage` and everything behind it no longer belong to the last pass
 void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
 
-// ---- what the inventory, tracks, quality, repair, slots, commands, fine, retune, collisions and lengths stages share on the host ----
+// ---- what the inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths and diversity stages share on the host ----
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void stage_free(rfid_ctx::Stage &st) {
@@ -754,6 +762,7 @@ void free_plan(rfid_ctx *c) {
   table_free(c->ret);
   table_free(c->col);
   table_free(c->len);
+  table_free(c->dvs);
   invalidate_from(c, rfid_ctx::CUR_STATS);
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
@@ -784,7 +793,7 @@ int join_tails(rfid_ctx *c) {
   return RFID_OK;
 }
 
-// ---- the eight window-table stages (quality, repair, slots, commands, fine, retune, collisions, lengths): what their plan, enqueue and get functions share ----
+// ---- the nine window-table stages (quality, repair, slots, commands, fine, retune, collisions, lengths, diversity): what their plan, enqueue and get functions share ----
 // A stage's description: what its checks ask for and how its messages name it.
 struct TableStage {
   const char *name;      // as in rfid_batch_<name>
@@ -801,6 +810,7 @@ constexpr TableStage ST_FINE = {"fine", true, true, rfid_ctx::CUR_TRACKS, true, 
 constexpr TableStage ST_RETUNE = {"retune", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
 constexpr TableStage ST_COLLISIONS = {"collisions", false, false, rfid_ctx::CUR_STATS, false, "RN16 windows"};
 constexpr TableStage ST_LENGTHS = {"lengths", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
+constexpr TableStage ST_DIVERSITY = {"diversity", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
 
 bool table_needs_met(const rfid_ctx *c, const TableStage &d) { return (!d.inv || c->inv.blk) && (!d.trk || c->trk.blk); }
 
@@ -1398,7 +1408,7 @@ int rfid_ctx_destroy(rfid_ctx *c) {
     if (e) (void)hipEventDestroy(e);
   for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep,
                                (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd, (rfid_ctx::Stage *)&c->fin, (rfid_ctx::Stage *)&c->ret,
-                               (rfid_ctx::Stage *)&c->col, (rfid_ctx::Stage *)&c->len})
+                               (rfid_ctx::Stage *)&c->col, (rfid_ctx::Stage *)&c->len, (rfid_ctx::Stage *)&c->dvs})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
@@ -2605,6 +2615,77 @@ int rfid_length_window(rfid_ctx *c, const rfid_cf32 *span, int n, const rfid_dec
   HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(lengths_one_kernel, dim3(1), dim3(64), 0, c->stream, (const float2 *)b, n, (const rfid_decode_result *)(b + sz_w),
                      (rfid_sized_frame *)(b + sz_w + sz_r));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
+}
+
+// ---- diversity stage: the EPC windows of every group of traces recorded together, combined before the sign is taken, behind the statistics of a pass (csrc/rfid_diversity.hpp) ----
+int rfid_batch_plan_diversity(rfid_ctx *c, int members) {
+  if (!c) return RFID_ERR_INVALID;
+  if (members < 2 || members > DIV_MAX) return failf(c, RFID_ERR_INVALID, "rfid_batch_plan_diversity: a group holds 2 to %d traces", DIV_MAX);
+  rfid_ctx::Diversity &p = c->dvs;
+  const int rows = (c->wmax + 1) / 2;      // EPC windows are every other window
+  const int groups = (c->B_plan >= members) ? c->B_plan / members : 1;
+  const int r = table_plan(c, p, ST_DIVERSITY, rows,
+                           {{&p.d_table, sizeof(rfid_diversity) * (size_t)rows * (size_t)groups},
+                            {(void **)&p.d_nrows, sizeof(int) * (size_t)groups}});
+  if (r) return r;
+  p.blocks = (rows + DIV_ROWS - 1) / DIV_ROWS;
+  p.members = members;
+  return RFID_OK;
+}
+
+int rfid_batch_diversity(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Diversity &p = c->dvs;
+  if (c->B && p.blk && c->B % p.members)
+    return failf(c, RFID_ERR_INVALID, "rfid_batch_diversity: the pass's %d traces are no whole groups of %d", c->B, p.members);
+  int n = 0;
+  DivArgs a;
+  { int r = table_begin(c, p, ST_DIVERSITY, &n, &a.p); if (r) return r; }
+  a.members = p.members; a.groups = n / p.members;
+  a.rows = p.rows; a.blocks = p.blocks; a.table = p.table<rfid_diversity>(); a.nrows = p.d_nrows;
+  // a window is never read behind its trace: the lengths of the pass (as its gate scan had them)
+  a.lens = c->d_lens; a.n_dec = c->last_n_raw / DECIM;
+  // single-wave workgroups, each walking blocks of eight rows of a group (10.7 KB of LDS each)
+  const int64_t items = (int64_t)a.groups * p.blocks;
+  const int64_t most = c->knobs.diversity_wgs ? (int64_t)c->knobs.diversity_wgs : (int64_t)c->n_cus * DIV_WGS_PER_CU;
+  hipLaunchKernelGGL(diversity_kernel, persistent_grid(items, most), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return table_end(c, p, a.groups);
+}
+
+int rfid_batch_get_window_diversity(rfid_ctx *c, int group, rfid_diversity *out, int64_t cap, int64_t *n) {
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->dvs, ST_DIVERSITY, "rfid_batch_get_window_diversity", sizeof(*out), group, out, cap, n);
+}
+
+int rfid_batch_diversity_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  return stage_ms(c, c->dvs, ms);
+}
+
+// the per-call form: one row's windows in host memory through the batch kernel's device functions (one launch, synchronising)
+int rfid_diversity_window(rfid_ctx *c, const rfid_cf32 *spans, int members, const rfid_decode_result *res, rfid_diversity *out) {
+  if (!c || !spans || !res || !out) return RFID_ERR_INVALID;
+  if (members < 2 || members > DIV_MAX) return failf(c, RFID_ERR_INVALID, "rfid_diversity_window: a group holds 2 to %d members", DIV_MAX);
+  for (int m = 0; m < members; ++m) {
+    if (res[m].type != RFID_DECODE_EPC) return failf(c, RFID_ERR_INVALID, "rfid_diversity_window: member %d: not the result of an EPC window", m);
+    if (res[m].index < 65 || res[m].index > 65 + N_SYNC - 1)
+      return failf(c, RFID_ERR_INVALID, "rfid_diversity_window: member %d: the result's index is no sync offset (65 .. 79)", m);
+    if (!(res[m].T >= DIV_T_LO && res[m].T <= DIV_T_HI))
+      return failf(c, RFID_ERR_INVALID, "rfid_diversity_window: member %d: the result's T is none of the decoder's (4.94999981 .. 5.05000019)", m);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_w = up256(sizeof(float2) * (size_t)EPC_WIN * (size_t)DIV_MAX), sz_r = up256(sizeof(rfid_decode_result) * (size_t)DIV_MAX);
+  { int r = grow(c, c->one, sz_w + sz_r + sizeof(rfid_diversity)); if (r) return r; }
+  char *b = (char *)c->one.p;
+  HIPCHK(c, hipMemcpyAsync(b, spans, sizeof(float2) * (size_t)EPC_WIN * (size_t)members, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res) * (size_t)members, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(diversity_one_kernel, dim3(1), dim3(64), 0, c->stream, (const float2 *)b, members, (const rfid_decode_result *)(b + sz_w),
+                     (rfid_diversity *)(b + sz_w + sz_r));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -112,6 +112,11 @@ SIZED_FRAME_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"
                               ("crc_rcvd", "<i4"), ("crc_calc", "<i4"), ("frame", "<u4", (5,)), ("reserved_", "<i4", (3,))])
 LENGTHS_SPAN, LENGTHS_MAX_WORDS = 1728, 8
 assert SIZED_FRAME_DTYPE.itemsize == 64
+DIVERSITY_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("flags", "<i4"), ("present", "<i4"), ("reads", "<i4"),
+                            ("frame", "<u4", (4,)), ("crc_rcvd", "<i4"), ("crc_calc", "<i4"), ("h_sq", "<f4"), ("margin_min", "<f4"),
+                            ("weakest", "<i4"), ("reserved_", "<i4")])
+DIVERSITY_MAX_MEMBERS, DIVERSITY_SLACK = 8, 4
+assert DIVERSITY_DTYPE.itemsize == 64
 GATE_FSM_IN_DTYPE = np.dtype([("mode", "<i4"), ("n_samples", "<i4"), ("signal_state", "<i4"), ("num_pulses", "<i4"),
                               ("gate_open", "<i4"), ("n_to_ungate", "<i4"), ("wtype", "<i4"), ("nvalid", "<i4"), ("pos", "<i4"),
                               ("reserved_", "<i4"), ("below", "<u8"), ("above", "<u8")])
@@ -258,6 +263,11 @@ SIGNATURES = {
     "rfid_batch_get_window_lengths": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_lengths_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_length_window": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "rfid_batch_plan_diversity": (_i, [_vp, _i]),
+    "rfid_batch_diversity": (_i, [_vp]),
+    "rfid_batch_get_window_diversity": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_diversity_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_diversity_window": (_i, [_vp, _vp, _i, _vp, _vp]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

@@ -61,6 +61,8 @@ class BatchDecoder:
         self.last_collisions = None   # one collisions array per trace (every RN16 window before the cut-off) of the last decode(..., collisions=True)
         self._len_planned = False
         self.last_lengths = None      # one sized-frame array per trace (every EPC window before the cut-off) of the last decode(..., lengths=True)
+        self._div_members = 0         # (the group size the diversity workspace was planned for; 0: none)
+        self.last_diversity = None    # one diversity array per GROUP (every EPC window before its anchor's cut-off) of the last decode(..., diversity=M)
 
     def close(self) -> None:
         self.ctx.close()
@@ -81,6 +83,7 @@ class BatchDecoder:
             self._ret_planned = False
             self._col_planned = False
             self._len_planned = False
+            self._div_members = 0
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -92,7 +95,7 @@ class BatchDecoder:
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
                inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False,
                repair: bool = False, slots: bool = False, commands: bool = False, fine: bool = False,
-               retune: bool = False, collisions: bool = False, lengths: bool = False):
+               retune: bool = False, collisions: bool = False, lengths: bool = False, diversity: int = 0):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
@@ -123,9 +126,17 @@ class BatchDecoder:
         those of the collided slots and tells two tags from more); nothing else changes.  lengths=True (implies nothing): the
         CRC-failed EPC windows are read again behind the pass at the length their own PC word announces (the decoder takes every
         reply for a 96-bit EPC); `self.last_lengths` keeps one capi.SIZED_FRAME_DTYPE array per trace, a record per EPC window
-        (sized_frame_fields() turns one into PC, EPC and its length); such a frame is not a read and changes nothing else."""
+        (sized_frame_fields() turns one into PC, EPC and its length); such a frame is not a read and changes nothing else.
+        diversity=M, 2 .. 8 (implies nothing): the traces are groups of M consecutive ones -- the receive antennas of one session, each
+        group's first the anchor; len(traces) must be a multiple of M -- and the EPC windows no antenna read are decided again behind
+        the pass from the antennas' summed decision values; `self.last_diversity` keeps one capi.DIVERSITY_DTYPE array per GROUP, a
+        record per EPC window of its anchor (diversity_fields() turns it into flags, member lists and the summed channel power); a
+        combined frame is not a read and changes nothing else."""
         torch = self._torch
         n = len(traces)
+        diversity = int(diversity)
+        if diversity and n % diversity:
+            raise ValueError("diversity: %d traces are no whole groups of %d" % (n, diversity))
         lens = np.array([len(t) for t in traces], dtype=np.int64)
         max_len = int(lens.max()) if n else 0
         if n == 0 or max_len == 0:
@@ -178,6 +189,9 @@ class BatchDecoder:
         if lengths and not self._len_planned:
             self.ctx.batch_plan_lengths()
             self._len_planned = True
+        if diversity and self._div_members != diversity:
+            self.ctx.batch_plan_diversity(diversity)
+            self._div_members = diversity
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
         if inventory:
             self.ctx.batch_inventory_enqueue()
@@ -199,6 +213,8 @@ class BatchDecoder:
             self.ctx.batch_collisions_enqueue()
         if lengths:
             self.ctx.batch_lengths_enqueue()
+        if diversity:
+            self.ctx.batch_diversity_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
@@ -221,6 +237,8 @@ class BatchDecoder:
             self.last_collisions = [self.ctx.batch_window_collisions(b) for b in range(n)]
         if lengths:
             self.last_lengths = [self.ctx.batch_window_lengths(b) for b in range(n)]
+        if diversity:
+            self.last_diversity = [self.ctx.batch_window_diversity(g) for g in range(n // diversity)]
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -542,6 +560,66 @@ def format_lengths_csv(rows: Sequence[np.ndarray], names: Sequence[str], results
     return "\n".join(lines) + "\n"
 
 
+DIVERSITY_HEADER = "file,epc,pc,seq,t_s,members,h_db,margin_min,weakest,known"
+
+
+def diversity_fields(rows: np.ndarray) -> dict:
+    """rfid_diversity records -> a dict, one value per record: read (flags bit 0: a present member read the window itself), recovered
+    (bit 1: the combined frame passes its CRC), lone (bit 2), combined (neither bit 0 nor bit 2: the members' decision values were
+    added), in binary64 h_db = 10 log10 h_sq, the members' summed channel power (nan where nothing was combined), and the lists of
+    member indices behind the two masks: members (present) and readers (reads)."""
+    rows = np.asarray(rows)
+    flags = rows["flags"]
+    combined = (flags & 5) == 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        h_db = np.where(combined, 10.0 * np.log10(rows["h_sq"].astype(np.float64)), np.nan)
+    of = lambda mask: [m for m in range(capi.DIVERSITY_MAX_MEMBERS) if (int(mask) >> m) & 1]
+    return dict(read=(flags & 1) != 0, recovered=(flags & 2) != 0, lone=(flags & 4) != 0, combined=combined, h_db=h_db,
+                members=[of(p) for p in rows["present"]], readers=[of(p) for p in rows["reads"]])
+
+
+def diversity_known(rows: np.ndarray, entries_of_members: Sequence[np.ndarray]) -> np.ndarray:
+    """Host side: per record of one group's diversity rows, whether it was recovered AND the inventory of at least one member
+    (`entries_of_members`: each member's capi.TAG_ENTRY_DTYPE records, Context.batch_inventory) holds the combined frame."""
+    rows = np.asarray(rows)
+    have = {bytes(np.ascontiguousarray(f)) for ent in entries_of_members for f in np.asarray(ent)["frame"]}
+    return np.array([bool(r["flags"] & 2) and bytes(np.ascontiguousarray(r["frame"])) in have for r in rows], dtype=bool)
+
+
+def format_diversity(rows: np.ndarray, entries_of_members: Sequence[np.ndarray]) -> str:
+    """One line for one group's EPC windows before its anchor's cut-off (Context.batch_window_diversity) and its members' inventories:
+    how many windows, how many at least one antenna read, how many none read, how many of those the combination recovers, how many
+    distinct EPCs those are and how many of them no member's inventory holds -- tags no antenna saw at all."""
+    rows = np.asarray(rows)
+    f = diversity_fields(rows)
+    got = f["recovered"]
+    known = diversity_known(rows, entries_of_members)
+    frames = {bytes(np.ascontiguousarray(r["frame"])) for r in rows[got]}
+    new = {bytes(np.ascontiguousarray(r["frame"])) for r in rows[got & ~known]}
+    return ("| EPC windows : %d  read by an antenna : %d  read by none : %d  recovered by combining : %d  distinct EPCs : %d  "
+            "in no antenna's inventory : %d\n" % (len(rows), int(f["read"].sum()), int((~f["read"]).sum()), int(got.sum()), len(frames), len(new)))
+
+
+def format_diversity_csv(rows: Sequence[np.ndarray], entries_of_members: Sequence[Sequence[np.ndarray]], names: Sequence[str]) -> str:
+    """CSV text, one line per recovered window, by group, then by seq: file,epc,pc,seq,t_s,members,h_db,margin_min,weakest,known.
+    rows[g]: the rfid_diversity records of group g; entries_of_members[g]: its members' inventories; names[g]: its ANCHOR's file.
+    epc / pc of the COMBINED frame, t_s = start / 400e3 as in the tracks CSV (the anchor's), members: the present members' indices
+    joined by +, h_db with %.4f, margin_min with %.9g (a binary32 value survives the round trip), known: 1 when a member's
+    inventory holds the frame."""
+    lines = [DIVERSITY_HEADER]
+    for rec, ents, name in zip(rows, entries_of_members, names):
+        rec = np.asarray(rec)
+        f = diversity_fields(rec)
+        known = diversity_known(rec, ents)
+        for k in np.flatnonzero(f["recovered"]):
+            r = rec[k]
+            pc, epc = frame_fields(r["frame"])
+            lines.append("%s,%s,%04x,%d,%.9g,%s,%.4f,%.9g,%d,%d" %
+                         (name, epc, pc, int(r["seq"]), int(r["start"]) / TRACKS_RATE, "+".join(map(str, f["members"][k])),
+                          float(f["h_db"][k]), float(r["margin_min"]), int(r["weakest"]), int(known[k])))
+    return "\n".join(lines) + "\n"
+
+
 MOMENTS_N = 240           # RFID_MOMENTS_SAMPLES: the samples of a window its moments are taken over
 SLOT_EMPTY, SLOT_SINGLE, SLOT_COLLIDED, SLOT_UNKNOWN = 0, 1, 2, -1
 SCHOUTE = 2.39            # Schoute's estimate of the tags behind a collided slot of a framed-ALOHA round
@@ -784,7 +862,7 @@ def format_commands_csv(rows: Sequence[np.ndarray], starts: Sequence[np.ndarray]
 
 
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] [--collisions OUT.csv] [--lengths OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] [--collisions OUT.csv] [--lengths OUT.csv] [--antennas M --diversity OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -825,8 +903,17 @@ def main(argv=None) -> int:
                     help="read the CRC-failed EPC windows again at the length their own PC word announces (built on the device): "
                          "finds tags whose EPC is not the 96 bits the decoder takes every reply for; one line per file, the windows "
                          "that pass to this CSV file")
+    ap.add_argument("--diversity", metavar="OUT.csv", default=None,
+                    help="combine the EPC windows of traces recorded together -- the receive antennas of one reader session -- before "
+                         "the sign is taken (built on the device): reads tags too weak for every antenna alone; one line per group, "
+                         "the recovered windows to this CSV file; implies --inventory")
+    ap.add_argument("--antennas", metavar="M", type=int, default=2,
+                    help="with --diversity: the files are given capture by capture, each capture's M antennas in order (2..8, "
+                         "default 2); the first of each is the anchor")
     args = ap.parse_args(argv)
-    if args.tracks or args.repair or args.retune:
+    if args.diversity and (not 2 <= args.antennas <= capi.DIVERSITY_MAX_MEMBERS or len(args.files) % args.antennas):
+        ap.error("--diversity: the files must be whole captures of --antennas M = 2..%d files each" % capi.DIVERSITY_MAX_MEMBERS)
+    if args.tracks or args.repair or args.retune or args.diversity:
         args.inventory = True
     dec = BatchDecoder(device=args.device, fixed_q=args.fixed_q, max_num_queries=args.max_queries)
     try:
@@ -835,7 +922,7 @@ def main(argv=None) -> int:
                                             tracks=bool(args.tracks), quality=args.quality, repair=bool(args.repair),
                                             slots=bool(args.slots), commands=bool(args.commands), fine=args.fine,
                                             retune=bool(args.retune), collisions=bool(args.collisions),
-                                            lengths=bool(args.lengths))
+                                            lengths=bool(args.lengths), diversity=args.antennas if args.diversity else 0)
         collided = ([classify_collisions(c, classify_slots(m)) for c, m in zip(dec.last_collisions, dec.last_slots)]
                     if args.collisions else None)
         per_trace = lambda entries, counts: np.split(entries, np.cumsum(counts)[:-1]) if len(counts) else []
@@ -858,6 +945,8 @@ def main(argv=None) -> int:
                 print(format_collisions(collided[i]), end="")
             if args.lengths:
                 print(format_lengths(dec.last_lengths[i]), end="")
+            if args.diversity and i % args.antennas == 0:           # (the group's line stands with its anchor)
+                print(format_diversity(dec.last_diversity[i // args.antennas], per_trace(*dec.last_inventory)[i:i + args.antennas]), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
               (len(args.files), timing["raw_samples"] / 1e6, timing["total_s"], timing["h2d_s"], timing["gpu_s"]))
         if args.inventory:
@@ -893,6 +982,11 @@ def main(argv=None) -> int:
             by_seq = [results[windows["stream"] == b] for b in range(len(args.files))]              # (ordered by seq)
             with open(args.lengths, "w") as f:
                 f.write(format_lengths_csv(dec.last_lengths, args.files, by_seq))
+        if args.diversity:
+            ents = per_trace(*dec.last_inventory)
+            with open(args.diversity, "w") as f:
+                f.write(format_diversity_csv(dec.last_diversity, [ents[i:i + args.antennas] for i in range(0, len(args.files), args.antennas)],
+                                             args.files[::args.antennas]))
         if args.commands:
             starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
             with open(args.commands, "w") as f:

@@ -704,6 +704,44 @@ class Context:
         self._chk(self._lib.rfid_length_window(self._h, span.ctypes.data, len(span), res.ctypes.data, out.ctypes.data))
         return out[0]
 
+    def batch_plan_diversity(self, members: int) -> None:
+        """Reserves the diversity workspace of the current plan for groups of `members` consecutive traces, 2 .. 8: the receive
+        antennas of one session, the first the anchor (a new plan drops it; no other stage's plan call does, and it needs none of
+        them)."""
+        self._chk(self._lib.rfid_batch_plan_diversity(self._h, int(members)))
+
+    def batch_diversity_enqueue(self) -> None:
+        """Asynchronous: the EPC windows of every group of the last pass combined before the sign is taken, behind its statistics
+        (rfid_batch_diversity).  The pass's stream count must be a multiple of the groups' size and its per-trace lengths still
+        valid."""
+        self._chk(self._lib.rfid_batch_diversity(self._h))
+
+    def batch_window_diversity(self, group: int, extra: int = 0) -> np.ndarray:
+        """One GROUP's row of the diversity table (synchronises): the capi.DIVERSITY_DTYPE record of EVERY EPC window of the group's
+        anchor before its cut-off, in seq order (n_windows_used // 2 of them), of the last batch_diversity_enqueue: flags bit 0 =
+        a present member read it (nothing combined), bit 1 = the combined frame passes its CRC, bit 2 = fewer than two members are
+        present (nothing combined).  extra > 0: up to that many of the table's rows behind them as well (zeroed by the stage)."""
+        return self._window_rows(self._lib.rfid_batch_get_window_diversity, capi.DIVERSITY_DTYPE, group, extra)
+
+    def batch_diversity_ms(self) -> float:
+        return self._stage_ms(self._lib.rfid_batch_diversity_ms)
+
+    def diversity_window(self, spans, results) -> np.ndarray:
+        """The same for the windows of ONE row in host memory (rfid_diversity_window): spans = (members, 1370) DC-free samples,
+        results = the members' capi.RESULT_DTYPE records, 2 .. 8 of them; all members are present.  -> one capi.DIVERSITY_DTYPE
+        record, stream = seq = start = 0."""
+        spans = np.ascontiguousarray(spans, dtype=np.complex64)
+        if spans.ndim != 2 or spans.shape[1] != 1370 or not 2 <= len(spans) <= capi.DIVERSITY_MAX_MEMBERS:
+            raise ValueError("spans must be (members, 1370), 2 to %d members" % capi.DIVERSITY_MAX_MEMBERS)
+        if len(results) != len(spans):
+            raise ValueError("one result per member")
+        res = np.zeros(len(spans), dtype=capi.RESULT_DTYPE)
+        for m, r in enumerate(results):
+            res[m] = r
+        out = np.zeros(1, dtype=capi.DIVERSITY_DTYPE)
+        self._chk(self._lib.rfid_diversity_window(self._h, spans.ctypes.data, len(spans), res.ctypes.data, out.ctypes.data))
+        return out[0]
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

@@ -342,6 +342,30 @@ def make_trace(n_rounds: int = 5, fixed_q: int = 0, tag_ids: Sequence[int] = (0x
     return Trace(samples=np.ascontiguousarray(x, dtype=np.complex64), slots=slots, fixed_q=fixed_q, plan=plan)
 
 
+def make_antennas(leaks: Sequence[complex], hs: Sequence[complex], sigma: float, noise_seeds: Sequence[int], **make_trace_kw):
+    """One reader session as several receive antennas record it -> (one Trace per antenna, the slot truth they share).
+
+    The same session (make_trace's arguments in `make_trace_kw`: its seed, rounds, tags ...; not leak, h, sigma or noise, which
+    are the antennas') is rendered once per antenna with noise=False -- the draws that decide slots, RN16s, EPCs and jitter do
+    not depend on leak or h, so every antenna sees the same commands and replies at the same samples -- with that antenna's
+    leak and h.  Noise of `sigma` is then added from default_rng(noise_seed), one seed per antenna, as add_noise_replicas draws
+    it (sigma = 0: none, the samples are make_trace(noise=False)'s byte for byte)."""
+    if not (len(leaks) == len(hs) == len(noise_seeds)) or not len(leaks):
+        raise ValueError("one leak, one h and one noise seed per antenna")
+    for name in ("leak", "h", "noise"):
+        if name in make_trace_kw:
+            raise ValueError("%s is set per antenna" % name)
+    if make_trace_kw.get("render", True) is not True:
+        raise ValueError("antennas are rendered")
+    traces = []
+    for leak, h, seed in zip(leaks, hs, noise_seeds):
+        t = make_trace(leak=leak, h=h, noise=False, **make_trace_kw)
+        if sigma > 0:
+            t.samples = add_noise_replicas(t.samples, 1, sigma, int(seed))[0]
+        traces.append(t)
+    return traces, traces[0].slots
+
+
 def fst_like_trace(sigma: float = 0.002, seed: int = 7) -> Trace:
     """Stand-in for the reference's missing misc/data/file_source_test: 71 rounds,
     FIXED_Q=0, one tag with id 0x27, one EPC corrupted -> expected print_results:

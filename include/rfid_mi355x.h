@@ -314,6 +314,52 @@ typedef struct rfid_sized_frame {    /* 64 bytes */
   int32_t  reserved_[3];             /* 0 */
 } rfid_sized_frame;
 
+/* what the diversity stage (rfid_batch_diversity, rfid_diversity_window) makes of one EPC window of a GROUP of traces: the receive
+ * antennas of one reader session, recorded together (a two-channel receiver, or several receivers on a common clock).  The decoder's
+ * 128 decisions are the best one receive channel allows; a tag too weak for every antenna alone fails its CRC on each and is absent
+ * from everything else a pass reports.  Adding the antennas' decision values before the sign is taken is maximum-ratio combining and
+ * gains 10 log10 M dB.  The weights are conj(h_est) -- each antenna's own channel estimate, unnormalised: that is maximum-ratio
+ * combining for EQUAL NOISE POWER on every antenna (no noise weighting).  A combined frame is NOT a read: nothing else the library
+ * reports changes.
+ * THE DEFINITION (the contract; binary32 throughout, every operation rounded by itself, no fused multiply-add):
+ *   groups   rfid_batch_plan_diversity(ctx, M), 2 <= M <= RFID_DIVERSITY_MAX_MEMBERS.  The traces of a pass form groups of M consecutive
+ *            rows: group g is traces g M .. g M + M - 1, member m of it trace g M + m.  Member 0 is the ANCHOR.
+ *   rows     row k of group g is the anchor's EPC window seq = 2 k + 1, for every such window before the anchor's TERMINATED cut-off
+ *            (seq < n_windows_used): nrows[g] = n_windows_used(anchor) / 2.  Rows behind it are zero.
+ *   present  member m is present in row k when window 2 k + 1 lies before m's own cut-off, its result's type is RFID_DECODE_EPC and
+ *            |start_m - start_0| <= RFID_DIVERSITY_SLACK filtered samples.  The slack is a definition, not a measurement: the decoder's
+ *            sync absorbs 15 offsets within a window, and gates that opened further apart did not open on the same command edge.  The
+ *            anchor is always present.
+ *   read by some   a present member's own CRC held (type RFID_DECODE_EPC and crc_ok == 1): flags bit 0, `reads` the mask of such members,
+ *            `frame` the four bit words of the lowest of them.  Nothing is combined: every field behind `frame` is 0.
+ *   lone     no present member read it and fewer than two are present: flags bit 2.  Nothing is combined.
+ *   combined neither.  For each present member, in ascending m, with that member's OWN values -- s = y - dc_est of its own window per
+ *            component, its result's T, index, h_re, h_im -- the decoder's decision values (tag_decoder_impl.cc:171-190), j = 0 .. 127:
+ *              ia = (int)((float)j * (2.0f * T) + (float)index),  ib = (int)(((float)(2 j) * T + T) + (float)index), both held inside
+ *              0 .. 1369;  (dx, dy) = s[ia] - s[ib];  r_j = dx * h_re - dy * (-h_im).
+ *            acc_j = r_j of the first present member, then acc_j = acc_j + r_j of each further one in order.  cur_j = acc_j > 0;
+ *            bit_j = (cur_j != cur_(j-1)), cur_(-1) positive.  The decoder's CRC-16 (check_crc, :401-445) over bits 0 .. 111 against
+ *            bits 112 .. 127: flags bit 1 when it holds.  crc_rcvd / crc_calc: the two words compared.  margin_min = min_j |acc_j|,
+ *            weakest = the lowest j attaining it.  h_sq: from 0.0f, over the present members in order, h_sq = h_sq + (h_re * h_re +
+ *            h_im * h_im).
+ * A window with a non-finite sample: unspecified, as its decoding is. */
+#define RFID_DIVERSITY_MAX_MEMBERS 8
+#define RFID_DIVERSITY_SLACK       4   /* filtered samples */
+typedef struct rfid_diversity {      /* 64 bytes */
+  int32_t  stream, seq;              /* the ANCHOR's EPC window (rfid_window::stream / seq) */
+  int32_t  start;                    /* rfid_window::start of that window */
+  int32_t  flags;                    /* bit 0: read by some member (nothing combined); bit 1: the combined frame passes its CRC-16;
+                                        bit 2: lone (nothing combined).  0: combined, and the frame fails */
+  int32_t  present, reads;           /* member masks (bit m: member m): present in this row / present and its own CRC held */
+  uint32_t frame[4];                 /* bit 0: the lowest reader's bits; combined: the combined frame's, packed as
+                                        rfid_decode_result::bits; lone: 0 */
+  int32_t  crc_rcvd, crc_calc;       /* combined: bits 112 .. 127 MSB first / the CRC computed over bits 0 .. 111; else 0 */
+  float    h_sq;                     /* combined: sum of |h_est|^2 over the present members; else 0 */
+  float    margin_min;               /* combined: min |acc_j|; else 0 */
+  int32_t  weakest;                  /* combined: the lowest j with |acc_j| == margin_min; else 0 */
+  int32_t  reserved_;                /* 0 */
+} rfid_diversity;
+
 /* what the collisions stage (rfid_batch_collisions, rfid_collisions_of) works out for one RN16 window: the two RN16s and the two
  * channels of a slot in which two tags replied at once.  The decoder is single-tag by construction (tag_detection_RN16,
  * lib/tag_decoder_impl.cc:114-142, 237-253): decision j is the difference d_j of two adjacent half-bit samples across a bit
@@ -1094,6 +1140,34 @@ RFID_API int rfid_batch_lengths_ms(rfid_ctx *ctx, float *ms);
  * 4.94999981 .. 5.05000019, else RFID_ERR_INVALID.  One launch of the batch kernel's device functions, synchronising.  out:
  * stream = seq = start = 0; flags bit 0 = res->crc_ok (then nothing is done). */
 RFID_API int rfid_length_window(rfid_ctx *ctx, const rfid_cf32 *span, int n, const rfid_decode_result *res, rfid_sized_frame *out);
+/* ---- (2l) batch diversity: the EPC windows of traces recorded together combined before the sign is taken, built on the device -- */
+/* Behind a pass: one rfid_diversity (see its definition above) per EPC window of every group's anchor with seq < n_windows_used in a
+ * device table [n_streams / members][ceil(wmax / 2)] (row = seq >> 1; the rows of a group behind its anchor's cut-off are zeroed:
+ * the table's bytes repeat from pass to pass).  The first stage that looks across traces.  Nothing else a pass reports changes: a
+ * combined frame is not a read.  rfid_batch_plan_diversity reserves the table (64 bytes per possible EPC window of a group) for
+ * groups of `members` traces.  RFID_ERR_INVALID: members outside 2 .. RFID_DIVERSITY_MAX_MEMBERS; RFID_ERR_STATE without a plan;
+ * RFID_ERR_HIP when the allocation fails (the plan and every other workspace stay usable).  A new rfid_batch_plan drops it; it neither
+ * needs nor drops any other stage's workspace, and their plan calls do not drop it. */
+RFID_API int rfid_batch_plan_diversity(rfid_ctx *ctx, int members);
+/* enqueues the diversity stage of the LAST pass behind its statistics (asynchronous, no host synchronisation).  RFID_ERR_STATE: no
+ * diversity workspace, or no pass with statistics yet; RFID_ERR_INVALID, with a message, when the pass's stream count is not a multiple
+ * of `members`.  It needs no inventory and may be enqueued before or behind the other stages: it neither needs nor changes their level.
+ * It reads that pass's matched-filter output -- never behind a trace's own length: the lengths are the pass's (d_lens, which must still
+ * be valid, or n_raw) -- window table, results and statistics on the context's main stream and has rfid_batch_slots' duties there.
+ * ONE table per plan, as rfid_batch_commands. */
+RFID_API int rfid_batch_diversity(rfid_ctx *ctx);
+/* synchronises; one GROUP's row of the table: every EPC window of its anchor before the cut-off in seq order: *n = n_windows_used / 2
+ * of the anchor.  cap as rfid_batch_get_window_quality.  RFID_ERR_STATE before the first rfid_batch_diversity of this plan;
+ * RFID_ERR_INVALID for a group the last rfid_batch_diversity did not cover. */
+RFID_API int rfid_batch_get_window_diversity(rfid_ctx *ctx, int group, rfid_diversity *out, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_diversity (HIP events) */
+RFID_API int rfid_batch_diversity_ms(rfid_ctx *ctx, float *ms);
+/* the same for the windows of ONE row in host memory: the per-call form.  spans: [members][1370] samples, member after member, DC-free
+ * already (dc_est = 0 in the definition); res: [members], the result rfid_decoder_work gave for each member's window.  All members are
+ * present.  RFID_ERR_INVALID: members outside 2 .. RFID_DIVERSITY_MAX_MEMBERS, or a member's result that rfid_length_window would
+ * refuse (type, index 65 .. 79, T inside 4.94999981 .. 5.05000019).  One launch of the batch kernel's device functions,
+ * synchronising.  out: stream = seq = start = 0, present = 2^members - 1. */
+RFID_API int rfid_diversity_window(rfid_ctx *ctx, const rfid_cf32 *spans, int members, const rfid_decode_result *res, rfid_diversity *out);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
