@@ -33,6 +33,7 @@
 #include "rfid_retune.hpp"
 #include "rfid_lengths.hpp"
 #include "rfid_diversity.hpp"
+#include "rfid_match.hpp"
 #include "rfid_collide.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
@@ -90,6 +91,7 @@ struct RfidKnobs {
   int collide_wgs = 0;     // RFID_COLLIDE_WGS       1..65536: most single-wave workgroups of the collisions stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
   int lengths_wgs = 0;     // RFID_LENGTHS_WGS       1..65536: most single-wave workgroups of the lengths stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
   int diversity_wgs = 0;   // RFID_DIVERSITY_WGS     1..65536: most single-wave workgroups of the diversity stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
+  int match_wgs = 0;       // RFID_MATCH_WGS         1..65536: most single-wave workgroups of the match stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
 };
 
 // the timing events of a pass: stage i of the four took the time from event i to event i + 1
@@ -305,7 +307,7 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
-  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths, diversity.  What the eleven share ----
+  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths, diversity, match.  What the twelve share ----
   struct Stage {
     void *blk = nullptr;              // one allocation, carved up (stage_alloc)
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
@@ -326,7 +328,7 @@ struct rfid_ctx {
     int64_t *d_off = nullptr;         // [B_plan x max_tags + 1]
     int *d_base = nullptr, *d_head = nullptr;
   } trk;
-  // ---- the nine window-table stages: one [B_plan][rows] table of fixed-size records each -- the diversity stage: [B_plan / members][rows] -- (csrc/rfid_stage.hpp) ----
+  // ---- the ten window-table stages: one [B_plan][rows] table of fixed-size records each -- the diversity stage: [B_plan / members][rows] -- (csrc/rfid_stage.hpp) ----
   struct Table : Stage {
     void *d_table = nullptr;          // [B_plan][rows] records of the stage's type
     template <typename R> R *table() const { return static_cast<R *>(d_table); }
@@ -365,12 +367,18 @@ struct rfid_ctx {
     int blocks = 0;                   // ceil(rows / DIV_ROWS)
     int members = 0;                  // traces per group
   } dvs;
+  // match (rfid_batch_plan_match): lives and dies with the plan; needs the pass's inventory, or with a caller's list its statistics only
+  struct Match : Table {
+    int blocks = 0;                   // ceil(rows / MAT_ROWS)
+    uint32_t *d_list = nullptr;       // [RFID_MATCH_MAX_LIST][4]: the caller's frames (rfid_batch_match_set_list)
+    int n_list = 0;                   // 0: every trace's own inventory
+  } mat;
   // fine (rfid_batch_plan_fine): lives and dies with the tracks workspace
   struct Fine : Table {
     rfid_read_fine *d_packed = nullptr;     // [trk.cap]: aligned with the tracks
   } fin;
   // What the per-call forms (rfid_repair_window, rfid_window_moments_of, rfid_commands_of, rfid_fine_window, rfid_retune_window, rfid_collisions_of,
-  // rfid_length_window, rfid_diversity_window) upload, compute on and download from.  One buffer for the eight: each synchronises c->stream before it returns, so no two of them ever have
+  // rfid_length_window, rfid_diversity_window, rfid_match_window) upload, compute on and download from.  One buffer for the nine: each synchronises c->stream before it returns, so no two of them ever have
   // work in flight on it, and grow() may free and reallocate it.
   DevBuf one;
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
@@ -434,6 +442,7 @@ const KnobEntry g_knob_table[] = {
   {"collide_wgs", "RFID_COLLIDE_WGS", &RfidKnobs::collide_wgs, 0, 65536},
   {"lengths_wgs", "RFID_LENGTHS_WGS", &RfidKnobs::lengths_wgs, 0, 65536},
   {"diversity_wgs", "RFID_DIVERSITY_WGS", &RfidKnobs::diversity_wgs, 0, 65536},
+  {"match_wgs", "RFID_MATCH_WGS", &RfidKnobs::match_wgs, 0, 65536},
 };
 int clamp_int(long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 // the environment, once per context: values out of range are clamped, anything that is not a number is ignored
@@ -517,7 +526,7 @@ void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
 // `stage` and everything behind it no longer belong to the last pass
 void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
 
-// ---- what the inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths and diversity stages share on the host ----
+// ---- what the inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths, diversity and match stages share on the host ----
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void stage_free(rfid_ctx::Stage &st) {
@@ -763,6 +772,8 @@ void free_plan(rfid_ctx *c) {
   table_free(c->col);
   table_free(c->len);
   table_free(c->dvs);
+  table_free(c->mat);
+  c->mat.n_list = 0;
   invalidate_from(c, rfid_ctx::CUR_STATS);
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
@@ -793,7 +804,7 @@ int join_tails(rfid_ctx *c) {
   return RFID_OK;
 }
 
-// ---- the nine window-table stages (quality, repair, slots, commands, fine, retune, collisions, lengths, diversity): what their plan, enqueue and get functions share ----
+// ---- the ten window-table stages (quality, repair, slots, commands, fine, retune, collisions, lengths, diversity, match): what their plan, enqueue and get functions share ----
 // A stage's description: what its checks ask for and how its messages name it.
 struct TableStage {
   const char *name;      // as in rfid_batch_<name>
@@ -811,6 +822,9 @@ constexpr TableStage ST_RETUNE = {"retune", false, false, rfid_ctx::CUR_STATS, f
 constexpr TableStage ST_COLLISIONS = {"collisions", false, false, rfid_ctx::CUR_STATS, false, "RN16 windows"};
 constexpr TableStage ST_LENGTHS = {"lengths", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
 constexpr TableStage ST_DIVERSITY = {"diversity", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
+// match: planned and, with a caller's list, enqueued as the lengths stage is; without a list enqueued as the repair stage is
+constexpr TableStage ST_MATCH = {"match", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
+constexpr TableStage ST_MATCH_OWN = {"match", true, false, rfid_ctx::CUR_INVENTORY, true, "EPC windows"};
 
 bool table_needs_met(const rfid_ctx *c, const TableStage &d) { return (!d.inv || c->inv.blk) && (!d.trk || c->trk.blk); }
 
@@ -1408,7 +1422,7 @@ int rfid_ctx_destroy(rfid_ctx *c) {
     if (e) (void)hipEventDestroy(e);
   for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep,
                                (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd, (rfid_ctx::Stage *)&c->fin, (rfid_ctx::Stage *)&c->ret,
-                               (rfid_ctx::Stage *)&c->col, (rfid_ctx::Stage *)&c->len, (rfid_ctx::Stage *)&c->dvs})
+                               (rfid_ctx::Stage *)&c->col, (rfid_ctx::Stage *)&c->len, (rfid_ctx::Stage *)&c->dvs, (rfid_ctx::Stage *)&c->mat})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
@@ -2688,6 +2702,88 @@ int rfid_diversity_window(rfid_ctx *c, const rfid_cf32 *spans, int members, cons
                      (rfid_diversity *)(b + sz_w + sz_r));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
+}
+
+// ---- match stage: known tags' frames found in CRC-failed EPC windows, behind the inventory of a pass or, with a caller's list, behind its statistics (csrc/rfid_match.hpp) ----
+int rfid_batch_plan_match(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Match &p = c->mat;
+  const int rows = (c->wmax + 1) / 2;      // EPC windows are every other window
+  const int r = table_plan(c, p, ST_MATCH, rows,
+                           {{&p.d_table, sizeof(rfid_match) * (size_t)rows * (size_t)c->B_plan},
+                            {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan},
+                            {(void **)&p.d_list, sizeof(uint32_t) * 4 * (size_t)MAT_MAX_LIST}});
+  p.n_list = 0;                            // (a workspace anew: the list went with the old one)
+  if (r) return r;
+  p.blocks = (rows + MAT_ROWS - 1) / MAT_ROWS;
+  return RFID_OK;
+}
+
+int rfid_batch_match_set_list(rfid_ctx *c, const uint32_t *frames, int n) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Match &p = c->mat;
+  if (n < 0 || n > MAT_MAX_LIST) return failf(c, RFID_ERR_INVALID, "rfid_batch_match_set_list: a list holds 0 to %d frames", MAT_MAX_LIST);
+  if (!p.blk) return fail(c, RFID_ERR_STATE, "rfid_batch_match_set_list: no plan with a match workspace (rfid_batch_plan_match)");
+  HIPCHK(c, hipSetDevice(c->device));
+  // (an enqueued stage may still read the list in place: behind it, and the caller's array is free again on return)
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!frames || n == 0) { p.n_list = 0; return RFID_OK; }
+  HIPCHK(c, hipMemcpyAsync(p.d_list, frames, sizeof(uint32_t) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  p.n_list = n;
+  return RFID_OK;
+}
+
+int rfid_batch_match(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Inventory &v = c->inv;
+  rfid_ctx::Match &p = c->mat;
+  const bool own = p.n_list == 0;
+  int n = 0;
+  MatArgs a;
+  { int r = table_begin(c, p, own ? ST_MATCH_OWN : ST_MATCH, &n, &a.p); if (r) return r; }
+  a.rows = p.rows; a.blocks = p.blocks; a.table = p.table<rfid_match>(); a.nrows = p.d_nrows;
+  a.list = own ? nullptr : p.d_list; a.n_list = p.n_list;
+  a.ent = own ? v.d_ent : nullptr; a.ent_counts = own ? v.d_counts : nullptr; a.ent_over = own ? v.d_over : nullptr; a.max_tags = own ? v.max_tags : 0;
+  // single-wave workgroups, each walking blocks of eight rows (512 bytes of LDS each)
+  const int64_t items = (int64_t)n * p.blocks;
+  const int64_t most = c->knobs.match_wgs ? (int64_t)c->knobs.match_wgs : (int64_t)c->n_cus * MAT_WGS_PER_CU;
+  hipLaunchKernelGGL(match_kernel, persistent_grid(items, most), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return table_end(c, p, n);
+}
+
+int rfid_batch_get_window_matches(rfid_ctx *c, int stream, rfid_match *out, int64_t cap, int64_t *n) {
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->mat, ST_MATCH, "rfid_batch_get_window_matches", sizeof(*out), stream, out, cap, n);
+}
+
+int rfid_batch_match_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  return stage_ms(c, c->mat, ms);
+}
+
+// the per-call form: one window and a list in host memory through the batch kernel's device functions (one launch, synchronising)
+int rfid_match_window(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_result *res, const uint32_t *frames, int n_frames, rfid_match *out) {
+  if (!c || !gated || !res || !frames || !out) return RFID_ERR_INVALID;
+  if (n_frames < 1 || n_frames > MAT_MAX_LIST) return failf(c, RFID_ERR_INVALID, "rfid_match_window: a list holds 1 to %d frames", MAT_MAX_LIST);
+  if (res->type != RFID_DECODE_EPC) return fail(c, RFID_ERR_INVALID, "rfid_match_window: not the result of an EPC window");
+  if (res->index < 65 || res->index > 65 + N_SYNC - 1) return fail(c, RFID_ERR_INVALID, "rfid_match_window: the result's index is no sync offset (65 .. 79)");
+  if (!(res->T >= MAT_T_LO && res->T <= MAT_T_HI))
+    return fail(c, RFID_ERR_INVALID, "rfid_match_window: the result's T is none of the decoder's (4.94999981 .. 5.05000019)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_w = up256(sizeof(float2) * (size_t)EPC_WIN), sz_r = up256(sizeof(rfid_decode_result)), sz_f = up256(sizeof(uint32_t) * 4 * (size_t)MAT_MAX_LIST);
+  { int r = grow(c, c->one, sz_w + sz_r + sz_f + sizeof(rfid_match)); if (r) return r; }
+  char *b = (char *)c->one.p;
+  HIPCHK(c, hipMemcpyAsync(b, gated, sizeof(float2) * (size_t)EPC_WIN, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_w + sz_r, frames, sizeof(uint32_t) * 4 * (size_t)n_frames, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(match_one_kernel, dim3(1), dim3(64), 0, c->stream, (const float2 *)b, (const rfid_decode_result *)(b + sz_w),
+                     (const uint32_t *)(b + sz_w + sz_r), n_frames, (rfid_match *)(b + sz_w + sz_r + sz_f));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r + sz_f, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
 }

@@ -42,6 +42,25 @@ struct QualArgs {
   int *nrows;                       // [n_streams]: EPC windows before the cut-off (n_windows_used / 2)
 };
 
+// The decision value r and its quadrature counterpart q of one decision from its two half-bit samples p and s (the definition's
+// expressions: the gate's output in[i] - dc_est per component, then the difference of the two).  One copy: the match stage
+// (rfid_match.hpp) correlates the same r_j.
+RFID_DEVICE void quality_rq(float2 p, float2 s, float dcr, float dci, float h_re, float h_im, float &r, float &q) {
+  const float nhim = -h_im;
+  const float dx = (p.x - dcr) - (s.x - dcr), dy = (p.y - dci) - (s.y - dci);
+  r = dx * h_re - dy * nhim;
+  q = dy * h_re - dx * h_im;
+}
+
+// (((0.0f + t_0) + t_1) + ...) + t_127 over 128 terms in LDS, ABS: over their magnitudes -- the in-order sums of the definition
+template <bool ABS>
+RFID_DEVICE float quality_sum128(const float *t) {
+  float acc = 0.0f;
+#pragma unroll 16
+  for (int j = 0; j < 128; ++j) acc = acc + (ABS ? __builtin_fabsf(t[j]) : t[j]);
+  return acc;
+}
+
 struct QualWin {     // what a window's gathers need (the same in every lane)
   const float2 *src;
   float dcr, dci, h_re, h_im, T, fidx;
@@ -90,12 +109,9 @@ RFID_KERNEL(64) void quality_kernel(QualArgs a) {
     // ---- terms, minimum ----
 #pragma unroll
     for (int u = 0; u < QUAL_PACK; ++u) {
-      const float dcr = w[u].dcr, dci = w[u].dci, h_re = w[u].h_re, h_im = w[u].h_im, nhim = -h_im;
-      // gate output in[i] - dc_est per component, then the difference of the two half-bit samples
-      const float dx0 = (pa[u].x - dcr) - (qa[u].x - dcr), dy0 = (pa[u].y - dci) - (qa[u].y - dci);
-      const float dx1 = (pb[u].x - dcr) - (qb[u].x - dcr), dy1 = (pb[u].y - dci) - (qb[u].y - dci);
-      const float r0v = dx0 * h_re - dy0 * nhim, q0v = dy0 * h_re - dx0 * h_im;
-      const float r1v = dx1 * h_re - dy1 * nhim, q1v = dy1 * h_re - dx1 * h_im;
+      float r0v, q0v, r1v, q1v;
+      quality_rq(pa[u], qa[u], w[u].dcr, w[u].dci, w[u].h_re, w[u].h_im, r0v, q0v);
+      quality_rq(pb[u], qb[u], w[u].dcr, w[u].dci, w[u].h_re, w[u].h_im, r1v, q1v);
       const float a0 = __builtin_fabsf(r0v), a1 = __builtin_fabsf(r1v);
       float *t = term + (u * 3) * QUAL_TERM_STRIDE;
       t[lane] = a0; t[lane + 64] = a1;
@@ -119,10 +135,7 @@ RFID_KERNEL(64) void quality_kernel(QualArgs a) {
     wv::wave_sync();
     // ---- the in-order sums: lane 3 u + c walks sum c of window u ----
     if (lane < QUAL_PACK * 3) {
-      const float *t = term + lane * QUAL_TERM_STRIDE;
-      float acc = 0.0f;
-#pragma unroll 16
-      for (int j = 0; j < 128; ++j) acc = acc + t[j];
+      const float acc = quality_sum128<false>(term + lane * QUAL_TERM_STRIDE);
       const int u = lane / 3, c = lane - 3 * u;
       rec[u * QUAL_WORDS + 2 + c] = (r0 + u < nrows) ? (int)wv::f2u(acc) : 0;
     }

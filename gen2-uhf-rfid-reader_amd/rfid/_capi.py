@@ -117,6 +117,11 @@ DIVERSITY_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"),
                             ("weakest", "<i4"), ("reserved_", "<i4")])
 DIVERSITY_MAX_MEMBERS, DIVERSITY_SLACK = 8, 4
 assert DIVERSITY_DTYPE.itemsize == 64
+MATCH_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("flags", "<i4"), ("n_cand", "<i4"), ("best", "<i4"),
+                        ("second", "<i4"), ("score_best", "<f4"), ("score_second", "<f4"), ("sig_abs", "<f4"), ("dist_best", "<i4"),
+                        ("diff", "<i4"), ("frame", "<u4", (4,))])
+MATCH_MAX_LIST = 1024
+assert MATCH_DTYPE.itemsize == 64
 GATE_FSM_IN_DTYPE = np.dtype([("mode", "<i4"), ("n_samples", "<i4"), ("signal_state", "<i4"), ("num_pulses", "<i4"),
                               ("gate_open", "<i4"), ("n_to_ungate", "<i4"), ("wtype", "<i4"), ("nvalid", "<i4"), ("pos", "<i4"),
                               ("reserved_", "<i4"), ("below", "<u8"), ("above", "<u8")])
@@ -268,6 +273,12 @@ SIGNATURES = {
     "rfid_batch_get_window_diversity": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_diversity_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_diversity_window": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "rfid_batch_plan_match": (_i, [_vp]),
+    "rfid_batch_match_set_list": (_i, [_vp, _vp, _i]),
+    "rfid_batch_match": (_i, [_vp]),
+    "rfid_batch_get_window_matches": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_match_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_match_window": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

@@ -63,6 +63,8 @@ class BatchDecoder:
         self.last_lengths = None      # one sized-frame array per trace (every EPC window before the cut-off) of the last decode(..., lengths=True)
         self._div_members = 0         # (the group size the diversity workspace was planned for; 0: none)
         self.last_diversity = None    # one diversity array per GROUP (every EPC window before its anchor's cut-off) of the last decode(..., diversity=M)
+        self._mat_planned = False
+        self.last_matches = None      # one match array per trace (every EPC window before the cut-off) of the last decode(..., match=True)
 
     def close(self) -> None:
         self.ctx.close()
@@ -84,6 +86,7 @@ class BatchDecoder:
             self._col_planned = False
             self._len_planned = False
             self._div_members = 0
+            self._mat_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -95,7 +98,8 @@ class BatchDecoder:
     def decode(self, traces: Sequence[np.ndarray], want_scores: bool = False, timing: Optional[dict] = None,
                inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False,
                repair: bool = False, slots: bool = False, commands: bool = False, fine: bool = False,
-               retune: bool = False, collisions: bool = False, lengths: bool = False, diversity: int = 0):
+               retune: bool = False, collisions: bool = False, lengths: bool = False, diversity: int = 0,
+               match: bool = False, match_list=None):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
@@ -131,9 +135,15 @@ class BatchDecoder:
         group's first the anchor; len(traces) must be a multiple of M -- and the EPC windows no antenna read are decided again behind
         the pass from the antennas' summed decision values; `self.last_diversity` keeps one capi.DIVERSITY_DTYPE array per GROUP, a
         record per EPC window of its anchor (diversity_fields() turns it into flags, member lists and the summed channel power); a
-        combined frame is not a read and changes nothing else."""
+        combined frame is not a read and changes nothing else.  match=True: the CRC-failed EPC windows are correlated behind the pass
+        against the frames of known tags -- match_list=frames, (n, 4) words as frame_of_epc() builds them, the same for every trace, or
+        without a list every trace's own inventory (then it implies inventory=True); `self.last_matches` keeps one capi.MATCH_DTYPE
+        array per trace, a record per EPC window (match_fields() says which are attributions); an attribution is not a read and
+        changes nothing else."""
         torch = self._torch
         n = len(traces)
+        match = bool(match) or match_list is not None
+        own_match = match and (match_list is None or len(match_list) == 0)
         diversity = int(diversity)
         if diversity and n % diversity:
             raise ValueError("diversity: %d traces are no whole groups of %d" % (n, diversity))
@@ -154,7 +164,7 @@ class BatchDecoder:
         t1 = time.perf_counter()
         tracks = tracks or quality or fine
         slots = slots or collisions
-        inventory = inventory or tracks or repair
+        inventory = inventory or tracks or repair or own_match
         if inventory and self._inv_tags != int(max_tags):
             self.ctx.batch_plan_inventory(int(max_tags))
             self._inv_tags = int(max_tags)
@@ -192,6 +202,11 @@ class BatchDecoder:
         if diversity and self._div_members != diversity:
             self.ctx.batch_plan_diversity(diversity)
             self._div_members = diversity
+        if match:
+            if not self._mat_planned:
+                self.ctx.batch_plan_match()
+                self._mat_planned = True
+            self.ctx.batch_match_set_list(None if own_match else match_list)
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
         if inventory:
             self.ctx.batch_inventory_enqueue()
@@ -215,6 +230,8 @@ class BatchDecoder:
             self.ctx.batch_lengths_enqueue()
         if diversity:
             self.ctx.batch_diversity_enqueue()
+        if match:
+            self.ctx.batch_match_enqueue()
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
@@ -239,6 +256,8 @@ class BatchDecoder:
             self.last_lengths = [self.ctx.batch_window_lengths(b) for b in range(n)]
         if diversity:
             self.last_diversity = [self.ctx.batch_window_diversity(g) for g in range(n // diversity)]
+        if match:
+            self.last_matches = [self.ctx.batch_window_matches(b) for b in range(n)]
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -620,6 +639,103 @@ def format_diversity_csv(rows: Sequence[np.ndarray], entries_of_members: Sequenc
     return "\n".join(lines) + "\n"
 
 
+MATCH_HEADER = "file,epc,pc,seq,t_s,rho,rho_second,diff,bit_errors,h_re,h_im,mag_db,phase_rad"
+MATCH_MIN_RHO = 0.5       # the default of --match-min (match_fields says why)
+
+
+def match_fields(rows: np.ndarray, min_rho: float = MATCH_MIN_RHO) -> dict:
+    """rfid_match records -> a dict, one value per record: searched (a failed window that had candidates), in binary64 rho =
+    score_best / sig_abs and rho_second = score_second / sig_abs (nan where there is none, or sig_abs is 0), gap = score_best -
+    score_second, gap_needed = diff * sig_abs / 128, and attributed: the HOST's policy, a definition and no part of the device record.
+    A window is attributed to `best` when both hold:
+      threshold  rho >= min_rho.  In a window that does not hold the candidate's reply the signs of r_j are independent of the
+                 pattern: rho has mean 0 and standard deviation sqrt(sum r^2) / sum |r|, for Gaussian r_j sqrt(pi / 2) / sqrt(128) =
+                 0.111.  The default 0.5 lies 4.5 standard deviations out: about 3e-6 per window and candidate.
+      gap        there is no second, or gap >= gap_needed.  best's and second's patterns differ on `diff` decisions, the mean |r_j| is
+                 sig_abs / 128: a clean reply of best puts the two scores 2 diff mean|r| apart, a clean reply of second the negative
+                 of it.  The rule asks for half of the former, diff mean|r|: the midpoint between "best's reply" and "cannot tell".
+    An attribution is never a read."""
+    rows = np.asarray(rows)
+    searched = ((rows["flags"] & 1) == 0) & (rows["n_cand"] > 0)
+    sig = rows["sig_abs"].astype(np.float64)
+    sb, ss = rows["score_best"].astype(np.float64), rows["score_second"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rho = np.where(searched & (sig > 0), sb / sig, np.nan)
+        rho_second = np.where(searched & (sig > 0) & (rows["second"] >= 0), ss / sig, np.nan)
+    gap = np.where(rows["second"] >= 0, sb - ss, np.inf)
+    gap_needed = np.where(rows["second"] >= 0, rows["diff"].astype(np.float64) * sig / 128.0, 0.0)
+    with np.errstate(invalid="ignore"):
+        attributed = searched & (rho >= float(min_rho)) & (gap >= gap_needed)
+    return dict(searched=searched, rho=rho, rho_second=rho_second, gap=gap, gap_needed=gap_needed, attributed=attributed)
+
+
+def _match_reads(rows: np.ndarray, results: np.ndarray) -> dict:
+    """frame bytes -> the reads of that frame among one trace's rows (flags bit 0), from its result records by seq"""
+    reads = {}
+    for r in rows[(rows["flags"] & 1) != 0]:
+        key = bytes(np.ascontiguousarray(results[int(r["seq"])]["bits"]))
+        reads[key] = reads.get(key, 0) + 1
+    return reads
+
+
+def format_match(rows: np.ndarray, results: np.ndarray, min_rho: float = MATCH_MIN_RHO) -> str:
+    """The lines for one trace's EPC windows before the cut-off (Context.batch_window_matches) and its result records by seq: how many
+    windows failed, how many of those are attributed to a known tag, how many distinct tags those are; then per such tag its reads
+    beside its attributed sightings, ordered by frame."""
+    rows = np.asarray(rows)
+    f = match_fields(rows, min_rho)
+    got = rows[f["attributed"]]
+    reads = _match_reads(rows, results)
+    seen = {}
+    for r in got:
+        key = bytes(np.ascontiguousarray(r["frame"]))
+        seen[key] = seen.get(key, 0) + 1
+    text = ("| EPC windows : %d  failed : %d  attributed to a known tag : %d  distinct tags : %d\n" %
+            (len(rows), int(((rows["flags"] & 1) == 0).sum()), len(got), len(seen)))
+    for key in sorted(seen):
+        pc, epc = frame_fields(np.frombuffer(key, dtype=np.uint32))
+        text += "|   %s  %04x  reads : %d  attributed : %d\n" % (epc, pc, reads.get(key, 0), seen[key])
+    return text
+
+
+def format_match_csv(rows: Sequence[np.ndarray], names: Sequence[str], results: Sequence[np.ndarray], min_rho: float = MATCH_MIN_RHO) -> str:
+    """CSV text, one line per attributed window, by trace, then by seq: file,epc,pc,seq,t_s,rho,rho_second,diff,bit_errors,h_re,h_im,
+    mag_db,phase_rad.  epc / pc of best's frame, t_s = start / 400e3 as in the tracks CSV, rho with %.6f (rho_second and diff empty
+    and -1 where there was one candidate), bit_errors = dist_best, h_re / h_im the window's own h_est (results[b][seq]) with %.9g, its
+    magnitude in dB and its phase as in the tracks CSV: what a sighting adds to a tag's track."""
+    lines = [MATCH_HEADER]
+    for rec, name, res in zip(rows, names, results):
+        rec = np.asarray(rec)
+        f = match_fields(rec, min_rho)
+        for k in np.flatnonzero(f["attributed"]):
+            r = rec[k]
+            d = res[int(r["seq"])]
+            pc, epc = frame_fields(r["frame"])
+            re, im = np.float64(d["h_re"]), np.float64(d["h_im"])
+            mag = float(np.hypot(re, im))
+            db = 20.0 * np.log10(mag) if mag > 0 else float("-inf")
+            second = "" if int(r["second"]) < 0 else "%.6f" % float(f["rho_second"][k])
+            lines.append("%s,%s,%04x,%d,%.9g,%.6f,%s,%d,%d,%.9g,%.9g,%.9g,%.9g" %
+                         (name, epc, pc, int(r["seq"]), int(r["start"]) / TRACKS_RATE, float(f["rho"][k]), second, int(r["diff"]),
+                          int(r["dist_best"]), float(d["h_re"]), float(d["h_im"]), db, float(np.arctan2(im, re))))
+    return "\n".join(lines) + "\n"
+
+
+def read_epc_list(path: str) -> np.ndarray:
+    """A text file with one hex EPC per line (96 bits), optionally PC:EPC; blank lines and lines that start with # are skipped
+    -> (n, 4) uint32 frames (frame_of_epc)."""
+    from .context import frame_of_epc
+    frames = []
+    with open(path) as f:
+        for ln in f:
+            ln = ln.strip()
+            if not ln or ln.startswith("#"):
+                continue
+            pc, _, epc = ln.rpartition(":")
+            frames.append(frame_of_epc(epc, int(pc, 16) if pc else 0x3000))
+    return np.array(frames, dtype=np.uint32).reshape(-1, 4)
+
+
 MOMENTS_N = 240           # RFID_MOMENTS_SAMPLES: the samples of a window its moments are taken over
 SLOT_EMPTY, SLOT_SINGLE, SLOT_COLLIDED, SLOT_UNKNOWN = 0, 1, 2, -1
 SCHOUTE = 2.39            # Schoute's estimate of the tags behind a collided slot of a framed-ALOHA round
@@ -862,7 +978,7 @@ def format_commands_csv(rows: Sequence[np.ndarray], starts: Sequence[np.ndarray]
 
 
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] [--collisions OUT.csv] [--lengths OUT.csv] [--antennas M --diversity OUT.csv] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] [--collisions OUT.csv] [--lengths OUT.csv] [--antennas M --diversity OUT.csv] [--match OUT.csv [--match-list EPCS.txt] [--match-min RHO]] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -910,10 +1026,27 @@ def main(argv=None) -> int:
     ap.add_argument("--antennas", metavar="M", type=int, default=2,
                     help="with --diversity: the files are given capture by capture, each capture's M antennas in order (2..8, "
                          "default 2); the first of each is the anchor")
+    ap.add_argument("--match", metavar="OUT.csv", default=None,
+                    help="correlate the CRC-failed EPC windows against the replies of known tags (built on the device): finds "
+                         "sightings of tags too weak to decode; per file the failed windows, how many are attributed, how many "
+                         "distinct tags those are and each one's reads beside its sightings, the attributed windows to this CSV "
+                         "file; without --match-list the known tags are each file's own inventory (implies --inventory)")
+    ap.add_argument("--match-list", metavar="EPCS.txt", default=None,
+                    help="with --match: the known tags, one hex EPC per line, optionally PC:EPC (default PC 3000), up to %d"
+                         % capi.MATCH_MAX_LIST)
+    ap.add_argument("--match-min", metavar="RHO", type=float, default=MATCH_MIN_RHO,
+                    help="with --match: the least score / sum |r| of an attribution (default %.1f)" % MATCH_MIN_RHO)
     args = ap.parse_args(argv)
+    match_list = None
+    if args.match_list:
+        if not args.match:
+            ap.error("--match-list goes with --match OUT.csv")
+        match_list = read_epc_list(args.match_list)
+        if not 1 <= len(match_list) <= capi.MATCH_MAX_LIST:
+            ap.error("--match-list: 1 to %d EPCs" % capi.MATCH_MAX_LIST)
     if args.diversity and (not 2 <= args.antennas <= capi.DIVERSITY_MAX_MEMBERS or len(args.files) % args.antennas):
         ap.error("--diversity: the files must be whole captures of --antennas M = 2..%d files each" % capi.DIVERSITY_MAX_MEMBERS)
-    if args.tracks or args.repair or args.retune or args.diversity:
+    if args.tracks or args.repair or args.retune or args.diversity or (args.match and match_list is None):
         args.inventory = True
     dec = BatchDecoder(device=args.device, fixed_q=args.fixed_q, max_num_queries=args.max_queries)
     try:
@@ -922,9 +1055,11 @@ def main(argv=None) -> int:
                                             tracks=bool(args.tracks), quality=args.quality, repair=bool(args.repair),
                                             slots=bool(args.slots), commands=bool(args.commands), fine=args.fine,
                                             retune=bool(args.retune), collisions=bool(args.collisions),
-                                            lengths=bool(args.lengths), diversity=args.antennas if args.diversity else 0)
+                                            lengths=bool(args.lengths), diversity=args.antennas if args.diversity else 0,
+                                            match=bool(args.match), match_list=match_list)
         collided = ([classify_collisions(c, classify_slots(m)) for c, m in zip(dec.last_collisions, dec.last_slots)]
                     if args.collisions else None)
+        by_seq = [results[windows["stream"] == b] for b in range(len(args.files))] if args.match else None   # (ordered by seq)
         per_trace = lambda entries, counts: np.split(entries, np.cumsum(counts)[:-1]) if len(counts) else []
         for i, (path, row) in enumerate(zip(args.files, stats)):
             print(path)
@@ -945,6 +1080,8 @@ def main(argv=None) -> int:
                 print(format_collisions(collided[i]), end="")
             if args.lengths:
                 print(format_lengths(dec.last_lengths[i]), end="")
+            if args.match:
+                print(format_match(dec.last_matches[i], by_seq[i], args.match_min), end="")
             if args.diversity and i % args.antennas == 0:           # (the group's line stands with its anchor)
                 print(format_diversity(dec.last_diversity[i // args.antennas], per_trace(*dec.last_inventory)[i:i + args.antennas]), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
@@ -987,6 +1124,9 @@ def main(argv=None) -> int:
             with open(args.diversity, "w") as f:
                 f.write(format_diversity_csv(dec.last_diversity, [ents[i:i + args.antennas] for i in range(0, len(args.files), args.antennas)],
                                              args.files[::args.antennas]))
+        if args.match:
+            with open(args.match, "w") as f:
+                f.write(format_match_csv(dec.last_matches, args.files, by_seq, args.match_min))
         if args.commands:
             starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
             with open(args.commands, "w") as f:

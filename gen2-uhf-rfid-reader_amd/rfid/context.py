@@ -742,6 +742,62 @@ class Context:
         self._chk(self._lib.rfid_diversity_window(self._h, spans.ctypes.data, len(spans), res.ctypes.data, out.ctypes.data))
         return out[0]
 
+    def batch_plan_match(self) -> None:
+        """Reserves the match workspace of the current plan, with room for a list of capi.MATCH_MAX_LIST frames (a new plan drops
+        it and the list; no other stage's plan call does)."""
+        self._chk(self._lib.rfid_batch_plan_match(self._h))
+
+    @staticmethod
+    def _frames(frames) -> np.ndarray:
+        f = np.ascontiguousarray(frames, dtype=np.uint32)
+        if f.ndim == 1 and len(f) % 4 == 0:
+            f = f.reshape(-1, 4)
+        if f.ndim != 2 or f.shape[1] != 4:
+            raise ValueError("frames must be (n, 4) words, packed as a result's bits")
+        return f
+
+    def batch_match_set_list(self, frames=None) -> None:
+        """The candidates of every trace from now on (rfid_batch_match_set_list, synchronises): frames = (n, 4) uint32 words, packed
+        as a result's bits (rfid.frame_of_epc builds one from an EPC), up to capi.MATCH_MAX_LIST of them, copied to the device.  None
+        or an empty list: every trace's own inventory again."""
+        f = self._frames(frames if frames is not None else np.zeros((0, 4), dtype=np.uint32))
+        if len(f) > capi.MATCH_MAX_LIST:
+            raise ValueError("a list holds at most %d frames" % capi.MATCH_MAX_LIST)
+        self._chk(self._lib.rfid_batch_match_set_list(self._h, f.ctypes.data if len(f) else None, len(f)))
+
+    def batch_match_enqueue(self) -> None:
+        """Asynchronous: the CRC-failed EPC windows of the last pass correlated against the known tags' frames (rfid_batch_match):
+        without a list behind the pass's inventory (batch_inventory_enqueue first, as for the repair stage), with one behind its
+        statistics."""
+        self._chk(self._lib.rfid_batch_match(self._h))
+
+    def batch_window_matches(self, stream: int, extra: int = 0) -> np.ndarray:
+        """One trace's row of the match table (synchronises): the capi.MATCH_DTYPE record of EVERY EPC window before the cut-off,
+        in seq order (n_windows_used // 2 of them), of the last batch_match_enqueue: flags bit 0 = the window was a read, bit 1 =
+        the trace's inventory overflowed, bit 2 = no candidates (nothing searched in all three), bit 3 = the candidates are the
+        caller's list.  rfid.batch.match_fields() says which records are attributions.  extra > 0: up to that many of the table's
+        rows behind them as well (zeroed by the stage)."""
+        return self._window_rows(self._lib.rfid_batch_get_window_matches, capi.MATCH_DTYPE, stream, extra)
+
+    def batch_match_ms(self) -> float:
+        return self._stage_ms(self._lib.rfid_batch_match_ms)
+
+    def match_window(self, gated, result, frames) -> np.ndarray:
+        """The same for ONE window in host memory (rfid_match_window): gated = 1370 DC-free samples, result = the window's
+        capi.RESULT_DTYPE record, frames = (n, 4) candidate frames, 1 .. capi.MATCH_MAX_LIST.  -> one capi.MATCH_DTYPE record,
+        stream = seq = start = 0."""
+        gated = np.ascontiguousarray(gated, dtype=np.complex64)
+        if gated.ndim != 1 or len(gated) != 1370:
+            raise ValueError("an EPC window has 1370 samples")
+        f = self._frames(frames)
+        if not 1 <= len(f) <= capi.MATCH_MAX_LIST:
+            raise ValueError("1 to %d candidate frames" % capi.MATCH_MAX_LIST)
+        res = np.zeros(1, dtype=capi.RESULT_DTYPE)
+        res[0] = result
+        out = np.zeros(1, dtype=capi.MATCH_DTYPE)
+        self._chk(self._lib.rfid_match_window(self._h, gated.ctypes.data, res.ctypes.data, f.ctypes.data, len(f), out.ctypes.data))
+        return out[0]
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)
@@ -802,3 +858,30 @@ def unpack_bits(words: np.ndarray, n_bits: int) -> np.ndarray:
     words = np.asarray(words, dtype=np.uint32)
     j = np.arange(n_bits)
     return ((words[j >> 5] >> (j & 31)) & 1).astype(np.uint8)
+
+
+def frame_of_epc(epc_hex: str, pc: int = 0x3000) -> np.ndarray:
+    """PC + EPC + CRC-16: the 128-bit frame a tag with this 96-bit EPC (24 hex digits, MSB first as sent) and PC word replies with,
+    packed as rfid_decode_result.bits -> four uint32 words.  The CRC is Gen2's (CCITT 0x1021, preset 0xFFFF, complemented) over
+    the 112 bits before it: what rfid_batch_match_set_list and rfid_match_window take as a candidate."""
+    digits = "".join(str(epc_hex).split()).lower()
+    if digits.startswith("0x"):
+        digits = digits[2:]
+    if len(digits) != 24:
+        raise ValueError("an EPC has 24 hex digits (96 bits)")
+    if not 0 <= int(pc) <= 0xFFFF:
+        raise ValueError("the PC is a 16-bit word")
+    body = (int(pc) << 96) | int(digits, 16)
+    bits = [(body >> (111 - i)) & 1 for i in range(112)]
+    reg = 0xFFFF
+    for b in bits:
+        msb = (reg >> 15) & 1
+        reg = (reg << 1) & 0xFFFF
+        if msb ^ b:
+            reg ^= 0x1021
+    reg ^= 0xFFFF
+    bits += [(reg >> i) & 1 for i in range(15, -1, -1)]
+    words = np.zeros(4, dtype=np.uint32)
+    for j, b in enumerate(bits):
+        words[j >> 5] |= np.uint32(b << (j & 31))
+    return words

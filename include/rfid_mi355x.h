@@ -360,6 +360,46 @@ typedef struct rfid_diversity {      /* 64 bytes */
   int32_t  reserved_;                /* 0 */
 } rfid_diversity;
 
+/* what the match stage (rfid_batch_match, rfid_match_window) finds for one EPC window: which of a set of KNOWN tags' replies the
+ * window most resembles.  Repair, retune, lengths and diversity all DECODE: the frame must come out whole and pass a CRC-16.  A tag
+ * the pass already knows -- in this trace's inventory, or on a list the caller supplies -- has a known reply of 128 bits, and a known
+ * reply is a known pattern of 128 signs: correlating the window's decision values against it is a matched filter over the whole frame
+ * and needs no single decision to be right.  An attribution is NOT a read: nothing else the library reports changes, and whether a
+ * score amounts to an attribution is the host's to say (rfid.batch.match_fields).
+ * THE DEFINITION (the contract; binary32 throughout, every operation rounded by itself, no fused multiply-add), for an EPC window
+ * with seq < n_windows_used:
+ *   candidates   with a list set (rfid_batch_match_set_list): the list's frames in the caller's order, the same for every trace (flags
+ *                bit 3).  Otherwise the entries of THIS trace's inventory of the same pass, in the inventory's order: a candidate's
+ *                index is what rfid_tag_read::entry is.  An overflowed inventory: flags bit 1, nothing is searched.  No candidates:
+ *                flags bit 2, nothing is searched.  A window whose own CRC held: flags bit 0, nothing is searched.
+ *   r_j          j = 0 .. 127, exactly as in the rfid_read_quality definition above (from the window's own result h_re, h_im, T,
+ *                index and s[i] = y[start + i] - dc).  sig_abs: the in-order sum of |r_j|, as rfid_read_quality::sig_abs.
+ *   pattern      of a candidate frame b: the one sign sequence from which the decoder's own chain (bit_j = c_j XOR c_(j-1), the
+ *                sign in front of the first one positive) yields b: c_j = 1 XOR b_0 XOR ... XOR b_j.
+ *   score        (((0.0f + t_0) + t_1) + ...) + t_127 with t_j = r_j where c_j = 1 and -r_j otherwise.
+ *   best         the candidate with the largest score (binary32 >), the smaller index on equal scores; second: the same rule over
+ *                the rest.  Duplicates are allowed.  dist_best: the frame bits in which rfid_decode_result::bits differ from best's
+ *                frame; diff: the decisions j on which best's and second's patterns differ.
+ * Bits 1 to 3 of flags say what the trace's candidates are and stand in every row before the cut-off.  Where nothing is searched
+ * every field behind flags is 0.  A candidate equal to the window's decoded frame scores sig_abs, bit for bit (a -0 term does not
+ * disturb an in-order sum that starts from +0); a span negated under the same result record scores -sig_abs.  A window with a
+ * non-finite sample: unspecified, as its decoding is. */
+#define RFID_MATCH_MAX_LIST 1024
+typedef struct rfid_match {          /* 64 bytes */
+  int32_t  stream, seq, start;       /* the EPC window */
+  int32_t  flags;                    /* bit 0: crc_ok of the window's result (nothing is searched)
+                                        bit 1: candidates are this trace's inventory and it overflowed (nothing is searched)
+                                        bit 2: no candidates (nothing is searched)
+                                        bit 3: the candidates are the caller's list */
+  int32_t  n_cand;                   /* candidates looked at */
+  int32_t  best, second;             /* candidate indices; -1: none */
+  float    score_best, score_second; /* 0.0f when none */
+  float    sig_abs;                  /* as rfid_read_quality::sig_abs of the same window, bit for bit */
+  int32_t  dist_best;                /* frame bits in which the window's decoded bits differ from best's frame; -1: none */
+  int32_t  diff;                     /* decisions on which best's and second's sign patterns differ; -1: no second */
+  uint32_t frame[4];                 /* best's frame, packed as rfid_decode_result::bits; zeros when none */
+} rfid_match;
+
 /* what the collisions stage (rfid_batch_collisions, rfid_collisions_of) works out for one RN16 window: the two RN16s and the two
  * channels of a slot in which two tags replied at once.  The decoder is single-tag by construction (tag_detection_RN16,
  * lib/tag_decoder_impl.cc:114-142, 237-253): decision j is the difference d_j of two adjacent half-bit samples across a bit
@@ -1168,6 +1208,38 @@ RFID_API int rfid_batch_diversity_ms(rfid_ctx *ctx, float *ms);
  * refuse (type, index 65 .. 79, T inside 4.94999981 .. 5.05000019).  One launch of the batch kernel's device functions,
  * synchronising.  out: stream = seq = start = 0, present = 2^members - 1. */
 RFID_API int rfid_diversity_window(rfid_ctx *ctx, const rfid_cf32 *spans, int members, const rfid_decode_result *res, rfid_diversity *out);
+/* ---- (2m) batch match: known tags' frames found in CRC-failed EPC windows, built on the device ----------------------------------- */
+/* Behind a pass: one rfid_match (see its definition above) per EPC window with seq < n_windows_used in a device table
+ * [n_streams][ceil(wmax / 2)] (row = seq >> 1; rows behind a trace's cut-off are zeroed: the table's bytes repeat from pass to pass).
+ * The first stage that detects where the others decode.  Nothing else a pass reports changes: an attribution is not a read.
+ * rfid_batch_plan_match reserves the table (64 bytes per possible EPC window) and room for a list of RFID_MATCH_MAX_LIST frames.
+ * RFID_ERR_STATE without a plan; RFID_ERR_HIP when the allocation fails (the plan and every other workspace stay usable).  A new
+ * rfid_batch_plan drops it, and the list with it; it drops no other stage's workspace, and their plan calls do not drop it. */
+RFID_API int rfid_batch_plan_match(rfid_ctx *ctx);
+/* synchronises; the candidates of every trace from now on: n frames of four words each, packed as rfid_decode_result::bits, copied to
+ * the device.  n = 0 or frames = NULL: every trace's own inventory again.  The list is kept until the workspace is dropped.
+ * RFID_ERR_INVALID: n < 0 or n > RFID_MATCH_MAX_LIST; RFID_ERR_STATE without a match workspace. */
+RFID_API int rfid_batch_match_set_list(rfid_ctx *ctx, const uint32_t *frames, int n);
+/* enqueues the match stage of the LAST pass (asynchronous, no host synchronisation).  Without a list it reads that pass's inventory
+ * and is enqueued behind it exactly as rfid_batch_repair is: RFID_ERR_STATE without an inventory workspace or without an
+ * rfid_batch_inventory behind the last pass.  With a list it needs the pass's statistics only, as rfid_batch_lengths does.  Either
+ * way it may be enqueued before or behind the other stages and neither raises nor lowers their level.  It reads that pass's
+ * matched-filter output, window table, results and statistics on the context's main stream and has rfid_batch_slots' duties there.
+ * ONE table per plan, as rfid_batch_commands. */
+RFID_API int rfid_batch_match(rfid_ctx *ctx);
+/* synchronises; one trace's row of the table: every EPC window before the cut-off in seq order: *n = n_windows_used / 2.  cap as
+ * rfid_batch_get_window_quality.  RFID_ERR_STATE before the first rfid_batch_match of this plan; RFID_ERR_INVALID for a trace the
+ * last rfid_batch_match did not cover. */
+RFID_API int rfid_batch_get_window_matches(rfid_ctx *ctx, int stream, rfid_match *out, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_match (HIP events) */
+RFID_API int rfid_batch_match_ms(rfid_ctx *ctx, float *ms);
+/* the same for ONE window in host memory against n_frames candidate frames: the per-call form.  gated: 1370 samples, DC-free already
+ * (dc = 0 in the definition); res: the result rfid_decoder_work gave for the window; frames: [n_frames][4] words.  RFID_ERR_INVALID:
+ * n_frames outside 1 .. RFID_MATCH_MAX_LIST, or a result that rfid_diversity_window would refuse (type, index 65 .. 79, T inside
+ * 4.94999981 .. 5.05000019).  One launch of the batch kernel's device functions, synchronising.  out: stream = seq = start = 0,
+ * flags bit 3 set; bit 0 = res->crc_ok (then nothing is searched). */
+RFID_API int rfid_match_window(rfid_ctx *ctx, const rfid_cf32 *gated, const rfid_decode_result *res, const uint32_t *frames, int n_frames,
+                               rfid_match *out);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
