@@ -34,6 +34,7 @@
 #include "rfid_lengths.hpp"
 #include "rfid_diversity.hpp"
 #include "rfid_match.hpp"
+#include "rfid_stack.hpp"
 #include "rfid_collide.hpp"
 #include "rfid_mi355x.h"
 #include "rfid_gen2_host.h"
@@ -92,6 +93,7 @@ struct RfidKnobs {
   int lengths_wgs = 0;     // RFID_LENGTHS_WGS       1..65536: most single-wave workgroups of the lengths stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
   int diversity_wgs = 0;   // RFID_DIVERSITY_WGS     1..65536: most single-wave workgroups of the diversity stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
   int match_wgs = 0;       // RFID_MATCH_WGS         1..65536: most single-wave workgroups of the match stage's launch (0: eight per compute unit).  A small grid makes every workgroup walk many blocks
+  int stack_wgs = 0;       // RFID_STACK_WGS         1..65536: most single-wave workgroups of the stack stage's launches (0: four per compute unit, what the LDS holds; the index kernel eight).  A small grid makes every workgroup walk many blocks
 };
 
 // the timing events of a pass: stage i of the four took the time from event i to event i + 1
@@ -307,7 +309,7 @@ struct rfid_ctx {
   bool y_recorded[2] = {false, false};
   int y_idx = 0;
   hipStream_t tail_stream = nullptr;        // where rfid_batch_decode / rfid_batch_stats enqueue (c->stream, or stream2 in an overlapped pass)
-  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths, diversity, match.  What the twelve share ----
+  // ---- the stages behind a pass: inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths, diversity, match, stack.  What the thirteen share ----
   struct Stage {
     void *blk = nullptr;              // one allocation, carved up (stage_alloc)
     hipEvent_t ev[2] = {nullptr, nullptr};   // around the stage's launches
@@ -328,7 +330,7 @@ struct rfid_ctx {
     int64_t *d_off = nullptr;         // [B_plan x max_tags + 1]
     int *d_base = nullptr, *d_head = nullptr;
   } trk;
-  // ---- the ten window-table stages: one [B_plan][rows] table of fixed-size records each -- the diversity stage: [B_plan / members][rows] -- (csrc/rfid_stage.hpp) ----
+  // ---- the eleven window-table stages: one [B_plan][rows] table of fixed-size records each -- the diversity stage: [B_plan / members][rows] -- (csrc/rfid_stage.hpp) ----
   struct Table : Stage {
     void *d_table = nullptr;          // [B_plan][rows] records of the stage's type
     template <typename R> R *table() const { return static_cast<R *>(d_table); }
@@ -373,12 +375,18 @@ struct rfid_ctx {
     uint32_t *d_list = nullptr;       // [RFID_MATCH_MAX_LIST][4]: the caller's frames (rfid_batch_match_set_list)
     int n_list = 0;                   // 0: every trace's own inventory
   } mat;
+  // stack (rfid_batch_plan_stack): lives and dies with the plan; needs the pass's statistics only
+  struct Stack : Table {
+    int blocks = 0;                   // ceil(rows / STK_BLOCK)
+    int *d_idx = nullptr;             // [B_plan][rows]: the row of failed ordinal f
+    int *d_count = nullptr;           // [B_plan]: failed rows
+  } stk;
   // fine (rfid_batch_plan_fine): lives and dies with the tracks workspace
   struct Fine : Table {
     rfid_read_fine *d_packed = nullptr;     // [trk.cap]: aligned with the tracks
   } fin;
   // What the per-call forms (rfid_repair_window, rfid_window_moments_of, rfid_commands_of, rfid_fine_window, rfid_retune_window, rfid_collisions_of,
-  // rfid_length_window, rfid_diversity_window, rfid_match_window) upload, compute on and download from.  One buffer for the nine: each synchronises c->stream before it returns, so no two of them ever have
+  // rfid_length_window, rfid_diversity_window, rfid_match_window, rfid_stack_windows) upload, compute on and download from.  One buffer for the ten: each synchronises c->stream before it returns, so no two of them ever have
   // work in flight on it, and grow() may free and reallocate it.
   DevBuf one;
   // How far the outputs on the device belong to the LAST pass: d_stats holds the statistics of the results in d_res
@@ -443,6 +451,7 @@ const KnobEntry g_knob_table[] = {
   {"lengths_wgs", "RFID_LENGTHS_WGS", &RfidKnobs::lengths_wgs, 0, 65536},
   {"diversity_wgs", "RFID_DIVERSITY_WGS", &RfidKnobs::diversity_wgs, 0, 65536},
   {"match_wgs", "RFID_MATCH_WGS", &RfidKnobs::match_wgs, 0, 65536},
+  {"stack_wgs", "RFID_STACK_WGS", &RfidKnobs::stack_wgs, 0, 65536},
 };
 int clamp_int(long v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); }
 // the environment, once per context: values out of range are clamped, anything that is not a number is ignored
@@ -526,7 +535,7 @@ void mark_current(rfid_ctx *c, int stage) { c->current = stage; }
 // `stage` and everything behind it no longer belong to the last pass
 void invalidate_from(rfid_ctx *c, int stage) { if (c->current >= stage) c->current = stage - 1; }
 
-// ---- what the inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths, diversity and match stages share on the host ----
+// ---- what the inventory, tracks, quality, repair, slots, commands, fine, retune, collisions, lengths, diversity, match and stack stages share on the host ----
 size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 void stage_free(rfid_ctx::Stage &st) {
@@ -774,6 +783,7 @@ void free_plan(rfid_ctx *c) {
   table_free(c->dvs);
   table_free(c->mat);
   c->mat.n_list = 0;
+  table_free(c->stk);
   invalidate_from(c, rfid_ctx::CUR_STATS);
   if (c->plan_blk) (void)hipFree(c->plan_blk);
   if (c->alt_blk) (void)hipFree(c->alt_blk);
@@ -804,7 +814,7 @@ int join_tails(rfid_ctx *c) {
   return RFID_OK;
 }
 
-// ---- the ten window-table stages (quality, repair, slots, commands, fine, retune, collisions, lengths, diversity, match): what their plan, enqueue and get functions share ----
+// ---- the eleven window-table stages (quality, repair, slots, commands, fine, retune, collisions, lengths, diversity, match, stack): what their plan, enqueue and get functions share ----
 // A stage's description: what its checks ask for and how its messages name it.
 struct TableStage {
   const char *name;      // as in rfid_batch_<name>
@@ -825,6 +835,7 @@ constexpr TableStage ST_DIVERSITY = {"diversity", false, false, rfid_ctx::CUR_ST
 // match: planned and, with a caller's list, enqueued as the lengths stage is; without a list enqueued as the repair stage is
 constexpr TableStage ST_MATCH = {"match", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
 constexpr TableStage ST_MATCH_OWN = {"match", true, false, rfid_ctx::CUR_INVENTORY, true, "EPC windows"};
+constexpr TableStage ST_STACK = {"stack", false, false, rfid_ctx::CUR_STATS, false, "EPC windows"};
 
 bool table_needs_met(const rfid_ctx *c, const TableStage &d) { return (!d.inv || c->inv.blk) && (!d.trk || c->trk.blk); }
 
@@ -1422,7 +1433,8 @@ int rfid_ctx_destroy(rfid_ctx *c) {
     if (e) (void)hipEventDestroy(e);
   for (rfid_ctx::Stage *st : {(rfid_ctx::Stage *)&c->inv, (rfid_ctx::Stage *)&c->trk, (rfid_ctx::Stage *)&c->qual, (rfid_ctx::Stage *)&c->rep,
                                (rfid_ctx::Stage *)&c->slt, (rfid_ctx::Stage *)&c->cmd, (rfid_ctx::Stage *)&c->fin, (rfid_ctx::Stage *)&c->ret,
-                               (rfid_ctx::Stage *)&c->col, (rfid_ctx::Stage *)&c->len, (rfid_ctx::Stage *)&c->dvs, (rfid_ctx::Stage *)&c->mat})
+                               (rfid_ctx::Stage *)&c->col, (rfid_ctx::Stage *)&c->len, (rfid_ctx::Stage *)&c->dvs, (rfid_ctx::Stage *)&c->mat,
+                               (rfid_ctx::Stage *)&c->stk})
     for (int i = 0; i < 2; ++i)
       if (st->ev[i]) (void)hipEventDestroy(st->ev[i]);
   if (c->stream2) {
@@ -2784,6 +2796,78 @@ int rfid_match_window(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_res
                      (const uint32_t *)(b + sz_w + sz_r), n_frames, (rfid_match *)(b + sz_w + sz_r + sz_f));
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r + sz_f, sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return RFID_OK;
+}
+
+// ---- stack stage: an unknown tag's repeated EPC frames combined over rounds, behind the statistics of a pass (csrc/rfid_stack.hpp) ----
+int rfid_batch_plan_stack(rfid_ctx *c) {
+  if (!c) return RFID_ERR_INVALID;
+  rfid_ctx::Stack &p = c->stk;
+  const int rows = (c->wmax + 1) / 2;      // EPC windows are every other window
+  const int r = table_plan(c, p, ST_STACK, rows,
+                           {{&p.d_table, sizeof(rfid_stack) * (size_t)rows * (size_t)c->B_plan},
+                            {(void **)&p.d_nrows, sizeof(int) * (size_t)c->B_plan},
+                            {(void **)&p.d_idx, sizeof(int) * (size_t)rows * (size_t)c->B_plan},
+                            {(void **)&p.d_count, sizeof(int) * (size_t)c->B_plan}});
+  if (r) return r;
+  p.blocks = (rows + STK_BLOCK - 1) / STK_BLOCK;
+  return RFID_OK;
+}
+
+static bool stack_rho_ok(float rho_min) { return rho_min > 0.0f && rho_min <= 1.0f; }      // (NaN fails both)
+
+int rfid_batch_stack(rfid_ctx *c, float rho_min) {
+  if (!c) return RFID_ERR_INVALID;
+  if (!stack_rho_ok(rho_min)) return fail(c, RFID_ERR_INVALID, "rfid_batch_stack: rho_min must be finite, above 0 and at most 1");
+  rfid_ctx::Stack &p = c->stk;
+  int n = 0;
+  StkArgs a;
+  { int r = table_begin(c, p, ST_STACK, &n, &a.p); if (r) return r; }
+  a.rows = p.rows; a.blocks = p.blocks; a.rho_min = rho_min; a.idx = p.d_idx; a.count = p.d_count; a.table = p.table<rfid_stack>(); a.nrows = p.d_nrows;
+  // the failed rows of every trace in row order (one wave per trace), then single-wave workgroups over blocks of 64 of them (32.5 KB of LDS each)
+  const int64_t most_i = c->knobs.stack_wgs ? (int64_t)c->knobs.stack_wgs : (int64_t)c->n_cus * STK_INDEX_WGS_PER_CU;
+  hipLaunchKernelGGL(stack_index_kernel, persistent_grid((int64_t)n, most_i), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  const int64_t items = (int64_t)n * p.blocks;
+  const int64_t most = c->knobs.stack_wgs ? (int64_t)c->knobs.stack_wgs : (int64_t)c->n_cus * STK_WGS_PER_CU;
+  hipLaunchKernelGGL(stack_kernel, persistent_grid(items, most), dim3(64), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return table_end(c, p, n);
+}
+
+int rfid_batch_get_window_stacks(rfid_ctx *c, int stream, rfid_stack *out, int64_t cap, int64_t *n) {
+  if (!c) return RFID_ERR_INVALID;
+  return table_get_rows(c, c->stk, ST_STACK, "rfid_batch_get_window_stacks", sizeof(*out), stream, out, cap, n);
+}
+
+int rfid_batch_stack_ms(rfid_ctx *c, float *ms) {
+  if (!c || !ms) return RFID_ERR_INVALID;
+  return stage_ms(c, c->stk, ms);
+}
+
+// the per-call form: up to 64 windows in host memory through the batch kernel's device functions (one launch, synchronising)
+int rfid_stack_windows(rfid_ctx *c, const rfid_cf32 *gated, const rfid_decode_result *res, int n, float rho_min, rfid_stack *out) {
+  if (!c || !gated || !res || !out) return RFID_ERR_INVALID;
+  if (n < 1 || n > STK_MAX_WINDOWS) return failf(c, RFID_ERR_INVALID, "rfid_stack_windows: 1 to %d windows", STK_MAX_WINDOWS);
+  if (!stack_rho_ok(rho_min)) return fail(c, RFID_ERR_INVALID, "rfid_stack_windows: rho_min must be finite, above 0 and at most 1");
+  for (int i = 0; i < n; ++i) {
+    if (res[i].type != RFID_DECODE_EPC) return failf(c, RFID_ERR_INVALID, "rfid_stack_windows: window %d: not the result of an EPC window", i);
+    if (res[i].index < 65 || res[i].index > 65 + N_SYNC - 1)
+      return failf(c, RFID_ERR_INVALID, "rfid_stack_windows: window %d: the result's index is no sync offset (65 .. 79)", i);
+    if (!(res[i].T >= STK_T_LO && res[i].T <= STK_T_HI))
+      return failf(c, RFID_ERR_INVALID, "rfid_stack_windows: window %d: the result's T is none of the decoder's (4.94999981 .. 5.05000019)", i);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t sz_w = up256(sizeof(float2) * (size_t)EPC_WIN * (size_t)n), sz_r = up256(sizeof(rfid_decode_result) * (size_t)n);
+  { int r = grow(c, c->one, sz_w + sz_r + sizeof(rfid_stack) * (size_t)n); if (r) return r; }
+  char *b = (char *)c->one.p;
+  HIPCHK(c, hipMemcpyAsync(b, gated, sizeof(float2) * (size_t)EPC_WIN * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(b + sz_w, res, sizeof(*res) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(stack_one_kernel, dim3(1), dim3(64), 0, c->stream, (const float2 *)b, (const rfid_decode_result *)(b + sz_w), n, rho_min,
+                     (rfid_stack *)(b + sz_w + sz_r));
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, b + sz_w + sz_r, sizeof(*out) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return RFID_OK;
 }

@@ -1,13 +1,13 @@
 // rfid_stage.hpp -- what the stages behind a batch pass decide in the same way, written once.  Every stage header includes
 // this file and, beside it, only the stage headers whose symbols it uses (the tracks: the inventory's table walk).
 //   stage_windows / stage_fetch   which windows of a trace count in a pass, how a result record is read and which records are
-//                                 reads (all twelve stages / inventory and tracks);
+//                                 reads (all thirteen stages / inventory and tracks);
 //   scan_share / scan_partials    the one-workgroup offsets scan (inventory, tracks; the repair stage takes the shares);
-//   StagePass                     what a pass left, as the ten window-table stages see it -- quality, repair, slots, commands,
-//                                 fine, retune, collisions, lengths, diversity, match: each fills one [trace][row] table (the diversity stage: [group][row]) of fixed-size records with a persistent grid of single-wave
+//   StagePass                     what a pass left, as the eleven window-table stages see it -- quality, repair, slots, commands,
+//                                 fine, retune, collisions, lengths, diversity, match, stack: each fills one [trace][row] table (the diversity stage: [group][row]) of fixed-size records with a persistent grid of single-wave
 //                                 workgroups, stage_windows gives the cut-off, rows behind it are zeroed, nrows[s] is written by
 //                                 the first pack.  How a table kernel loads, parks, sums and stores is its own (its header says why);
-//   epc_clamp / epc_gather        the decoder's half-bit gather of an EPC window (quality, repair, fine, diversity, match);
+//   epc_clamp / epc_gather        the decoder's half-bit gather of an EPC window (quality, repair, fine, diversity, match, stack);
 //   table_gather_kernel           the table's records of the CRC-verified reads, aligned with the tracks (quality, fine).
 // Only primitives both device environments offer.
 #pragma once
@@ -80,7 +80,7 @@ RFID_DEVICE int scan_partials(int *part, int tid, int nthr, int sum, int &total)
 }
 
 // ---- the window-table stages -----------------------------------------------------------------------------------------
-// What a pass left: the FIRST member of QualArgs, RepArgs, MomArgs, CmdArgs, FineArgs, RetArgs, ColArgs, LenArgs, DivArgs and MatArgs, filled by the host's table_begin.
+// What a pass left: the FIRST member of QualArgs, RepArgs, MomArgs, CmdArgs, FineArgs, RetArgs, ColArgs, LenArgs, DivArgs, MatArgs and StkArgs, filled by the host's table_begin.
 // (InvArgs and TrkArgs carry no y and another order: they stay their own.)
 struct StagePass {
   const float2 *y;                  // the matched filter's output of the pass

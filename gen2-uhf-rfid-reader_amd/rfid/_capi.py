@@ -122,6 +122,11 @@ MATCH_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("f
                         ("diff", "<i4"), ("frame", "<u4", (4,))])
 MATCH_MAX_LIST = 1024
 assert MATCH_DTYPE.itemsize == 64
+STACK_DTYPE = np.dtype([("stream", "<i4"), ("seq", "<i4"), ("start", "<i4"), ("flags", "<i4"), ("ordinal", "<i4"), ("n_partners", "<i4"),
+                        ("member_mask", "<u8"), ("sig_abs", "<f4"), ("margin_min", "<f4"), ("weakest", "<i4"), ("reserved_", "<i4"),
+                        ("frame", "<u4", (4,))])
+STACK_BLOCK, STACK_MAX_WINDOWS = 64, 64
+assert STACK_DTYPE.itemsize == 64
 GATE_FSM_IN_DTYPE = np.dtype([("mode", "<i4"), ("n_samples", "<i4"), ("signal_state", "<i4"), ("num_pulses", "<i4"),
                               ("gate_open", "<i4"), ("n_to_ungate", "<i4"), ("wtype", "<i4"), ("nvalid", "<i4"), ("pos", "<i4"),
                               ("reserved_", "<i4"), ("below", "<u8"), ("above", "<u8")])
@@ -279,6 +284,11 @@ SIGNATURES = {
     "rfid_batch_get_window_matches": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
     "rfid_batch_match_ms": (_i, [_vp, C.POINTER(C.c_float)]),
     "rfid_match_window": (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "rfid_batch_plan_stack": (_i, [_vp]),
+    "rfid_batch_stack": (_i, [_vp, C.c_float]),
+    "rfid_batch_get_window_stacks": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64)]),
+    "rfid_batch_stack_ms": (_i, [_vp, C.POINTER(C.c_float)]),
+    "rfid_stack_windows": (_i, [_vp, _vp, _vp, _i, C.c_float, _vp]),
     "rfid_batch_sync": (_i, [_vp]),
     "rfid_batch_timing_get": (_i, [_vp, C.POINTER(BatchTiming)]),
     "rfid_batch_get_stats": (_i, [_vp, _vp, _i]),

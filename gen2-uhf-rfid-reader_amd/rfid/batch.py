@@ -65,6 +65,8 @@ class BatchDecoder:
         self.last_diversity = None    # one diversity array per GROUP (every EPC window before its anchor's cut-off) of the last decode(..., diversity=M)
         self._mat_planned = False
         self.last_matches = None      # one match array per trace (every EPC window before the cut-off) of the last decode(..., match=True)
+        self._stk_planned = False
+        self.last_stacks = None       # one stack array per trace (every EPC window before the cut-off) of the last decode(..., stack=rho)
 
     def close(self) -> None:
         self.ctx.close()
@@ -87,6 +89,7 @@ class BatchDecoder:
             self._len_planned = False
             self._div_members = 0
             self._mat_planned = False
+            self._stk_planned = False
         # the plan may be larger than this batch (decoder reuse): process exactly n_traces rows
         self.ctx.batch_set_streams(n_traces)
         need = n_traces * stride * 2
@@ -99,7 +102,7 @@ class BatchDecoder:
                inventory: bool = False, max_tags: int = 64, tracks: bool = False, quality: bool = False,
                repair: bool = False, slots: bool = False, commands: bool = False, fine: bool = False,
                retune: bool = False, collisions: bool = False, lengths: bool = False, diversity: int = 0,
-               match: bool = False, match_list=None):
+               match: bool = False, match_list=None, stack: float = 0.0):
         """traces: list of complex64 arrays (ragged).  Returns (stats, windows, results, scores).
 
         `timing` (optional dict) receives h2d_s / gpu_s / total_s of this call.  inventory=True: the distinct EPC frames
@@ -139,7 +142,10 @@ class BatchDecoder:
         against the frames of known tags -- match_list=frames, (n, 4) words as frame_of_epc() builds them, the same for every trace, or
         without a list every trace's own inventory (then it implies inventory=True); `self.last_matches` keeps one capi.MATCH_DTYPE
         array per trace, a record per EPC window (match_fields() says which are attributions); an attribution is not a read and
-        changes nothing else."""
+        changes nothing else.  stack=rho (0 < rho <= 1; 0: off): the CRC-failed EPC windows of a trace whose decision values correlate
+        (s >= rho * a, within blocks of 64 failed windows) are added up behind the pass before the sign is taken -- an unknown tag's
+        repeated frame over the rounds of a session; `self.last_stacks` keeps one capi.STACK_DTYPE array per trace, a record per EPC
+        window (stack_fields() turns it into flags and member lists); a stacked frame is not a read and changes nothing else."""
         torch = self._torch
         n = len(traces)
         match = bool(match) or match_list is not None
@@ -207,6 +213,9 @@ class BatchDecoder:
                 self.ctx.batch_plan_match()
                 self._mat_planned = True
             self.ctx.batch_match_set_list(None if own_match else match_list)
+        if stack and not self._stk_planned:
+            self.ctx.batch_plan_stack()
+            self._stk_planned = True
         self.ctx.batch_process_ptr(dev.data_ptr(), stride, max_len, self._lens_dev.data_ptr(), want_scores=want_scores)
         if inventory:
             self.ctx.batch_inventory_enqueue()
@@ -232,6 +241,8 @@ class BatchDecoder:
             self.ctx.batch_diversity_enqueue()
         if match:
             self.ctx.batch_match_enqueue()
+        if stack:
+            self.ctx.batch_stack_enqueue(float(stack))
         self.ctx.batch_sync()
         t2 = time.perf_counter()
         if inventory:
@@ -258,6 +269,8 @@ class BatchDecoder:
             self.last_diversity = [self.ctx.batch_window_diversity(g) for g in range(n // diversity)]
         if match:
             self.last_matches = [self.ctx.batch_window_matches(b) for b in range(n)]
+        if stack:
+            self.last_stacks = [self.ctx.batch_window_stacks(b) for b in range(n)]
         stats = self.ctx.batch_stats()[:n]
         w, r, s = self.ctx.batch_windows(want_scores=want_scores)
         if timing is not None:
@@ -736,6 +749,69 @@ def read_epc_list(path: str) -> np.ndarray:
     return np.array(frames, dtype=np.uint32).reshape(-1, 4)
 
 
+STACK_HEADER = "file,epc,pc,seq,t_s,n_members,member_seqs,margin_min,weakest,known"
+STACK_MIN_RHO = 0.5       # the default of --stack-min (DESIGN.md derives it)
+
+
+def stack_fields(rows: np.ndarray) -> dict:
+    """rfid_stack records of ONE trace, in seq order -> a dict, one value per record: read (flags bit 0), failed (not a read), stacked
+    (bit 1: the window has partners and a combination was formed), passed (bit 2: the combination's CRC holds -- the acceptance
+    test; rho_min only decides what is added up), members: the indices INTO rows of the record's members in ascending order, its
+    own among them (empty for a read), and member_seqs: their seq."""
+    rows = np.asarray(rows)
+    flags = rows["flags"]
+    read = (flags & 1) != 0
+    where = np.flatnonzero(~read)                                  # ordinal f -> index into rows
+    members = []
+    for r, is_read in zip(rows, read):
+        base = (int(r["ordinal"]) // capi.STACK_BLOCK) * capi.STACK_BLOCK
+        members.append([] if is_read else [int(where[base + l]) for l in range(capi.STACK_BLOCK)
+                                           if (int(r["member_mask"]) >> l) & 1 and base + l < len(where)])
+    return dict(read=read, failed=~read, stacked=(flags & 2) != 0, passed=(flags & 4) != 0, members=members,
+                member_seqs=[[int(rows[i]["seq"]) for i in m] for m in members])
+
+
+def stack_known(rows: np.ndarray, entries: np.ndarray) -> np.ndarray:
+    """Host side: per record of one trace's stack rows, whether its combination passes the CRC AND the trace's inventory (`entries`:
+    capi.TAG_ENTRY_DTYPE records, Context.batch_inventory) holds that frame."""
+    rows = np.asarray(rows)
+    have = {bytes(np.ascontiguousarray(f)) for f in np.asarray(entries)["frame"]}
+    return np.array([bool(r["flags"] & 4) and bytes(np.ascontiguousarray(r["frame"])) in have for r in rows], dtype=bool)
+
+
+def format_stack(rows: np.ndarray, entries: np.ndarray) -> str:
+    """One line for one trace's EPC windows before the cut-off (Context.batch_window_stacks) and its inventory: how many windows, how
+    many failed, how many of those were stacked with partners, how many combinations pass the CRC, how many distinct EPCs those are
+    and how many of them the inventory lacks -- tags the decoder did not read once."""
+    rows = np.asarray(rows)
+    f = stack_fields(rows)
+    known = stack_known(rows, entries)
+    frames = {bytes(np.ascontiguousarray(r["frame"])) for r in rows[f["passed"]]}
+    new = {bytes(np.ascontiguousarray(r["frame"])) for r in rows[f["passed"] & ~known]}
+    return ("| EPC windows : %d  failed : %d  stacked : %d  combinations that pass the CRC : %d  distinct EPCs : %d  "
+            "not in the inventory : %d\n" % (len(rows), int(f["failed"].sum()), int(f["stacked"].sum()), int(f["passed"].sum()),
+                                             len(frames), len(new)))
+
+
+def format_stack_csv(rows: Sequence[np.ndarray], entries: Sequence[np.ndarray], names: Sequence[str]) -> str:
+    """CSV text, one line per window whose combination passes the CRC, by trace, then by seq: file,epc,pc,seq,t_s,n_members,
+    member_seqs,margin_min,weakest,known.  rows[b]: the rfid_stack records of trace b; entries[b]: its inventory; names[b]: its file.
+    epc / pc of the COMBINED frame, t_s = start / 400e3 as in the tracks CSV, member_seqs: the members' seq joined by +, the window's own
+    among them, margin_min with %.9g (a binary32 value survives the round trip), known: 1 when the trace's inventory holds the frame."""
+    lines = [STACK_HEADER]
+    for rec, ents, name in zip(rows, entries, names):
+        rec = np.asarray(rec)
+        f = stack_fields(rec)
+        known = stack_known(rec, ents)
+        for k in np.flatnonzero(f["passed"]):
+            r = rec[k]
+            pc, epc = frame_fields(r["frame"])
+            lines.append("%s,%s,%04x,%d,%.9g,%d,%s,%.9g,%d,%d" %
+                         (name, epc, pc, int(r["seq"]), int(r["start"]) / TRACKS_RATE, len(f["members"][k]),
+                          "+".join(map(str, f["member_seqs"][k])), float(r["margin_min"]), int(r["weakest"]), int(known[k])))
+    return "\n".join(lines) + "\n"
+
+
 MOMENTS_N = 240           # RFID_MOMENTS_SAMPLES: the samples of a window its moments are taken over
 SLOT_EMPTY, SLOT_SINGLE, SLOT_COLLIDED, SLOT_UNKNOWN = 0, 1, 2, -1
 SCHOUTE = 2.39            # Schoute's estimate of the tags behind a collided slot of a framed-ALOHA round
@@ -978,7 +1054,7 @@ def format_commands_csv(rows: Sequence[np.ndarray], starts: Sequence[np.ndarray]
 
 
 def main(argv=None) -> int:
-    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] [--collisions OUT.csv] [--lengths OUT.csv] [--antennas M --diversity OUT.csv] [--match OUT.csv [--match-list EPCS.txt] [--match-min RHO]] TRACE_FILE...  -- decode recorded traces in one batched pass."""
+    """python -m rfid.batch [--device N] [--fixed-q Q] [--inventory [--max-tags N]] [--tracks OUT.csv] [--quality] [--repair OUT.csv] [--slots OUT.csv] [--commands OUT.csv] [--fine] [--retune OUT.csv] [--collisions OUT.csv] [--lengths OUT.csv] [--antennas M --diversity OUT.csv] [--match OUT.csv [--match-list EPCS.txt] [--match-min RHO]] [--stack OUT.csv [--stack-min RHO]] TRACE_FILE...  -- decode recorded traces in one batched pass."""
     import argparse
     ap = argparse.ArgumentParser(prog="python -m rfid.batch", description=main.__doc__)
     ap.add_argument("files", nargs="+")
@@ -1036,7 +1112,18 @@ def main(argv=None) -> int:
                          % capi.MATCH_MAX_LIST)
     ap.add_argument("--match-min", metavar="RHO", type=float, default=MATCH_MIN_RHO,
                     help="with --match: the least score / sum |r| of an attribution (default %.1f)" % MATCH_MIN_RHO)
+    ap.add_argument("--stack", metavar="OUT.csv", default=None,
+                    help="add up the CRC-failed EPC windows of a file that hold the same frame (found by the correlation of their "
+                         "decision values, built on the device): finds tags too weak in every round that nobody knows; per file the "
+                         "failed windows, how many were stacked, how many combinations pass the CRC, how many distinct EPCs those "
+                         "are and how many the inventory lacks, the windows whose combination passes to this CSV file (implies "
+                         "--inventory, for the known column only)")
+    ap.add_argument("--stack-min", metavar="RHO", type=float, default=STACK_MIN_RHO,
+                    help="with --stack: the least correlation s / a of two windows that are added up, above 0 and at most 1 "
+                         "(default %.1f); the CRC decides what is a frame" % STACK_MIN_RHO)
     args = ap.parse_args(argv)
+    if args.stack and not 0.0 < args.stack_min <= 1.0:
+        ap.error("--stack-min: above 0 and at most 1")
     match_list = None
     if args.match_list:
         if not args.match:
@@ -1046,7 +1133,7 @@ def main(argv=None) -> int:
             ap.error("--match-list: 1 to %d EPCs" % capi.MATCH_MAX_LIST)
     if args.diversity and (not 2 <= args.antennas <= capi.DIVERSITY_MAX_MEMBERS or len(args.files) % args.antennas):
         ap.error("--diversity: the files must be whole captures of --antennas M = 2..%d files each" % capi.DIVERSITY_MAX_MEMBERS)
-    if args.tracks or args.repair or args.retune or args.diversity or (args.match and match_list is None):
+    if args.tracks or args.repair or args.retune or args.diversity or args.stack or (args.match and match_list is None):
         args.inventory = True
     dec = BatchDecoder(device=args.device, fixed_q=args.fixed_q, max_num_queries=args.max_queries)
     try:
@@ -1056,7 +1143,8 @@ def main(argv=None) -> int:
                                             slots=bool(args.slots), commands=bool(args.commands), fine=args.fine,
                                             retune=bool(args.retune), collisions=bool(args.collisions),
                                             lengths=bool(args.lengths), diversity=args.antennas if args.diversity else 0,
-                                            match=bool(args.match), match_list=match_list)
+                                            match=bool(args.match), match_list=match_list,
+                                            stack=args.stack_min if args.stack else 0.0)
         collided = ([classify_collisions(c, classify_slots(m)) for c, m in zip(dec.last_collisions, dec.last_slots)]
                     if args.collisions else None)
         by_seq = [results[windows["stream"] == b] for b in range(len(args.files))] if args.match else None   # (ordered by seq)
@@ -1082,6 +1170,8 @@ def main(argv=None) -> int:
                 print(format_lengths(dec.last_lengths[i]), end="")
             if args.match:
                 print(format_match(dec.last_matches[i], by_seq[i], args.match_min), end="")
+            if args.stack:
+                print(format_stack(dec.last_stacks[i], per_trace(*dec.last_inventory)[i]), end="")
             if args.diversity and i % args.antennas == 0:           # (the group's line stands with its anchor)
                 print(format_diversity(dec.last_diversity[i // args.antennas], per_trace(*dec.last_inventory)[i:i + args.antennas]), end="")
         print("%d traces, %.1f M raw samples: %.3f s (host->HBM %.3f s, GPU pass %.4f s)" %
@@ -1127,6 +1217,9 @@ def main(argv=None) -> int:
         if args.match:
             with open(args.match, "w") as f:
                 f.write(format_match_csv(dec.last_matches, args.files, by_seq, args.match_min))
+        if args.stack:
+            with open(args.stack, "w") as f:
+                f.write(format_stack_csv(dec.last_stacks, per_trace(*dec.last_inventory), args.files))
         if args.commands:
             starts = [windows["start"][windows["stream"] == b] for b in range(len(args.files))]     # (ordered by seq)
             with open(args.commands, "w") as f:

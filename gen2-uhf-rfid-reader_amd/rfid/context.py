@@ -798,6 +798,42 @@ class Context:
         self._chk(self._lib.rfid_match_window(self._h, gated.ctypes.data, res.ctypes.data, f.ctypes.data, len(f), out.ctypes.data))
         return out[0]
 
+    def batch_plan_stack(self) -> None:
+        """Reserves the stack workspace of the current plan (a new plan drops it; no other stage's plan call does)."""
+        self._chk(self._lib.rfid_batch_plan_stack(self._h))
+
+    def batch_stack_enqueue(self, rho_min: float = 0.5) -> None:
+        """Asynchronous: the CRC-failed EPC windows of the last pass that hold the same frame found by the correlation of their
+        decision values (s >= rho_min * a, 0 < rho_min <= 1) and combined before the sign is taken (rfid_batch_stack): behind
+        the pass's statistics, as the match stage with a list."""
+        self._chk(self._lib.rfid_batch_stack(self._h, float(rho_min)))
+
+    def batch_window_stacks(self, stream: int, extra: int = 0) -> np.ndarray:
+        """One trace's row of the stack table (synchronises): the capi.STACK_DTYPE record of EVERY EPC window before the cut-off,
+        in seq order (n_windows_used // 2 of them), of the last batch_stack_enqueue: flags bit 0 = the window was a read, bit 1 =
+        a combination was formed (the window has partners: member_mask, bit l = failed row 64 * (ordinal // 64) + l), bit 2 = the
+        combination's CRC holds and `frame` is a frame.  extra > 0: up to that many of the table's rows behind them as well
+        (zeroed by the stage)."""
+        return self._window_rows(self._lib.rfid_batch_get_window_stacks, capi.STACK_DTYPE, stream, extra)
+
+    def batch_stack_ms(self) -> float:
+        return self._stage_ms(self._lib.rfid_batch_stack_ms)
+
+    def stack_windows(self, gated, results, rho_min: float = 0.5) -> np.ndarray:
+        """The same for n = 1 .. capi.STACK_MAX_WINDOWS windows in host memory, one block (rfid_stack_windows): gated = (n, 1370)
+        DC-free samples, results = the windows' capi.RESULT_DTYPE records.  -> n capi.STACK_DTYPE records, stream = seq = start = 0."""
+        gated = np.ascontiguousarray(gated, dtype=np.complex64)
+        if gated.ndim != 2 or gated.shape[1] != 1370 or not 1 <= gated.shape[0] <= capi.STACK_MAX_WINDOWS:
+            raise ValueError("gated must be (n, 1370), n = 1 .. %d" % capi.STACK_MAX_WINDOWS)
+        if len(results) != len(gated):
+            raise ValueError("one result record per window")
+        res = np.zeros(len(gated), dtype=capi.RESULT_DTYPE)
+        for i, r in enumerate(results):
+            res[i] = r
+        out = np.zeros(len(gated), dtype=capi.STACK_DTYPE)
+        self._chk(self._lib.rfid_stack_windows(self._h, gated.ctypes.data, res.ctypes.data, len(gated), float(rho_min), out.ctypes.data))
+        return out
+
     def batch_mf_output(self, stream: int) -> np.ndarray:
         cap = self._planned[1] // 5 + 1
         out = np.empty(cap, dtype=np.complex64)

@@ -400,6 +400,49 @@ typedef struct rfid_match {          /* 64 bytes */
   uint32_t frame[4];                 /* best's frame, packed as rfid_decode_result::bits; zeros when none */
 } rfid_match;
 
+/* what the stack stage (rfid_batch_stack, rfid_stack_windows) finds for one EPC window: the CRC-failed windows near it that hold the
+ * SAME frame, and what their decision values add up to.  Repair and retune work on one window alone, diversity needs several
+ * antennas, match needs the tag's EPC.  A tag too weak in every round that nobody knows is asked for the same 128-bit frame round
+ * after round: two failed windows that hold the same frame have strongly correlated decision values, two that hold different
+ * frames, noise or collisions uncorrelated ones.  Adding the r_j of the windows that correlate, before the sign is taken, is
+ * maximum-ratio combining over rounds (each r_j carries its own conj(h_est)); the CRC-16 then decides whether the sum is a frame.
+ * rho_min is a DETECTION threshold; the CRC is the acceptance test.  A stacked frame is NOT a read: nothing else the library
+ * reports changes.
+ * THE DEFINITION (the contract; binary32 throughout, every operation rounded by itself, no fused multiply-add, every sum in order
+ * from 0.0f, every tie to the lower index), for the EPC windows of a trace with seq < n_windows_used:
+ *   failed rows  the EPC windows whose result is not a verified read (type EPC and crc_ok = 1 is one), in row order, numbered
+ *                f = 0 .. F - 1: the ordinals.
+ *   blocks       block q holds ordinals 64 q .. 64 q + 63 (RFID_STACK_BLOCK).  Partners are sought inside a window's own block only:
+ *                the work on a trace with 100 000 failed windows stays bounded, and at one reply per tag and round 64
+ *                consecutive failed windows span many rounds.
+ *   r^f_j        j = 0 .. 127, the decision values of row f exactly as in the rfid_read_quality definition above (from the
+ *                window's own start, dc, T, index and h_re, h_im).
+ *   partner      for rows f != g of one block: s = sum_j (r^f_j * r^g_j), a = sum_j |r^f_j * r^g_j| (each product rounded once and
+ *                used in both sums).  g is a partner of f iff s > 0 and s >= rho_min * a (the product on the right rounded once).
+ *                The relation is symmetric bit for bit.
+ *   members(f)   f together with its partners: member_mask has bit l set for ordinal 64 q + l, f's own bit included; n_partners
+ *                = popcount - 1.  Without a partner nothing is combined: flags = 0 and every field behind member_mask is 0.
+ *   combination  R_j = the sum of r^m_j over the members in ascending ordinal, the anchor in its place; the decoder's own sign chain
+ *                (bit_j = (R_j > 0) XOR (R_(j-1) > 0), the sign in front of the first one positive) and CRC-16 over R.  sig_abs
+ *                = sum_j |R_j|; margin_min = min_j |R_j|, weakest the lowest j that attains it.
+ * Rows behind a trace's cut-off are zero.  A window with a non-finite sample: unspecified, as its decoding is. */
+#define RFID_STACK_BLOCK 64
+#define RFID_STACK_MAX_WINDOWS 64
+typedef struct rfid_stack {          /* 64 bytes */
+  int32_t  stream, seq, start;       /* the EPC window */
+  int32_t  flags;                    /* bit 0: the window is a verified read (ordinal = -1, everything behind it 0)
+                                        bit 1: a combination was formed (at least one partner)
+                                        bit 2: the combination's CRC holds */
+  int32_t  ordinal;                  /* f; -1 for a read */
+  int32_t  n_partners;
+  uint64_t member_mask;              /* bit l: ordinal 64 (f / 64) + l is a member; the window's own bit included */
+  float    sig_abs;                  /* sum |R_j| */
+  float    margin_min;               /* min |R_j| */
+  int32_t  weakest;                  /* the lowest j with |R_j| = margin_min */
+  int32_t  reserved_;                /* 0 */
+  uint32_t frame[4];                 /* the combination's 128 bits whenever bit 1 is set, packed as rfid_decode_result::bits */
+} rfid_stack;
+
 /* what the collisions stage (rfid_batch_collisions, rfid_collisions_of) works out for one RN16 window: the two RN16s and the two
  * channels of a slot in which two tags replied at once.  The decoder is single-tag by construction (tag_detection_RN16,
  * lib/tag_decoder_impl.cc:114-142, 237-253): decision j is the difference d_j of two adjacent half-bit samples across a bit
@@ -1240,6 +1283,32 @@ RFID_API int rfid_batch_match_ms(rfid_ctx *ctx, float *ms);
  * flags bit 3 set; bit 0 = res->crc_ok (then nothing is searched). */
 RFID_API int rfid_match_window(rfid_ctx *ctx, const rfid_cf32 *gated, const rfid_decode_result *res, const uint32_t *frames, int n_frames,
                                rfid_match *out);
+/* ---- (2n) batch stack: an unknown tag's repeated EPC frames combined over rounds, built on the device ----------------------------- */
+/* Behind a pass: one rfid_stack (see its definition above) per EPC window with seq < n_windows_used in a device table
+ * [n_streams][ceil(wmax / 2)] (row = seq >> 1; rows behind a trace's cut-off are zeroed: the table's bytes repeat from pass to pass).
+ * Needs no antenna beside the trace's own and no list of known tags.  Nothing else a pass reports changes: a stacked frame is not a
+ * read.  rfid_batch_plan_stack reserves the table (64 bytes per possible EPC window) and the list of failed rows (4 bytes each).
+ * RFID_ERR_STATE without a plan; RFID_ERR_HIP when the allocation fails (the plan and every other workspace stay usable).  A new
+ * rfid_batch_plan drops it; it drops no other stage's workspace, and their plan calls do not drop it. */
+RFID_API int rfid_batch_plan_stack(rfid_ctx *ctx);
+/* enqueues the stack stage of the LAST pass (asynchronous, no host synchronisation) with the partner threshold rho_min.
+ * RFID_ERR_INVALID unless rho_min is finite and 0 < rho_min <= 1 (nothing is enqueued).  It needs the pass's statistics only, as
+ * rfid_batch_match with a list does, and has its state rules and stream duties: it may be enqueued before or behind the other
+ * stages and neither raises nor lowers their level.  ONE table per plan, as rfid_batch_commands. */
+RFID_API int rfid_batch_stack(rfid_ctx *ctx, float rho_min);
+/* synchronises; one trace's row of the table: every EPC window before the cut-off in seq order: *n = n_windows_used / 2.  cap as
+ * rfid_batch_get_window_quality.  RFID_ERR_STATE before the first rfid_batch_stack of this plan; RFID_ERR_INVALID for a trace the
+ * last rfid_batch_stack did not cover. */
+RFID_API int rfid_batch_get_window_stacks(rfid_ctx *ctx, int stream, rfid_stack *out, int64_t cap, int64_t *n);
+/* synchronises; device time of the last rfid_batch_stack (HIP events) */
+RFID_API int rfid_batch_stack_ms(rfid_ctx *ctx, float *ms);
+/* the same for n = 1 .. RFID_STACK_MAX_WINDOWS windows in host memory, one block: the per-call form.  gated: [n][1370] samples,
+ * DC-free already (dc = 0 in the definition); res: [n] the results rfid_decoder_work gave for them; out: [n] records, out[i] for
+ * window i, stream = seq = start = 0.  A window whose res has crc_ok = 1 is a read (bit 0) and takes no ordinal; the others get
+ * their ordinals in the order given.  RFID_ERR_INVALID: n outside 1 .. 64, rho_min as for rfid_batch_stack, or a result that
+ * rfid_match_window would refuse (type, index 65 .. 79, T inside 4.94999981 .. 5.05000019).  One launch of the batch kernel's device
+ * functions, synchronising. */
+RFID_API int rfid_stack_windows(rfid_ctx *ctx, const rfid_cf32 *gated, const rfid_decode_result *res, int n, float rho_min, rfid_stack *out);
 /* the HIP stream the ctx launches on (hipStream_t as void*) */
 RFID_API void *rfid_ctx_stream(rfid_ctx *ctx);
 
